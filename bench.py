@@ -14,10 +14,14 @@ GPUs): the samples of every step are split over the ranks (pathed_amd/parallel.s
 adds into its own sums, and ONE RCCL reduce to rank 0 closes the timed region.  --scaling weak fixes the
 per-GPU work instead.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with, besides the headline value:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints it; with --full
+the line also carries, besides the headline value:
   roofline      what bounds the pipeline on this workload, with a denominator measured on this box
+                (a counting pass, HIP-event timing of the launches, probes and the large-BVH leg)
   cpu_baseline  the CPU oracle (a port of the reference estimator; the reference binary cannot be
                 built) timed on the host cores, bounded sample   [N = 1 only]
+Without --full both are null.  --dump-outputs DIR writes the radiance sums of the timed steps as
+DIR/radiance_sums.npy (float32, H x W x 3), so that two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -60,14 +64,19 @@ def parse_args():
                         help="rehearsal on a one-GPU box: every rank renders on device 0 (use with --backend gloo: RCCL refuses two ranks on one device)")
     parser.add_argument("--dist-single", action="store_true",
                         help="run the single-GPU bench as a ONE-rank process group: init, barrier, reduce and all_gather of the N > 1 path execute (RCCL rehearsal on a one-GPU box)")
-    parser.add_argument("--no-cpu-baseline", action="store_true")
+    parser.add_argument("--full", action="store_true",
+                        help="also measure what the headline figure does not need: the roofline block (counting pass, kernel timing, "
+                             "probes, large-BVH leg) and the CPU baseline; a plain run times the steps and nothing else")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write the radiance sums they computed as DIR/radiance_sums.npy (float32)")
+    parser.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
     parser.add_argument("--no-large-bvh", action="store_true",
-                        help="skip the second, BVH-traversal-bound workload (scenes/dragon-standin.json) behind roofline.large_bvh")
+                        help="with --full: skip the second, BVH-traversal-bound workload (scenes/dragon-standin.json) behind roofline.large_bvh")
     parser.add_argument("--large-bvh-subdiv", type=int, default=10, help="icosphere subdivisions of the stand-in mesh: 9 = 5.2 M, 10 = 21 M triangles")
     parser.add_argument("--time-every-launch", action="store_true",
-                        help="HIP events around every trace / shade launch instead of every 8th")
+                        help="with --full: HIP events around every trace / shade launch instead of every 8th")
     parser.add_argument("--no-kernel-timing", action="store_true",
-                        help="no HIP-event timing of kernel launches (the roofline block becomes null)")
+                        help="with --full: no HIP-event timing of kernel launches (the roofline block becomes null)")
     parser.add_argument("--allow-overrides", action="store_true",
                         help="run although PATHED_* variables are set in the environment (they are listed in the line either way: "
                              "PATHED_HIP_LIB selects another library, the experiments build honours tuning variables)")
@@ -338,6 +347,24 @@ def kernel_rates(counted, counted_samples, timed, timed_samples):
     }
 
 
+def dump_outputs(directory, name, array, budget=60 * 1000 * 1000):
+    """--dump-outputs: DIR/<name>.npy in float32.  An array of more than `budget` bytes is written as a fixed, seeded sample of
+    its rows (the last axis kept whole), with the row indices beside it in DIR/<name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    data = np.ascontiguousarray(array, dtype=np.float32)
+    index_path = os.path.join(directory, name + "_rows.npy")
+    if os.path.exists(index_path):
+        os.remove(index_path)
+    if data.nbytes > budget:
+        rows = data.reshape(-1, data.shape[-1])
+        keep = budget // (rows.shape[1] * 4 + 8)
+        index = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+        np.save(index_path, index.astype(np.float64))
+        data = rows[index]
+    np.save(os.path.join(directory, name + ".npy"), data)
+
+
 def ensure_large_bvh_mesh(args):
     """The stand-in mesh is generated on the box (the 100 MB file does not travel with the snapshot) -- by a child
     process, so this runs BEFORE this process makes its first GPU call."""
@@ -510,7 +537,8 @@ def run_rank(args):
     rank = int(os.environ.get("RANK", "0"))
     local_rank = 0 if args.share_gpu else int(os.environ.get("LOCAL_RANK", "0"))
     distributed = world_size > 1 or args.dist_single
-    wants_large_bvh = (world_size == 1 and not args.no_large_bvh and not args.no_kernel_timing and args.scene == "scenes/cornell.json")
+    wants_large_bvh = (args.full and world_size == 1 and not args.no_large_bvh and not args.no_kernel_timing
+                       and args.scene == "scenes/cornell.json")
     if wants_large_bvh and rank == 0:
         ensure_large_bvh_mesh(args)   # a child process: before anything here touches the GPU
     if not torch.cuda.is_available():
@@ -556,8 +584,8 @@ def run_rank(args):
     # one untimed, counting pass over the first timed step's samples: exact ray / box / triangle counts
     counted = None
     counted_samples = 0
-    timing = not args.no_kernel_timing
-    if rank == 0 and timing:   # (a PMC run passes --no-kernel-timing: nothing but the timed path's kernels then)
+    timing = args.full and not args.no_kernel_timing
+    if rank == 0 and timing:   # (a plain run, like a PMC run, launches nothing but the timed path's kernels)
         gpu.set_stats_mode(count=True)
         gpu.reset_stats()
         scratch = torch.zeros_like(accum)
@@ -622,6 +650,8 @@ def run_rank(args):
         elapsed = max(row[2] for row in per_rank)   # MAX over ranks
 
     timed = gpu.stats()
+    if rank == 0 and args.dump_outputs:   # rank 0 holds the reduced sums
+        dump_outputs(args.dump_outputs, "radiance_sums", accum.cpu().numpy())
 
     if rank == 0:
         pixels = args.width * args.height
@@ -731,7 +761,7 @@ def run_rank(args):
 
         baseline = None
         # the CPU oracle is timed on rank 0 of the single-GPU run only
-        if not args.no_cpu_baseline and world_size == 1:
+        if args.full and not args.no_cpu_baseline and world_size == 1:
             baseline = cpu_baseline(scene, args)
 
         mean = (accum / float(total_spp)).mean(dim=(0, 1)).tolist()

@@ -48,3 +48,27 @@ def test_default_arguments_are_the_baseline_configuration():
         sys.argv = sys_argv
     assert (args.gpus, args.scene, args.width, args.height, args.spp_per_step, args.steps) == (1, "scenes/cornell.json", 1024, 1024, 1024, 4)
     assert args.scaling == "strong" and args.backend == "nccl" and args.large_bvh_subdiv == 10
+    assert args.full is False and args.dump_outputs is None
+
+
+def test_dump_outputs_writes_float32_and_samples_what_is_over_the_budget(tmp_path):
+    """--dump-outputs: an array within the budget is written whole in float32; a larger one as a fixed, seeded sample of its
+    rows (the same rows every time), with the row indices beside it, and both files together stay within the budget."""
+    import numpy as np
+    import bench
+    sums = np.arange(48 * 64 * 3, dtype=np.float64).reshape(48, 64, 3)
+    bench.dump_outputs(str(tmp_path), "radiance_sums", sums)
+    written = np.load(str(tmp_path / "radiance_sums.npy"))
+    assert written.dtype == np.float32 and written.shape == (48, 64, 3) and np.array_equal(written, sums.astype(np.float32))
+    assert not (tmp_path / "radiance_sums_rows.npy").exists()
+    budget = 4000
+    bench.dump_outputs(str(tmp_path), "radiance_sums", sums, budget=budget)
+    sample = np.load(str(tmp_path / "radiance_sums.npy"))
+    rows = np.load(str(tmp_path / "radiance_sums_rows.npy"))
+    assert sample.dtype == np.float32 and rows.dtype == np.float64 and sample.shape == (len(rows), 3)
+    assert sample.nbytes + rows.nbytes <= budget and len(rows) > 0 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(sample, sums.reshape(-1, 3)[rows.astype(np.int64)].astype(np.float32))
+    bench.dump_outputs(str(tmp_path), "radiance_sums", sums, budget=budget)
+    assert np.array_equal(np.load(str(tmp_path / "radiance_sums_rows.npy")), rows)
+    bench.dump_outputs(str(tmp_path), "radiance_sums", sums)   # whole again: no stale row indices left beside it
+    assert not (tmp_path / "radiance_sums_rows.npy").exists()

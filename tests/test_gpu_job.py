@@ -308,7 +308,8 @@ def test_bench_line_carries_the_contract_fields():
     issue) -- and a `cpu_baseline` that states its cores, the host's quota and the rate at every thread count it tried."""
     import sys
     from pathed_amd import _capi
-    command = [sys.executable, os.path.join(_capi.REPO_ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--spp-per-step", "64", "--no-large-bvh"]
+    command = [sys.executable, os.path.join(_capi.REPO_ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--spp-per-step", "64", "--no-large-bvh",
+               "--full"]
     result = subprocess.run(command, capture_output=True, text=True, timeout=900)
     assert result.returncode == 0, result.stdout + result.stderr
     lines = [text for text in result.stdout.strip().splitlines() if text.startswith("{")]
@@ -333,3 +334,23 @@ def test_bench_line_carries_the_contract_fields():
     assert cpu["cores"] == cpu["threads"] <= cpu["host"]["usable"] and len(cpu["thread_counts_tried"]) >= 1
     assert all(entry["spp"] >= 2 for entry in cpu["thread_counts_tried"])
     assert max(entry["Msamples_per_s"] for entry in cpu["thread_counts_tried"]) > 0
+
+
+def test_plain_bench_times_the_steps_only_and_dumps_what_they_computed(tmp_path):
+    """A plain bench.py run (no --full) carries the headline and nothing it does not need: no roofline, no cpu_baseline.
+    --dump-outputs writes the radiance sums of the timed steps, and two runs with the same arguments render the same samples."""
+    import sys
+    from pathed_amd import _capi
+    dumps = []
+    for run in ("a", "b"):
+        command = [sys.executable, os.path.join(_capi.REPO_ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--spp-per-step", "16",
+                   "--width", "96", "--height", "64", "--dump-outputs", str(tmp_path / run)]
+        result = subprocess.run(command, capture_output=True, text=True, timeout=600)
+        assert result.returncode == 0, result.stdout + result.stderr
+        line = json.loads(result.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["roofline"] is None and line["cpu_baseline"] is None
+        sums = np.load(str(tmp_path / run / "radiance_sums.npy"))
+        assert sums.dtype == np.float32 and sums.shape == (64, 96, 3) and np.all(np.isfinite(sums))
+        assert np.allclose((sums.astype(np.float64) / (3 * 16)).mean(axis=(0, 1)), line["image_mean_rgb"], rtol=1e-4)
+        dumps.append(sums)
+    assert np.allclose(dumps[0], dumps[1], rtol=1e-5, atol=1e-5)

@@ -10,7 +10,7 @@ rm -rf $OUT; mkdir -p $OUT
 TICKER=$!
 trap 'kill $TICKER 2>/dev/null' EXIT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --no-cpu-baseline $BENCH_ARGS > $OUT/bench.log 2> $OUT/bench.err || { echo "profiled bench failed"; tail -5 $OUT/bench.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --no-cpu-baseline $BENCH_ARGS > $OUT/bench.log 2> $OUT/bench.err || { echo "profiled bench failed"; tail -5 $OUT/bench.err; exit 1; }
 find $OUT/trace -name "*_kernel_trace.csv" -delete
 python3 - <<PY
 import csv, glob
