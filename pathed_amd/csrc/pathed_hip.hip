@@ -21,6 +21,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace pathed;
@@ -67,8 +68,8 @@ struct DeviceBuffer {
     size_t count = 0;
 
     DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer &) = delete;              // owns its allocation: a member added to PathedScene
-    DeviceBuffer &operator=(const DeviceBuffer &) = delete;   // is freed with it, whether or not ~PathedScene names it
+    DeviceBuffer(const DeviceBuffer &) = delete;              // owns its allocation: the members of PathedScene
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;   // are freed with it
     ~DeviceBuffer() { release(); }
 
     hipError_t allocate(size_t n)
@@ -173,6 +174,18 @@ static const int kDefaultShadeLaunches = 1;   // shade launches per trace launch
 static const int kDefaultSmallPhase1 = 1;   // PathedSceneOptions.small_phase1 = 0: 1 VALU, 2 matrix pipe
 
 
+// The compile-time scene sets (shading.h: SceneTraits) that contain the scene.  They overlap -- a Lambertian-only scene is
+// also triangleLit, roughBeckmann and smoothSet -- and every launch ladder ranks them for its own kernel.
+struct SceneTraitFlags {
+    bool lambertianTriangles = false;   // constant-albedo Lambertian surfaces, triangle lights, no spheres, no environment: k_path_small<.., TraitsLambertianTriangles>
+    bool lambertianPlasticSpheres = false;   // the Veach scene's set (shading.h)
+    bool triangleLit = false;                // any BSDF, constant albedo, triangle lights only, no spheres, no environment
+    // [r5] ... narrowed further (shading.h: the ladder): rough BSDFs over one microfacet distribution / Lambertian + glass + mirror
+    bool roughBeckmann = false, roughGgx = false, smoothSet = false;
+    bool lambertianGlassContainer = false;   // the reference's volume scene's set
+    bool envOnly = false;     // the one light is the environment and no material emits: k_shade<.., ENV_ONLY> (kernels.h)
+};
+
 struct PathedScene {
     DScene device;
     int width = 0, height = 0;
@@ -233,14 +246,8 @@ struct PathedScene {
     int waveShadeReady = 40;      // ... and a wave shades once this many of its paths have their rays back
     int waveRefill = kRefillThreshold;   // ... and idle lanes draw from the wave's list once fewer than this many are busy
     bool stagedShade = true;  // k_shade_staged (dense, state-sorted stages inside a block) or k_shade (one lane per slot)
-    bool lambertianTriangles = false;   // constant-albedo Lambertian surfaces, triangle lights, no spheres, no environment: k_path_small<.., TraitsLambertianTriangles>
-    bool lambertianPlasticSpheres = false;   // the Veach scene's set (shading.h)
-    bool triangleLit = false;                // any BSDF, constant albedo, triangle lights only, no spheres, no environment
-    // [r5] ... narrowed further (shading.h: the ladder): rough BSDFs over one microfacet distribution / Lambertian + glass + mirror
-    bool roughBeckmann = false, roughGgx = false, smoothSet = false;
-    bool lambertianGlassContainer = false;   // the reference's volume scene's set
+    SceneTraitFlags traits;   // which narrowed kernel instantiations serve the scene (sceneTraits)
     int nodeFormat = 0;                      // what k_trace walks (trace.h): 0 the 128-byte float nodes, 1 nodeQ, 2 node8
-    bool envOnly = false;     // the one light is the environment and no material emits: k_shade<.., ENV_ONLY> (kernels.h)
     bool splitShade = false;  // k_vertex + k_regen over the hit / miss lists the trace kernel writes (kernels.h: split shade stage)
     int vertexGrid = 0, regenGrid = 0;   // their persistent grids, blocks
     unsigned int listCap = 0;            // list blocks per shard
@@ -303,16 +310,6 @@ struct PathedScene {
 
     ~PathedScene()
     {
-        nodes.release(); nodesQ.release(); leafTris.release(); triShade.release(); triCompact.release(); envRgba.release(); texels.release();
-        spheres.release(); materials.release(); lights.release();
-        thetaCdf.release(); phiCdf.release(); phiEmpty.release(); thetaGuide.release(); phiGuide.release();
-        media.release(); primMedium.release(); volumeOverflow.release();
-        thetaRecords.release(); phiRecords.release();
-        rayO.release(); rayD.release(); hit.release(); mod.release(); thr.release();
-        res.release(); pend.release(); acc.release(); shO.release(); shD.release(); chunkBuf.release();
-        counters.release(); stats.release();
-        suspendMask.release(); suspendData.release(); stackOverflow.release();
-        slotLists.release(); deferredLists.release();
         if (hostRemaining) { (void)hipHostFree(hostRemaining); }
         for (int h = 0; h < kMaxPools; h++) {
             if (poolStreams[h]) { (void)hipStreamDestroy(poolStreams[h]); }
@@ -539,45 +536,35 @@ int ensureRenderState(PathedScene *scene, int nSlots, size_t chunkEntries)
     return PATHED_OK;
 }
 
+// The launch ladders pick ONE instantiation of a kernel from run-time flags.  withBool turns such a flag into a compile-time
+// constant: f is called with std::true_type or std::false_type and is compiled for both, so a rung that exists for both values
+// of a flag is one line inside it.  A rung that exists for one value only is written with that value, outside.  What the
+// ladders name is what the library contains (tests/test_kernel_resources.py counts it).
+template <typename F>
+void withBool(bool value, F &&f)
+{
+    if (value) { f(std::true_type{}); } else { f(std::false_type{}); }
+}
+
+// k_trace<STACK, LDS_SCENE, COUNT, LISTS, SPHERES, FORMAT>: every rung with and without counting
 template <int STACK>
 void launchTraceStack(PathedScene *scene, const RenderParams &params, hipStream_t stream)
 {
-    const dim3 grid((unsigned)scene->traceGrid), block(kBlock);
-    const size_t lds = scene->traceLdsBytes;
+    const auto run = [&](void (*kernel)(RenderParams)) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)scene->traceGrid), dim3(kBlock), scene->traceLdsBytes, stream, params);
+    };
+    withBool(scene->countMode, [&](auto COUNT) {
 #if PATHED_EXPERIMENTS
-    if (scene->splitShade) {
-        if (scene->sceneInLds) {
-            if (scene->countMode) { hipLaunchKernelGGL((k_trace<STACK, true, true, true>), grid, block, lds, stream, params); }
-            else { hipLaunchKernelGGL((k_trace<STACK, true, false, true>), grid, block, lds, stream, params); }
-        } else {
-            if (scene->countMode) { hipLaunchKernelGGL((k_trace<STACK, false, true, true>), grid, block, lds, stream, params); }
-            else { hipLaunchKernelGGL((k_trace<STACK, false, false, true>), grid, block, lds, stream, params); }
-        }
-        return;
-    }
-    if (scene->nodeFormat == 1) {
-        if (scene->countMode) { hipLaunchKernelGGL((k_trace<STACK, false, true, false, false, 1>), grid, block, lds, stream, params); }
-        else { hipLaunchKernelGGL((k_trace<STACK, false, false, false, false, 1>), grid, block, lds, stream, params); }
-        return;
-    }
-    if (scene->nodeFormat == 2) {
-        if (scene->countMode) { hipLaunchKernelGGL((k_trace<STACK, false, true, false, false, 2>), grid, block, lds, stream, params); }
-        else { hipLaunchKernelGGL((k_trace<STACK, false, false, false, false, 2>), grid, block, lds, stream, params); }
-        return;
-    }
+        if (scene->splitShade) { withBool(scene->sceneInLds, [&](auto LDS_SCENE) { run(k_trace<STACK, LDS_SCENE, COUNT, true>); }); return; }
+        if (scene->nodeFormat == 1) { run(k_trace<STACK, false, COUNT, false, false, 1>); return; }
+        if (scene->nodeFormat == 2) { run(k_trace<STACK, false, COUNT, false, false, 2>); return; }
 #endif
-    if (!scene->sceneInLds && scene->device.nSpheres == 0 && !scene->options.generic_kernels && !tuningEnv("PATHED_NO_SCENE_TRAITS")) {
-        if (scene->countMode) { hipLaunchKernelGGL((k_trace<STACK, false, true, false, false>), grid, block, lds, stream, params); }
-        else { hipLaunchKernelGGL((k_trace<STACK, false, false, false, false>), grid, block, lds, stream, params); }
-        return;
-    }
-    if (scene->sceneInLds) {
-        if (scene->countMode) { hipLaunchKernelGGL((k_trace<STACK, true, true, false>), grid, block, lds, stream, params); }
-        else { hipLaunchKernelGGL((k_trace<STACK, true, false, false>), grid, block, lds, stream, params); }
-    } else {
-        if (scene->countMode) { hipLaunchKernelGGL((k_trace<STACK, false, true, false>), grid, block, lds, stream, params); }
-        else { hipLaunchKernelGGL((k_trace<STACK, false, false, false>), grid, block, lds, stream, params); }
-    }
+        if (!scene->sceneInLds && scene->device.nSpheres == 0 && !scene->options.generic_kernels && !tuningEnv("PATHED_NO_SCENE_TRAITS")) {
+            run(k_trace<STACK, false, COUNT, false, false>);
+            return;
+        }
+        withBool(scene->sceneInLds, [&](auto LDS_SCENE) { run(k_trace<STACK, LDS_SCENE, COUNT, false>); });
+    });
 }
 
 void launchTrace(PathedScene *scene, const RenderParams &params, hipStream_t stream)
@@ -586,8 +573,7 @@ void launchTrace(PathedScene *scene, const RenderParams &params, hipStream_t str
         // uniform cost per batch and no per-block setup: one 64-ray batch per wave, the hardware
         // dispatcher balances (a persistent grid quantises 3.3 batches per wave to 4 rounds)
         const dim3 grid((unsigned)(2 * params.nSlots / kBlock)), block(kBlock);
-        if (scene->countMode) { hipLaunchKernelGGL((k_trace_small<true>), grid, block, 0, stream, params, scene->smallTris); }
-        else { hipLaunchKernelGGL((k_trace_small<false>), grid, block, 0, stream, params, scene->smallTris); }
+        withBool(scene->countMode, [&](auto COUNT) { hipLaunchKernelGGL((k_trace_small<COUNT>), grid, block, 0, stream, params, scene->smallTris); });
         return;
     }
     switch (scene->stackRows) {
@@ -685,80 +671,43 @@ static void sortProbe(PathedScene *scene, const RenderParams &q, hipStream_t str
 }
 #endif
 
+// every rung with the materials in LDS and without
 void launchShade(PathedScene *scene, const RenderParams &params, hipStream_t stream)
 {
+    const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
 #if PATHED_EXPERIMENTS
+    const size_t lds = ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0;
     if (scene->splitShade && !PATHED_EXP_LISTS_ONLY) {
-        const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
-        const size_t lds = ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0;
         const int slotBlocks = params.nSlots / kBlock;
         const dim3 vertexGrid((unsigned)(scene->vertexGrid < slotBlocks ? scene->vertexGrid : slotBlocks));
         const dim3 regenGrid((unsigned)(scene->regenGrid < slotBlocks ? scene->regenGrid : slotBlocks));
-        if (ldsMaterials) { hipLaunchKernelGGL((k_vertex<true>), vertexGrid, dim3(kBlock), lds, stream, params); }
-        else { hipLaunchKernelGGL((k_vertex<false>), vertexGrid, dim3(kBlock), lds, stream, params); }
+        withBool(ldsMaterials, [&](auto LDS_MATERIALS) { hipLaunchKernelGGL((k_vertex<LDS_MATERIALS>), vertexGrid, dim3(kBlock), lds, stream, params); });
         hipLaunchKernelGGL(k_regen, regenGrid, dim3(kBlock), 0, stream, params);
         return;
     }
     if (scene->stagedShade) {
         const dim3 grid((unsigned)(params.nSlots / (kBlock * scene->stageRounds))), block(kBlock);
-        const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
-        const size_t lds = ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0;
-        if (scene->stageRounds == 4) {
-            if (ldsMaterials) { hipLaunchKernelGGL((k_shade_staged<true, 4>), grid, block, lds, stream, params); }
-            else { hipLaunchKernelGGL((k_shade_staged<false, 4>), grid, block, lds, stream, params); }
-        } else {
-            if (ldsMaterials) { hipLaunchKernelGGL((k_shade_staged<true, 2>), grid, block, lds, stream, params); }
-            else { hipLaunchKernelGGL((k_shade_staged<false, 2>), grid, block, lds, stream, params); }
-        }
+        withBool(ldsMaterials, [&](auto LDS_MATERIALS) {
+            if (scene->stageRounds == 4) { hipLaunchKernelGGL((k_shade_staged<LDS_MATERIALS, 4>), grid, block, lds, stream, params); }
+            else { hipLaunchKernelGGL((k_shade_staged<LDS_MATERIALS, 2>), grid, block, lds, stream, params); }
+        });
         return;
     }
 #endif
     const dim3 grid((unsigned)(params.nSlots / kBlock)), block(kBlock);
-    if (scene->device.nMaterials <= kMaxLdsMaterials) {
-        // (k_shade narrowed further to {Lambertian, plastic, environment} -- 88 VGPRs against 92 -- shortens the shade launches of
-        // the 5.2 M-triangle mesh by 13 % and LENGTHENS the other pool's trace launches by 23 %: -4.8 % overall, not adopted,
-        // profiles/r3_ab_scene_traits.log)
-        // ([r5] again with local rays, when the trace kernel has a fifth of its rays left: {Lambertian, plastic, environment} 2 312
-        // against 2 456 Msamples/s on the same mesh, the sphere-free environment set +-0: profiles/r5_ab_local_rays.log)
-        // [r5] environment-only scenes: k_shade_env -- the same vertex code, the next sample's camera ray started (and, if it is a
-        // local ray that hits a large triangle, its first vertex shaded) in the launch that ends a sample; shade_chain = 1: the
-        // plain k_shade<.., ENV_ONLY> (A/B runs, same floats)
-        if (scene->envOnly && scene->options.shade_chain != 1) { hipLaunchKernelGGL((k_shade_env<true>), grid, block, 0, stream, params); }
-        else if (scene->envOnly) { hipLaunchKernelGGL((k_shade<true, true>), grid, block, 0, stream, params); }
-        else { hipLaunchKernelGGL((k_shade<true, false>), grid, block, 0, stream, params); }
-    } else {
-        if (scene->envOnly && scene->options.shade_chain != 1) { hipLaunchKernelGGL((k_shade_env<false>), grid, block, 0, stream, params); }
-        else if (scene->envOnly) { hipLaunchKernelGGL((k_shade<false, true>), grid, block, 0, stream, params); }
-        else { hipLaunchKernelGGL((k_shade<false, false>), grid, block, 0, stream, params); }
-    }
-}
-
-template <int STACK, bool SMALL>
-void launchVolumeStack(const RenderParams &params, const SmallTris &smallTris, dim3 grid, size_t lds, bool ldsMaterials, hipStream_t stream)
-{
-    if (ldsMaterials) { hipLaunchKernelGGL((k_path_volume<true, STACK, SMALL>), grid, dim3(kBlock), lds, stream, params, smallTris); }
-    else { hipLaunchKernelGGL((k_path_volume<false, STACK, SMALL>), grid, dim3(kBlock), lds, stream, params, smallTris); }
-}
-
-// small: the scene's triangles go through the all-triangles intersector (kernarg pair records), no tree walk
-void launchVolume(int stackRows, bool small, bool narrowed, const RenderParams &params, const SmallTris &smallTris, dim3 grid, size_t lds, bool ldsMaterials,
-                  hipStream_t stream)
-{
-    if (small && narrowed && ldsMaterials) {   // the reference's own volume scene kinds (shading.h: TraitsLambertianGlassContainer)
-        if (params.smallQuads > 0) { hipLaunchKernelGGL((k_path_volume<true, 8, true, TraitsLambertianGlassContainer, true>), grid, dim3(kBlock), lds, stream, params, smallTris); }
-        else { hipLaunchKernelGGL((k_path_volume<true, 8, true, TraitsLambertianGlassContainer>), grid, dim3(kBlock), lds, stream, params, smallTris); }
-        return;
-    }
-    if (small && ldsMaterials && params.smallQuads > 0) {
-        hipLaunchKernelGGL((k_path_volume<true, 8, true, TraitsAll, true>), grid, dim3(kBlock), lds, stream, params, smallTris);
-        return;
-    }
-    if (small) { launchVolumeStack<8, true>(params, smallTris, grid, lds, ldsMaterials, stream); return; }
-    switch (stackRows) {
-    case 8: launchVolumeStack<8, false>(params, smallTris, grid, lds, ldsMaterials, stream); break;
-    case 16: launchVolumeStack<16, false>(params, smallTris, grid, lds, ldsMaterials, stream); break;
-    default: launchVolumeStack<22, false>(params, smallTris, grid, lds, ldsMaterials, stream); break;
-    }
+    // (k_shade narrowed further to {Lambertian, plastic, environment} -- 88 VGPRs against 92 -- shortens the shade launches of
+    // the 5.2 M-triangle mesh by 13 % and LENGTHENS the other pool's trace launches by 23 %: -4.8 % overall, not adopted,
+    // profiles/r3_ab_scene_traits.log)
+    // ([r5] again with local rays, when the trace kernel has a fifth of its rays left: {Lambertian, plastic, environment} 2 312
+    // against 2 456 Msamples/s on the same mesh, the sphere-free environment set +-0: profiles/r5_ab_local_rays.log)
+    // [r5] environment-only scenes: k_shade_env -- the same vertex code, the next sample's camera ray started (and, if it is a
+    // local ray that hits a large triangle, its first vertex shaded) in the launch that ends a sample; shade_chain = 1: the
+    // plain k_shade<.., ENV_ONLY> (A/B runs, same floats)
+    withBool(ldsMaterials, [&](auto LDS_MATERIALS) {
+        if (scene->traits.envOnly && scene->options.shade_chain != 1) { hipLaunchKernelGGL((k_shade_env<LDS_MATERIALS>), grid, block, 0, stream, params); }
+        else if (scene->traits.envOnly) { hipLaunchKernelGGL((k_shade<LDS_MATERIALS, true>), grid, block, 0, stream, params); }
+        else { hipLaunchKernelGGL((k_shade<LDS_MATERIALS, false>), grid, block, 0, stream, params); }
+    });
 }
 
 // what node_format 0 picks for the scenes the compressed trees serve: 0 float nodes, 1 nodeQ, 2 node8 (DESIGN.md has the measurements)
@@ -1453,6 +1402,40 @@ static hipError_t buildHybrid(PathedScene *scene, const PathedSceneDesc *desc)
     return rebuildHybridItems(scene);
 }
 
+// Which compile-time scene sets (shading.h: SceneTraits) contain the scene.  generic_kernels = 1 leaves every flag off.
+static SceneTraitFlags sceneTraits(const PathedSceneDesc *desc, const std::vector<DMaterial> &materials, const std::vector<DLight> &lights,
+                                   const PathedSceneOptions &options)
+{
+    const unsigned rough = (1u << PATHED_MAT_LAMBERTIAN) | (1u << PATHED_MAT_OREN_NAYAR) | (1u << PATHED_MAT_MICROFACET) | (1u << PATHED_MAT_PLASTIC);
+    const unsigned smooth = (1u << PATHED_MAT_LAMBERTIAN) | (1u << PATHED_MAT_GLASS) | (1u << PATHED_MAT_MIRROR);
+    const unsigned lambertianPlastic = (1u << PATHED_MAT_LAMBERTIAN) | (1u << PATHED_MAT_PLASTIC);
+    const unsigned glassContainer = (1u << PATHED_MAT_LAMBERTIAN) | (1u << PATHED_MAT_GLASS) | (1u << PATHED_MAT_PASSTHROUGH);
+    unsigned kinds = 0u, distributions = 0u;   // material types that occur; 1 Beckmann, 2 GGX among the microfacet / plastic materials
+    bool emissive = false, constantAlbedo = true;
+    for (uint32_t i = 0; i < desc->n_materials; i++) {
+        const PathedMaterial &material = desc->materials[i];
+        kinds |= 1u << material.type;
+        if (material.type == PATHED_MAT_MICROFACET || material.type == PATHED_MAT_PLASTIC) { distributions |= material.distribution == PATHED_DIST_GGX ? 2u : 1u; }
+        emissive = emissive || emits(materials[i]);
+        constantAlbedo = constantAlbedo && material.albedo_type == PATHED_ALBEDO_CONSTANT;
+    }
+    bool triangleLights = false;
+    for (const DLight &light : lights) { triangleLights = triangleLights || light.kind == 0; }
+    const bool noEnv = desc->env == nullptr, noSpheres = desc->n_spheres == 0;
+    const bool narrow = options.generic_kernels == 0 && !tuningEnv("PATHED_NO_SCENE_TRAITS");
+
+    SceneTraitFlags t;
+    t.envOnly = !noEnv && lights.size() == 1 && !emissive && options.generic_kernels == 0 && !tuningEnv("PATHED_NO_ENV_ONLY");
+    t.lambertianTriangles = narrow && noEnv && noSpheres && constantAlbedo && kinds == (1u << PATHED_MAT_LAMBERTIAN);
+    t.lambertianPlasticSpheres = narrow && noEnv && !triangleLights && constantAlbedo && (kinds & ~lambertianPlastic) == 0u;
+    t.triangleLit = narrow && noEnv && noSpheres && constantAlbedo && (kinds & (1u << PATHED_MAT_PASSTHROUGH)) == 0u;
+    t.roughBeckmann = t.triangleLit && (kinds & ~rough) == 0u && (distributions & 2u) == 0u;
+    t.roughGgx = t.triangleLit && (kinds & ~rough) == 0u && distributions == 2u;
+    t.smoothSet = t.triangleLit && (kinds & ~smooth) == 0u;
+    t.lambertianGlassContainer = narrow && noEnv && constantAlbedo && (kinds & ~glassContainer) == 0u;
+    return t;
+}
+
 int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOptions *optionsIn, PathedScene **out)
 {
     if (!out) { return fail(PATHED_E_INVALID, "out pointer is null"); }
@@ -1839,51 +1822,7 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
     d.nMaterials = (int)desc->n_materials;
     d.lights = scene->lights.ptr;
     d.nLights = (int)lights.size();
-    {
-        bool emissive = false;
-        for (const DMaterial &material : materials) { emissive = emissive || emits(material); }
-        scene->envOnly = desc->env != nullptr && lights.size() == 1 && !emissive && options.generic_kernels == 0 && !tuningEnv("PATHED_NO_ENV_ONLY");
-        bool plainLambertian = desc->env == nullptr && desc->n_spheres == 0;
-        for (uint32_t i = 0; i < desc->n_materials; i++) {
-            plainLambertian = plainLambertian && desc->materials[i].type == PATHED_MAT_LAMBERTIAN && desc->materials[i].albedo_type == PATHED_ALBEDO_CONSTANT;
-        }
-        const bool narrow = options.generic_kernels == 0 && !tuningEnv("PATHED_NO_SCENE_TRAITS");
-        scene->lambertianTriangles = plainLambertian && narrow;
-        bool lambertianPlastic = true;
-        for (uint32_t i = 0; i < desc->n_materials; i++) {
-            lambertianPlastic = lambertianPlastic && (desc->materials[i].type == PATHED_MAT_LAMBERTIAN || desc->materials[i].type == PATHED_MAT_PLASTIC)
-                && desc->materials[i].albedo_type == PATHED_ALBEDO_CONSTANT;
-        }
-        bool triangleLights = false;
-        for (const DLight &light : lights) { triangleLights = triangleLights || light.kind == 0; }
-        scene->lambertianPlasticSpheres = lambertianPlastic && desc->env == nullptr && !triangleLights && narrow;
-        bool constantAlbedo = true, noContainer = true;
-        for (uint32_t i = 0; i < desc->n_materials; i++) {
-            constantAlbedo = constantAlbedo && desc->materials[i].albedo_type == PATHED_ALBEDO_CONSTANT;
-            noContainer = noContainer && desc->materials[i].type != PATHED_MAT_PASSTHROUGH;
-        }
-        scene->triangleLit = constantAlbedo && noContainer && desc->env == nullptr && desc->n_spheres == 0 && narrow;
-        {
-            unsigned kinds = 0u, distributions = 0u;
-            for (uint32_t i = 0; i < desc->n_materials; i++) {
-                const int type = desc->materials[i].type;
-                kinds |= 1u << type;
-                if (type == PATHED_MAT_MICROFACET || type == PATHED_MAT_PLASTIC) { distributions |= desc->materials[i].distribution == PATHED_DIST_GGX ? 2u : 1u; }
-            }
-            const unsigned rough = (1u << PATHED_MAT_LAMBERTIAN) | (1u << PATHED_MAT_OREN_NAYAR) | (1u << PATHED_MAT_MICROFACET) | (1u << PATHED_MAT_PLASTIC);
-            const unsigned smooth = (1u << PATHED_MAT_LAMBERTIAN) | (1u << PATHED_MAT_GLASS) | (1u << PATHED_MAT_MIRROR);
-            scene->roughBeckmann = scene->triangleLit && (kinds & ~rough) == 0u && (distributions & 2u) == 0u;
-            scene->roughGgx = scene->triangleLit && (kinds & ~rough) == 0u && distributions == 2u;
-            scene->smoothSet = scene->triangleLit && (kinds & ~smooth) == 0u;
-        }
-        bool glassContainer = desc->env == nullptr;
-        for (uint32_t i = 0; i < desc->n_materials; i++) {
-            const int type = desc->materials[i].type;
-            glassContainer = glassContainer && (type == PATHED_MAT_LAMBERTIAN || type == PATHED_MAT_GLASS || type == PATHED_MAT_PASSTHROUGH)
-                && desc->materials[i].albedo_type == PATHED_ALBEDO_CONSTANT;
-        }
-        scene->lambertianGlassContainer = glassContainer && narrow;
-    }
+    scene->traits = sceneTraits(desc, materials, lights, options);
     d.media = scene->media.ptr;
     d.primMedium = scene->primMedium.ptr;
     d.nMedia = (int)desc->n_media;
@@ -2065,6 +2004,8 @@ void pathed_hip_scene_destroy(PathedScene *scene)
     delete scene;
 }
 
+}  // extern "C" (the render passes below are internal; persistentPass is a template)
+
 // The unit order of one pool's launch parameters (kernels.h: THE UNIT ORDER).  The (nQueues x pools) queues share out
 // ITEMS round-robin -- the chunks of the pass (stripes: an item is one whole image of units) or groups of kUnitGroup pixels
 // (tiles: an item is all chunks of the group) -- queue q of pool `pool` owns the items (q * pools + pool) + j * queues.
@@ -2124,21 +2065,50 @@ static bool usesVolumeKernel(const PathedScene *scene)
     return scene->hasContainers || scene->device.nMedia > 0 || scene->options.generic_kernels != 0;
 }
 
-// One internal pass of the fused path kernel (scenes of <= 64 triangles): a single persistent launch
-// renders every unit of the pass; no slot pool, no iteration loop, no polling.
-static int renderPassFused(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_t count,
-                           int start_bounce, int last_bounce, float *d_accum, hipStream_t stream)
-{
-    const int nPixels = scene->width * scene->height;
-    const int chunk = scene->samplesPerUnit;
-    const int chunksPerPixel = (int)((count + (uint32_t)chunk - 1) / (uint32_t)chunk);
-    const unsigned long long nUnits64 = (unsigned long long)nPixels * (unsigned long long)chunksPerPixel;
-    if (nUnits64 >= 0xFFFFFFF0ull) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
-    const unsigned int nUnits = (unsigned int)nUnits64;
+// One internal pass of a render call: samples [begin, begin + count) of every pixel, count <= chunk * kMaxChunksPerPass,
+// summed into `accum` behind whatever `stream` holds.  Its work units are `chunk` samples of one pixel each.
+struct Pass {
+    uint64_t seed;
+    uint32_t begin, count;
+    int startBounce, lastBounce;
+    float *accum;
+    hipStream_t stream;
+    int nPixels, chunk, chunksPerPixel;
+    unsigned int nUnits;
+};
 
-    if (scene->chunkCapacity < (size_t)nUnits) {
-        HIP_TRY(scene->chunkBuf.allocate((size_t)nUnits));
-        scene->chunkCapacity = (size_t)nUnits;
+// The launch parameters every kernel of the pass reads, and the unit order of pool `pool` of `pools` over nQueues queues.
+// Returns false when the unit ids of the pass do not fit 32 bits.
+static bool fillPassParams(RenderParams &q, const PathedScene *scene, const Pass &pass, int pool, int pools, int nQueues)
+{
+    q.scene = scene->device;
+    q.state.chunkBuf = scene->chunkBuf.ptr;
+    q.counters = scene->counters.ptr + (size_t)pool * kCtrCount;
+    q.stats = scene->stats.ptr;
+    q.accum = pass.accum;
+    q.nPixels = pass.nPixels;
+    q.chunk = pass.chunk;
+    q.chunksPerPixel = pass.chunksPerPixel;
+    q.seedLo = (uint32_t)pass.seed;
+    q.seedHi = (uint32_t)(pass.seed >> 32);
+    q.sppBegin = pass.begin;
+    q.sppEnd = pass.begin + pass.count;
+    q.startBounce = pass.startBounce;
+    q.lastBounce = pass.lastBounce;
+    return fillUnitOrder(q, scene->unitOrder, scene->width, scene->height, pass.chunksPerPixel, pool, pools, nQueues);
+}
+
+// A pass as ONE persistent launch that renders every unit: no slot pool, no iteration loop, no polling.  This is all that the
+// fused, volume, wave and hybrid organisations share; `launch(params, grid, stream)` sets the path's own RenderParams fields
+// and starts its kernel.  blocksPerCu: what the kernel's register budget keeps resident (waves per SIMD = blocks per CU).
+// maxStack > 0: the kernel keeps ldsRows rows of a lane's traversal stack in LDS and spills the entries beyond them, up to the
+// tree's bound maxStack, to HBM; 0: it walks no tree.
+template <typename Launch>
+static int persistentPass(PathedScene *scene, const Pass &pass, int blocksPerCu, int maxStack, int ldsRows, Launch launch)
+{
+    if (scene->chunkCapacity < (size_t)pass.nUnits) {
+        HIP_TRY(scene->chunkBuf.allocate((size_t)pass.nUnits));
+        scene->chunkCapacity = (size_t)pass.nUnits;
     }
     if (!scene->counters.ptr) { HIP_TRY(scene->counters.allocate(kMaxPools * kCtrCount)); }
     if (!scene->stats.ptr) {
@@ -2146,414 +2116,205 @@ static int renderPassFused(PathedScene *scene, uint64_t seed, uint32_t begin, ui
         HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
     }
 
-    // persistent grid: what the register budget keeps resident (PATHED_FUSED_WAVES waves per SIMD = blocks per CU),
-    // or fewer when the pass has fewer than 64 units per wave
-    unsigned long long blocks = (unsigned long long)scene->computeUnits * PATHED_FUSED_WAVES;
-    const unsigned long long blocksNeeded = (nUnits64 + (unsigned long long)kBlock - 1) / kBlock;
+    // the grid: blocksPerCu blocks per CU, or fewer when the pass has fewer than 64 units per wave
+    unsigned long long blocks = (unsigned long long)scene->computeUnits * blocksPerCu;
+    const unsigned long long blocksNeeded = ((unsigned long long)pass.nUnits + (unsigned long long)kBlock - 1) / kBlock;
     if (blocks > blocksNeeded) { blocks = blocksNeeded; }
     if (blocks < 1) { blocks = 1; }
     const unsigned int waves = (unsigned int)blocks * kWavesPerBlock;
 
     RenderParams params;
     std::memset(&params, 0, sizeof params);
-    params.scene = scene->device;
-    params.state.chunkBuf = scene->chunkBuf.ptr;
-    params.counters = scene->counters.ptr;
-    params.stats = scene->stats.ptr;
-    params.accum = d_accum;
-    params.nPixels = nPixels;
-    if (!fillUnitOrder(params, scene->unitOrder, scene->width, scene->height, chunksPerPixel, 0, 1,
-                       (int)(waves < (unsigned int)kUnitQueues ? waves : (unsigned int)kUnitQueues))) {
+    if (maxStack > 0) {
+        const size_t overflowRows = (size_t)(maxStack > ldsRows ? maxStack - ldsRows : 0);
+        const size_t overflowInts = (size_t)blocks * kBlock * (overflowRows ? overflowRows : 1);
+        if (scene->volumeOverflow.count < overflowInts) { HIP_TRY(scene->volumeOverflow.allocate(overflowInts)); }
+        params.stackOverflow = scene->volumeOverflow.ptr;
+        params.maxStack = maxStack;
+    }
+    if (!fillPassParams(params, scene, pass, 0, 1, (int)(waves < (unsigned int)kUnitQueues ? waves : (unsigned int)kUnitQueues))) {
         return fail(PATHED_E_INVALID, "too many work units in one pass");
     }
     {
         // a wave reserves up to one unit per lane at a time; passes too small for that hand out less per atomic,
         // so that the last reservations of a queue do not leave most waves idle
         const unsigned int wavesPerQueue = (waves + (unsigned int)params.nQueues - 1) / (unsigned int)params.nQueues;
-        unsigned int grab = (nUnits / (unsigned int)params.nQueues) / (wavesPerQueue * 4u);
+        unsigned int grab = (pass.nUnits / (unsigned int)params.nQueues) / (wavesPerQueue * 4u);
         params.unitGrab = (int)(grab < 1u ? 1u : grab > 64u ? 64u : grab);
     }
-    params.chunk = chunk;
-    params.chunksPerPixel = chunksPerPixel;
-    params.seedLo = (uint32_t)seed;
-    params.seedHi = (uint32_t)(seed >> 32);
-    params.sppBegin = begin;
-    params.sppEnd = begin + count;
-    params.startBounce = start_bounce;
-    params.lastBounce = last_bounce;
 
-    HIP_TRY(hipMemsetAsync(params.counters, 0, kCtrCount * sizeof(unsigned int), stream));
-    const dim3 grid((unsigned)blocks), block(kBlock);
-    const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
-    const size_t lds = ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0;
+    HIP_TRY(hipMemsetAsync(params.counters, 0, kCtrCount * sizeof(unsigned int), pass.stream));
     int timed = -1;
     if (scene->timeKernels) {
         timed = scene->traceEvents.acquire();
-        (void)hipEventRecord(scene->traceEvents.start[timed], stream);
+        (void)hipEventRecord(scene->traceEvents.start[timed], pass.stream);
     }
-    // the narrowest instantiation whose compile-time scene set contains this scene's (shading.h: SceneTraits)
-    params.mfmaTable = scene->mfmaTable.ptr;
-    params.mfmaFrame = scene->mfmaFrame;
-    params.smallQuads = scene->smallLayout.nQuads;
-    params.smallKappaT = scene->smallLayout.kappaT;
-    params.scene.leafTris = scene->itemTris.ptr;   // phase 2 indexes the triangles in the order phase 1's bits come in
-    std::memcpy(params.spherePairs, scene->spherePairs, sizeof params.spherePairs);
+    launch(params, dim3((unsigned)blocks), pass.stream);
+    if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], pass.stream); }
+    scene->traceLaunchesAll++;
+    const dim3 pixelGrid((unsigned)((pass.nPixels + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_resolve, pixelGrid, dim3(kBlock), 0, pass.stream, params);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(pass.stream));
+
+    scene->iterations += 1;
+    scene->cameraSamples += (unsigned long long)pass.count * (unsigned long long)pass.nPixels;
+    return PATHED_OK;
+}
+
+// The fused path kernel (k_path_small: scenes of <= 64 triangles, whole paths in registers).  No tree, no stack.
+static int renderPassFused(PathedScene *scene, const Pass &pass)
+{
+    return persistentPass(scene, pass, PATHED_FUSED_WAVES, 0, 0, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
+        const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
+        const size_t lds = ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0;
+        params.mfmaTable = scene->mfmaTable.ptr;
+        params.mfmaFrame = scene->mfmaFrame;
+        params.smallQuads = scene->smallLayout.nQuads;
+        params.smallKappaT = scene->smallLayout.kappaT;
+        params.scene.leafTris = scene->itemTris.ptr;   // phase 2 indexes the triangles in the order phase 1's bits come in
+        std::memcpy(params.spherePairs, scene->spherePairs, sizeof params.spherePairs);
+
+        // k_path_small<LDS_MATERIALS, COUNT, TRAITS, MFMA, QUADS>: the narrowest instantiation whose compile-time scene set contains
+        // this scene's (shading.h: SceneTraits).  MFMA and QUADS exist with the materials in LDS only.
+        const SceneTraitFlags &traits = scene->traits;
+        const bool count = scene->countMode;
+        const auto run = [&](void (*kernel)(RenderParams, SmallTris)) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, scene->smallItems); };
 #if PATHED_EXPERIMENTS
-    if (scene->mfmaPhase1 && ldsMaterials) {
-        // phase 1 on the matrix pipe: the same instantiations with MFMA = true
-        if (scene->lambertianTriangles) {
-            if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsLambertianTriangles, true>), grid, block, lds, stream, params, scene->smallItems); }
-            else { hipLaunchKernelGGL((k_path_small<true, false, TraitsLambertianTriangles, true>), grid, block, lds, stream, params, scene->smallItems); }
-        } else if (scene->lambertianPlasticSpheres) {
-            if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsLambertianPlasticSpheres, true>), grid, block, lds, stream, params, scene->smallItems); }
-            else { hipLaunchKernelGGL((k_path_small<true, false, TraitsLambertianPlasticSpheres, true>), grid, block, lds, stream, params, scene->smallItems); }
-        } else {
-            if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsAll, true>), grid, block, lds, stream, params, scene->smallItems); }
-            else { hipLaunchKernelGGL((k_path_small<true, false, TraitsAll, true>), grid, block, lds, stream, params, scene->smallItems); }
-        }
-    } else
+        if (scene->mfmaPhase1 && ldsMaterials) {
+            // phase 1 on the matrix pipe
+            withBool(count, [&](auto COUNT) {
+                if (traits.lambertianTriangles) { run(k_path_small<true, COUNT, TraitsLambertianTriangles, true>); }
+                else if (traits.lambertianPlasticSpheres) { run(k_path_small<true, COUNT, TraitsLambertianPlasticSpheres, true>); }
+                else { run(k_path_small<true, COUNT, TraitsAll, true>); }
+            });
+        } else
 #endif
-    if (scene->smallLayout.nQuads > 0 && ldsMaterials) {
-        // some triangles are halves of parallelograms: phase 1 tests those as parallelograms (small_items.h)
-        if (scene->lambertianTriangles) {
-            if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsLambertianTriangles, false, true>), grid, block, lds, stream, params, scene->smallItems); }
-            else { hipLaunchKernelGGL((k_path_small<true, false, TraitsLambertianTriangles, false, true>), grid, block, lds, stream, params, scene->smallItems); }
-        } else if (scene->lambertianPlasticSpheres) {
-            if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsLambertianPlasticSpheres, false, true>), grid, block, lds, stream, params, scene->smallItems); }
-            else { hipLaunchKernelGGL((k_path_small<true, false, TraitsLambertianPlasticSpheres, false, true>), grid, block, lds, stream, params, scene->smallItems); }
-        } else if (scene->roughBeckmann && !scene->countMode) {
-            hipLaunchKernelGGL((k_path_small<true, false, TraitsRoughBeckmann, false, true>), grid, block, lds, stream, params, scene->smallItems);
-        } else if (scene->roughGgx && !scene->countMode) {
-            hipLaunchKernelGGL((k_path_small<true, false, TraitsRoughGgx, false, true>), grid, block, lds, stream, params, scene->smallItems);
-        } else if (scene->smoothSet && !scene->countMode) {
-            hipLaunchKernelGGL((k_path_small<true, false, TraitsSmooth, false, true>), grid, block, lds, stream, params, scene->smallItems);
-        } else if (scene->triangleLit && !scene->countMode) {
-            hipLaunchKernelGGL((k_path_small<true, false, TraitsTriangleLit, false, true>), grid, block, lds, stream, params, scene->smallItems);
+        if (scene->smallLayout.nQuads > 0 && ldsMaterials) {
+            // some triangles are halves of parallelograms: phase 1 tests those as parallelograms (small_items.h).  The rough, smooth
+            // and triangle-lit sets have no counting instantiation: a counting call of such a scene takes TraitsAll
+            if (traits.lambertianTriangles) { withBool(count, [&](auto COUNT) { run(k_path_small<true, COUNT, TraitsLambertianTriangles, false, true>); }); }
+            else if (traits.lambertianPlasticSpheres) { withBool(count, [&](auto COUNT) { run(k_path_small<true, COUNT, TraitsLambertianPlasticSpheres, false, true>); }); }
+            else if (traits.roughBeckmann && !count) { run(k_path_small<true, false, TraitsRoughBeckmann, false, true>); }
+            else if (traits.roughGgx && !count) { run(k_path_small<true, false, TraitsRoughGgx, false, true>); }
+            else if (traits.smoothSet && !count) { run(k_path_small<true, false, TraitsSmooth, false, true>); }
+            else if (traits.triangleLit && !count) { run(k_path_small<true, false, TraitsTriangleLit, false, true>); }
+            else { withBool(count, [&](auto COUNT) { run(k_path_small<true, COUNT, TraitsAll, false, true>); }); }
+        } else if (traits.lambertianTriangles) {
+            withBool(ldsMaterials, [&](auto LDS_MATERIALS) { withBool(count, [&](auto COUNT) { run(k_path_small<LDS_MATERIALS, COUNT, TraitsLambertianTriangles>); }); });
+        } else if (traits.lambertianPlasticSpheres && ldsMaterials) {
+            withBool(count, [&](auto COUNT) { run(k_path_small<true, COUNT, TraitsLambertianPlasticSpheres>); });
         } else {
-            if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsAll, false, true>), grid, block, lds, stream, params, scene->smallItems); }
-            else { hipLaunchKernelGGL((k_path_small<true, false, TraitsAll, false, true>), grid, block, lds, stream, params, scene->smallItems); }
+            withBool(ldsMaterials, [&](auto LDS_MATERIALS) { withBool(count, [&](auto COUNT) { run(k_path_small<LDS_MATERIALS, COUNT, TraitsAll>); }); });
         }
-    } else
-    if (scene->lambertianTriangles) {
-        if (ldsMaterials) {
-            if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsLambertianTriangles>), grid, block, lds, stream, params, scene->smallItems); }
-            else { hipLaunchKernelGGL((k_path_small<true, false, TraitsLambertianTriangles>), grid, block, lds, stream, params, scene->smallItems); }
-        } else {
-            if (scene->countMode) { hipLaunchKernelGGL((k_path_small<false, true, TraitsLambertianTriangles>), grid, block, lds, stream, params, scene->smallItems); }
-            else { hipLaunchKernelGGL((k_path_small<false, false, TraitsLambertianTriangles>), grid, block, lds, stream, params, scene->smallItems); }
-        }
-    } else if (scene->lambertianPlasticSpheres && ldsMaterials) {
-        if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsLambertianPlasticSpheres>), grid, block, lds, stream, params, scene->smallItems); }
-        else { hipLaunchKernelGGL((k_path_small<true, false, TraitsLambertianPlasticSpheres>), grid, block, lds, stream, params, scene->smallItems); }
-    } else if (ldsMaterials) {
-        if (scene->countMode) { hipLaunchKernelGGL((k_path_small<true, true, TraitsAll>), grid, block, lds, stream, params, scene->smallItems); }
-        else { hipLaunchKernelGGL((k_path_small<true, false, TraitsAll>), grid, block, lds, stream, params, scene->smallItems); }
-    } else {
-        if (scene->countMode) { hipLaunchKernelGGL((k_path_small<false, true, TraitsAll>), grid, block, lds, stream, params, scene->smallItems); }
-        else { hipLaunchKernelGGL((k_path_small<false, false, TraitsAll>), grid, block, lds, stream, params, scene->smallItems); }
-    }
-    if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], stream); }
-    scene->traceLaunchesAll++;
-    const dim3 pixelGrid((unsigned)((nPixels + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_resolve, pixelGrid, block, 0, stream, params);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-
-    scene->iterations += 1;
-    scene->cameraSamples += (unsigned long long)count * (unsigned long long)nPixels;
-    return PATHED_OK;
+    });
 }
 
-// One internal pass of the volume integrator (k_path_volume): like renderPassFused, one persistent launch.
-static int renderPassVolume(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_t count,
-                            int start_bounce, int last_bounce, float *d_accum, hipStream_t stream)
+// The volume integrator (k_path_volume).  small: <= 64 triangles, <= 16 spheres go through the all-triangles intersector
+// (kernarg pair records), no tree walk.
+static int renderPassVolume(PathedScene *scene, const Pass &pass)
 {
-    const int nPixels = scene->width * scene->height;
-    const int chunk = scene->samplesPerUnit;
-    const int chunksPerPixel = (int)((count + (uint32_t)chunk - 1) / (uint32_t)chunk);
-    const unsigned long long nUnits64 = (unsigned long long)nPixels * (unsigned long long)chunksPerPixel;
-    if (nUnits64 >= 0xFFFFFFF0ull) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
-    const unsigned int nUnits = (unsigned int)nUnits64;
+    return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, scene->stackRows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
+        const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
+        const bool small = scene->bruteForce;
+        const size_t lds = (size_t)((small ? 8 : scene->stackRows) + 1) * kBlock * sizeof(int)
+            + (ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0);
+        // scenes made of quads: phase 1 over the item records (small_items.h), phase 2 over the item-ordered triangles
+        const bool quads = small && ldsMaterials && scene->smallLayout.nQuads > 0;
+        params.smallQuads = quads ? scene->smallLayout.nQuads : 0;
+        params.smallKappaT = scene->smallLayout.kappaT;
+        if (quads) { params.scene.leafTris = scene->itemTris.ptr; }
 
-    if (scene->chunkCapacity < (size_t)nUnits) {
-        HIP_TRY(scene->chunkBuf.allocate((size_t)nUnits));
-        scene->chunkCapacity = (size_t)nUnits;
-    }
-    if (!scene->counters.ptr) { HIP_TRY(scene->counters.allocate(kMaxPools * kCtrCount)); }
-    if (!scene->stats.ptr) {
-        HIP_TRY(scene->stats.allocate(kStatCount));
-        HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
-    }
-
-    const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
-    const bool small = scene->bruteForce;   // <= 64 triangles, <= 16 spheres: the all-triangles intersector
-    const size_t lds = (size_t)((small ? 8 : scene->stackRows) + 1) * kBlock * sizeof(int)
-        + (ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0);
-    unsigned long long blocks = (unsigned long long)scene->computeUnits * PATHED_VOLUME_WAVES;   // what the kernel's register budget keeps resident
-    const unsigned long long blocksNeeded = (nUnits64 + (unsigned long long)kBlock - 1) / kBlock;
-    if (blocks > blocksNeeded) { blocks = blocksNeeded; }
-    if (blocks < 1) { blocks = 1; }
-    const unsigned int waves = (unsigned int)blocks * kWavesPerBlock;
-    const size_t overflowRows = (size_t)(scene->maxStack > scene->stackRows ? scene->maxStack - scene->stackRows : 0);
-    const size_t overflowInts = (size_t)blocks * kBlock * (overflowRows ? overflowRows : 1);
-    if (scene->volumeOverflow.count < overflowInts) { HIP_TRY(scene->volumeOverflow.allocate(overflowInts)); }
-
-    RenderParams params;
-    std::memset(&params, 0, sizeof params);
-    params.scene = scene->device;
-    params.state.chunkBuf = scene->chunkBuf.ptr;
-    params.counters = scene->counters.ptr;
-    params.stats = scene->stats.ptr;
-    params.stackOverflow = scene->volumeOverflow.ptr;
-    params.maxStack = scene->maxStack;
-    params.accum = d_accum;
-    params.nPixels = nPixels;
-    if (!fillUnitOrder(params, scene->unitOrder, scene->width, scene->height, chunksPerPixel, 0, 1,
-                       (int)(waves < (unsigned int)kUnitQueues ? waves : (unsigned int)kUnitQueues))) {
-        return fail(PATHED_E_INVALID, "too many work units in one pass");
-    }
-    {
-        const unsigned int wavesPerQueue = (waves + (unsigned int)params.nQueues - 1) / (unsigned int)params.nQueues;
-        unsigned int grab = (nUnits / (unsigned int)params.nQueues) / (wavesPerQueue * 4u);
-        params.unitGrab = (int)(grab < 1u ? 1u : grab > 64u ? 64u : grab);
-    }
-    params.chunk = chunk;
-    params.chunksPerPixel = chunksPerPixel;
-    params.seedLo = (uint32_t)seed;
-    params.seedHi = (uint32_t)(seed >> 32);
-    params.sppBegin = begin;
-    params.sppEnd = begin + count;
-    params.startBounce = start_bounce;
-    params.lastBounce = last_bounce;
-
-    HIP_TRY(hipMemsetAsync(params.counters, 0, kCtrCount * sizeof(unsigned int), stream));
-    const dim3 grid((unsigned)blocks);
-    int timed = -1;
-    if (scene->timeKernels) {
-        timed = scene->traceEvents.acquire();
-        (void)hipEventRecord(scene->traceEvents.start[timed], stream);
-    }
-    // scenes made of quads: phase 1 over the item records (small_items.h), phase 2 over the item-ordered triangles
-    const bool quads = small && ldsMaterials && scene->smallLayout.nQuads > 0;
-    params.smallQuads = quads ? scene->smallLayout.nQuads : 0;
-    params.smallKappaT = scene->smallLayout.kappaT;
-    if (quads) { params.scene.leafTris = scene->itemTris.ptr; }
-    launchVolume(scene->stackRows, small, scene->lambertianGlassContainer, params, quads ? scene->smallItems : scene->smallTris, grid, lds, ldsMaterials, stream);
-    if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], stream); }
-    scene->traceLaunchesAll++;
-    const dim3 pixelGrid((unsigned)((nPixels + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_resolve, pixelGrid, dim3(kBlock), 0, stream, params);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-
-    scene->iterations += 1;
-    scene->cameraSamples += (unsigned long long)count * (unsigned long long)nPixels;
-    return PATHED_OK;
+        // k_path_volume<LDS_MATERIALS, STACK, SMALL, TRAITS, QUADS>: the narrowed set and QUADS exist for small scenes with the
+        // materials in LDS only
+        const auto run = [&](void (*kernel)(RenderParams, SmallTris)) {
+            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, quads ? scene->smallItems : scene->smallTris);
+        };
+        if (small && ldsMaterials && scene->traits.lambertianGlassContainer) {   // the reference's own volume scene kinds
+            withBool(quads, [&](auto QUADS) { run(k_path_volume<true, 8, true, TraitsLambertianGlassContainer, QUADS>); });
+        } else if (quads) {
+            run(k_path_volume<true, 8, true, TraitsAll, true>);
+        } else {
+            withBool(ldsMaterials, [&](auto LDS_MATERIALS) {
+                if (small) { run(k_path_volume<LDS_MATERIALS, 8, true>); return; }
+                switch (scene->stackRows) {
+                case 8: run(k_path_volume<LDS_MATERIALS, 8, false>); break;
+                case 16: run(k_path_volume<LDS_MATERIALS, 16, false>); break;
+                default: run(k_path_volume<LDS_MATERIALS, 22, false>); break;
+                }
+            });
+        }
+    });
 }
 
-// One internal pass of the path tracer over a BVH with the paths on chip (k_path_wave, path_wave.h): one persistent launch.
-static int renderPassWave(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_t count,
-                          int start_bounce, int last_bounce, float *d_accum, hipStream_t stream)
+// The path tracer over a BVH with the paths on chip (k_path_wave, path_wave.h).
+static int renderPassWave(PathedScene *scene, const Pass &pass)
 {
-    const int nPixels = scene->width * scene->height;
-    const int chunk = scene->samplesPerUnit;
-    const int chunksPerPixel = (int)((count + (uint32_t)chunk - 1) / (uint32_t)chunk);
-    const unsigned long long nUnits64 = (unsigned long long)nPixels * (unsigned long long)chunksPerPixel;
-    if (nUnits64 >= 0xFFFFFFF0ull) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
-    const unsigned int nUnits = (unsigned int)nUnits64;
-
-    if (scene->chunkCapacity < (size_t)nUnits) {
-        HIP_TRY(scene->chunkBuf.allocate((size_t)nUnits));
-        scene->chunkCapacity = (size_t)nUnits;
-    }
-    if (!scene->counters.ptr) { HIP_TRY(scene->counters.allocate(kMaxPools * kCtrCount)); }
-    if (!scene->stats.ptr) {
-        HIP_TRY(scene->stats.allocate(kStatCount));
-        HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
-    }
-
     const int stackRows = 22;
-    const size_t lds = pathWaveLdsBytes(stackRows, scene->device.nMaterials, PATHED_EXPERIMENTS && scene->waveBlock);
-    unsigned long long blocks = (unsigned long long)scene->computeUnits * PATHED_WAVE_WAVES;
-    const unsigned long long blocksNeeded = (nUnits64 + (unsigned long long)kBlock - 1) / kBlock;
-    if (blocks > blocksNeeded) { blocks = blocksNeeded; }
-    if (blocks < 1) { blocks = 1; }
-    const unsigned int waves = (unsigned int)blocks * kWavesPerBlock;
-    const size_t overflowRows = (size_t)(scene->maxStack > stackRows ? scene->maxStack - stackRows : 0);
-    const size_t overflowInts = (size_t)blocks * kBlock * (overflowRows ? overflowRows : 1);
-    if (scene->volumeOverflow.count < overflowInts) { HIP_TRY(scene->volumeOverflow.allocate(overflowInts)); }
+    return persistentPass(scene, pass, PATHED_WAVE_WAVES, scene->maxStack, stackRows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
+        const size_t lds = pathWaveLdsBytes(stackRows, scene->device.nMaterials, PATHED_EXPERIMENTS && scene->waveBlock);
+        params.suspendLanes = scene->waveStragglers;
+        params.suspendPatience = scene->waveRefill;   // k_path_wave: idle lanes are refilled from the wave's list once fewer than this many are busy
+        params.parkMinCardsPerWave = scene->waveShadeReady;   // k_path_wave<BLOCK>: a wave shades once this many of its paths have their rays back
 
-    RenderParams params;
-    std::memset(&params, 0, sizeof params);
-    params.scene = scene->device;
-    params.state.chunkBuf = scene->chunkBuf.ptr;
-    params.counters = scene->counters.ptr;
-    params.stats = scene->stats.ptr;
-    params.stackOverflow = scene->volumeOverflow.ptr;
-    params.maxStack = scene->maxStack;
-    params.suspendLanes = scene->waveStragglers;
-    params.suspendPatience = scene->waveRefill;   // k_path_wave: idle lanes are refilled from the wave's list once fewer than this many are busy
-    params.accum = d_accum;
-    params.nPixels = nPixels;
-    if (!fillUnitOrder(params, scene->unitOrder, scene->width, scene->height, chunksPerPixel, 0, 1,
-                       (int)(waves < (unsigned int)kUnitQueues ? waves : (unsigned int)kUnitQueues))) {
-        return fail(PATHED_E_INVALID, "too many work units in one pass");
-    }
-    {
-        const unsigned int wavesPerQueue = (waves + (unsigned int)params.nQueues - 1) / (unsigned int)params.nQueues;
-        unsigned int grab = (nUnits / (unsigned int)params.nQueues) / (wavesPerQueue * 4u);
-        params.unitGrab = (int)(grab < 1u ? 1u : grab > 64u ? 64u : grab);
-    }
-    params.chunk = chunk;
-    params.chunksPerPixel = chunksPerPixel;
-    params.seedLo = (uint32_t)seed;
-    params.seedHi = (uint32_t)(seed >> 32);
-    params.sppBegin = begin;
-    params.sppEnd = begin + count;
-    params.startBounce = start_bounce;
-    params.lastBounce = last_bounce;
-
-    HIP_TRY(hipMemsetAsync(params.counters, 0, kCtrCount * sizeof(unsigned int), stream));
-    const dim3 grid((unsigned)blocks);
-    int timed = -1;
-    if (scene->timeKernels) {
-        timed = scene->traceEvents.acquire();
-        (void)hipEventRecord(scene->traceEvents.start[timed], stream);
-    }
-    params.parkMinCardsPerWave = scene->waveShadeReady;   // k_path_wave<BLOCK>: a wave shades once this many of its paths have their rays back
+        // k_path_wave<LDS_MATERIALS, STACK, TRAITS, SPHERES, BLOCK>
+        const SceneTraitFlags &traits = scene->traits;
+        const bool envOnly = traits.envOnly && scene->device.nSpheres == 0 && !scene->hasContainers;
+        const auto run = [&](void (*kernel)(RenderParams)) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params); };
 #if PATHED_EXPERIMENTS
-    // the block's waves sharing one ray ring: measured 13-20 % slower than a list per wave (profiles/r4_ab_wave.log)
-    if (scene->waveBlock && scene->envOnly && scene->device.nSpheres == 0 && !scene->hasContainers) { hipLaunchKernelGGL((k_path_wave<true, 22, TraitsEnvironmentOnly, false, true>), grid, dim3(kBlock), lds, stream, params); }
-    else
+        // the block's waves sharing one ray ring: measured 13-20 % slower than a list per wave (profiles/r4_ab_wave.log)
+        if (scene->waveBlock && envOnly) { run(k_path_wave<true, 22, TraitsEnvironmentOnly, false, true>); }
+        else
 #endif
-    if (scene->envOnly && scene->device.nSpheres == 0 && !scene->hasContainers) { hipLaunchKernelGGL((k_path_wave<true, 22, TraitsEnvironmentOnly, false>), grid, dim3(kBlock), lds, stream, params); }
-    else if (scene->smoothSet) { hipLaunchKernelGGL((k_path_wave<true, 22, TraitsSmooth, false>), grid, dim3(kBlock), lds, stream, params); }
-    else if (scene->triangleLit) { hipLaunchKernelGGL((k_path_wave<true, 22, TraitsTriangleLit, false>), grid, dim3(kBlock), lds, stream, params); }
-    else if (scene->device.nSpheres == 0) { hipLaunchKernelGGL((k_path_wave<true, 22, TraitsAll, false>), grid, dim3(kBlock), lds, stream, params); }
-    else { hipLaunchKernelGGL((k_path_wave<true, 22, TraitsAll, true>), grid, dim3(kBlock), lds, stream, params); }
-    if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], stream); }
-    scene->traceLaunchesAll++;
-    const dim3 pixelGrid((unsigned)((nPixels + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_resolve, pixelGrid, dim3(kBlock), 0, stream, params);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-
-    scene->iterations += 1;
-    scene->cameraSamples += (unsigned long long)count * (unsigned long long)nPixels;
-    return PATHED_OK;
+        if (envOnly) { run(k_path_wave<true, 22, TraitsEnvironmentOnly, false>); }
+        else if (traits.smoothSet) { run(k_path_wave<true, 22, TraitsSmooth, false>); }
+        else if (traits.triangleLit) { run(k_path_wave<true, 22, TraitsTriangleLit, false>); }
+        else if (scene->device.nSpheres == 0) { run(k_path_wave<true, 22, TraitsAll, false>); }
+        else { run(k_path_wave<true, 22, TraitsAll, true>); }
+    });
 }
 
-// One internal pass of the hybrid path kernel (k_path_hybrid, path_hybrid.h): as renderPassFused, one persistent launch.
-static int renderPassHybrid(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_t count,
-                            int start_bounce, int last_bounce, float *d_accum, hipStream_t stream)
+// The hybrid path kernel (k_path_hybrid, path_hybrid.h): a direct set of large triangles and a tree of its own for the rest.
+static int renderPassHybrid(PathedScene *scene, const Pass &pass)
 {
-    const int nPixels = scene->width * scene->height;
-    const int chunk = scene->samplesPerUnit;
-    const int chunksPerPixel = (int)((count + (uint32_t)chunk - 1) / (uint32_t)chunk);
-    const unsigned long long nUnits64 = (unsigned long long)nPixels * (unsigned long long)chunksPerPixel;
-    if (nUnits64 >= 0xFFFFFFF0ull) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
-    const unsigned int nUnits = (unsigned int)nUnits64;
+    return persistentPass(scene, pass, PATHED_HYBRID_WAVES, scene->hybridMaxStack, kHybridStackRows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
+        const PathedSceneOptions &options = scene->options;
+        const size_t lds = (size_t)scene->device.nMaterials * sizeof(DMaterial);
+        params.smallQuads = scene->hybridLayout.nQuads;
+        params.smallKappaT = scene->hybridLayout.kappaT;
+        params.scene.leafTris = scene->hybridItemTris.ptr;   // the direct set in item order
+        params.hybridNodes = scene->hybridNodes.ptr;
+        params.hybridTris = scene->hybridTris.ptr;
+        params.hybridNodeCount = scene->hybridNodeCount;
+        params.hybridTreeTris = scene->hybridTreeTris;
+        params.hybridDirectTris = scene->hybridDirectTris;
+        for (int a = 0; a < 3; a++) { params.hybridLo[a] = scene->hybridLo[a]; params.hybridHi[a] = scene->hybridHi[a]; }
+        for (int a = 0; a < 4; a++) { params.hybridSphere[a] = scene->hybridSphere[a]; }
+        // scheduling of its bursts (PathedSceneOptions.wave_stragglers / wave_refill): results do not depend on them
+        params.suspendLanes = options.wave_stragglers != 0 ? (options.wave_stragglers < 0 ? 0 : options.wave_stragglers) : kHybridStragglers;
+        params.suspendPatience = options.wave_refill != 0 ? options.wave_refill : kHybridRefill;
+        params.hybridBatch = options.hybrid_batch != 0 ? options.hybrid_batch : kHybridBatch;
+        params.hybridReady = options.hybrid_ready != 0 ? (options.hybrid_ready < 0 ? 1 : options.hybrid_ready) : kHybridReady;
 
-    if (scene->chunkCapacity < (size_t)nUnits) {
-        HIP_TRY(scene->chunkBuf.allocate((size_t)nUnits));
-        scene->chunkCapacity = (size_t)nUnits;
-    }
-    if (!scene->counters.ptr) { HIP_TRY(scene->counters.allocate(kMaxPools * kCtrCount)); }
-    if (!scene->stats.ptr) {
-        HIP_TRY(scene->stats.allocate(kStatCount));
-        HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
-    }
-
-    unsigned long long blocks = (unsigned long long)scene->computeUnits * PATHED_HYBRID_WAVES;
-    const unsigned long long blocksNeeded = (nUnits64 + (unsigned long long)kBlock - 1) / kBlock;
-    if (blocks > blocksNeeded) { blocks = blocksNeeded; }
-    if (blocks < 1) { blocks = 1; }
-    const unsigned int waves = (unsigned int)blocks * kWavesPerBlock;
-    const size_t overflowRows = (size_t)(scene->hybridMaxStack > kHybridStackRows ? scene->hybridMaxStack - kHybridStackRows : 0);
-    const size_t overflowInts = (size_t)blocks * kBlock * (overflowRows ? overflowRows : 1);
-    if (scene->volumeOverflow.count < overflowInts) { HIP_TRY(scene->volumeOverflow.allocate(overflowInts)); }
-
-    RenderParams params;
-    std::memset(&params, 0, sizeof params);
-    params.scene = scene->device;
-    params.state.chunkBuf = scene->chunkBuf.ptr;
-    params.counters = scene->counters.ptr;
-    params.stats = scene->stats.ptr;
-    params.stackOverflow = scene->volumeOverflow.ptr;
-    params.maxStack = scene->hybridMaxStack;
-    params.accum = d_accum;
-    params.nPixels = nPixels;
-    if (!fillUnitOrder(params, scene->unitOrder, scene->width, scene->height, chunksPerPixel, 0, 1,
-                       (int)(waves < (unsigned int)kUnitQueues ? waves : (unsigned int)kUnitQueues))) {
-        return fail(PATHED_E_INVALID, "too many work units in one pass");
-    }
-    {
-        const unsigned int wavesPerQueue = (waves + (unsigned int)params.nQueues - 1) / (unsigned int)params.nQueues;
-        unsigned int grab = (nUnits / (unsigned int)params.nQueues) / (wavesPerQueue * 4u);
-        params.unitGrab = (int)(grab < 1u ? 1u : grab > 64u ? 64u : grab);
-    }
-    params.chunk = chunk;
-    params.chunksPerPixel = chunksPerPixel;
-    params.seedLo = (uint32_t)seed;
-    params.seedHi = (uint32_t)(seed >> 32);
-    params.sppBegin = begin;
-    params.sppEnd = begin + count;
-    params.startBounce = start_bounce;
-    params.lastBounce = last_bounce;
-    params.smallQuads = scene->hybridLayout.nQuads;
-    params.smallKappaT = scene->hybridLayout.kappaT;
-    params.scene.leafTris = scene->hybridItemTris.ptr;   // the direct set in item order
-    params.hybridNodes = scene->hybridNodes.ptr;
-    params.hybridTris = scene->hybridTris.ptr;
-    params.hybridNodeCount = scene->hybridNodeCount;
-    params.hybridTreeTris = scene->hybridTreeTris;
-    params.hybridDirectTris = scene->hybridDirectTris;
-    for (int a = 0; a < 3; a++) { params.hybridLo[a] = scene->hybridLo[a]; params.hybridHi[a] = scene->hybridHi[a]; }
-    for (int a = 0; a < 4; a++) { params.hybridSphere[a] = scene->hybridSphere[a]; }
-    // scheduling of its bursts (PathedSceneOptions.wave_stragglers / wave_refill): results do not depend on them
-    params.suspendLanes = scene->options.wave_stragglers != 0 ? (scene->options.wave_stragglers < 0 ? 0 : scene->options.wave_stragglers) : kHybridStragglers;
-    params.suspendPatience = scene->options.wave_refill != 0 ? scene->options.wave_refill : kHybridRefill;
-    params.hybridBatch = scene->options.hybrid_batch != 0 ? scene->options.hybrid_batch : kHybridBatch;
-    params.hybridReady = scene->options.hybrid_ready != 0 ? (scene->options.hybrid_ready < 0 ? 1 : scene->options.hybrid_ready) : kHybridReady;
-
-    HIP_TRY(hipMemsetAsync(params.counters, 0, kCtrCount * sizeof(unsigned int), stream));
-    const dim3 grid((unsigned)blocks), block(kBlock);
-    const size_t lds = (size_t)scene->device.nMaterials * sizeof(DMaterial);
-    int timed = -1;
-    if (scene->timeKernels) {
-        timed = scene->traceEvents.acquire();
-        (void)hipEventRecord(scene->traceEvents.start[timed], stream);
-    }
-    // the narrowest instantiation whose compile-time scene set contains this scene's (shading.h: SceneTraits)
-    if (scene->envOnly && !scene->hasContainers) { hipLaunchKernelGGL((k_path_hybrid<TraitsEnvironmentOnly>), grid, block, lds, stream, params, scene->hybridItems); }
-    else if (scene->smoothSet) { hipLaunchKernelGGL((k_path_hybrid<TraitsSmooth>), grid, block, lds, stream, params, scene->hybridItems); }
-    else if (scene->triangleLit) { hipLaunchKernelGGL((k_path_hybrid<TraitsTriangleLit>), grid, block, lds, stream, params, scene->hybridItems); }
-    else { hipLaunchKernelGGL((k_path_hybrid<TraitsAll>), grid, block, lds, stream, params, scene->hybridItems); }
-    if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], stream); }
-    scene->traceLaunchesAll++;
-    const dim3 pixelGrid((unsigned)((nPixels + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_resolve, pixelGrid, block, 0, stream, params);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-
-    scene->iterations += 1;
-    scene->cameraSamples += (unsigned long long)count * (unsigned long long)nPixels;
-    return PATHED_OK;
+        // k_path_hybrid<TRAITS>: the narrowest instantiation whose compile-time scene set contains this scene's
+        const SceneTraitFlags &traits = scene->traits;
+        const auto run = [&](void (*kernel)(RenderParams, SmallTris)) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, scene->hybridItems); };
+        if (traits.envOnly && !scene->hasContainers) { run(k_path_hybrid<TraitsEnvironmentOnly>); }
+        else if (traits.smoothSet) { run(k_path_hybrid<TraitsSmooth>); }
+        else if (traits.triangleLit) { run(k_path_hybrid<TraitsTriangleLit>); }
+        else { run(k_path_hybrid<TraitsAll>); }
+    });
 }
 
-// One internal pass: samples [begin, begin+count), count <= chunk * kMaxChunksPerPass.
+// A pass on the wavefront kernels (k_init, k_trace / k_trace_small, k_shade over a pool of path slots in HBM).
 // The slot pool is split into `pools` independent halves, each with its own unit range,
 // counters and HIP stream: while one half runs its (ALU-bound) trace kernel the other runs its
 // (memory-bound) shade kernel, so the two overlap instead of alternating.
-static int renderPass(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_t count,
-                      int start_bounce, int last_bounce, float *d_accum, hipStream_t stream)
+static int renderPass(PathedScene *scene, const Pass &pass)
 {
-    const int nPixels = scene->width * scene->height;
-    const int chunk = scene->samplesPerUnit;
-    const int chunksPerPixel = (int)((count + (uint32_t)chunk - 1) / (uint32_t)chunk);
-    const unsigned long long nUnits64 = (unsigned long long)nPixels * (unsigned long long)chunksPerPixel;
-    if (nUnits64 >= 0xFFFFFFF0ull) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
-    const unsigned int nUnits = (unsigned int)nUnits64;
+    const hipStream_t stream = pass.stream;
+    const int nPixels = pass.nPixels;
+    const unsigned long long nUnits64 = pass.nUnits;
 
     // small jobs use one pool; otherwise split slots and units evenly
     int pools = scene->pools;
@@ -2572,7 +2333,7 @@ static int renderPass(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_
     const unsigned long long slotQuantum = (unsigned long long)kBlock * (scene->stagedShade ? scene->stageRounds : 1);
     const int slotsPerPool = (int)((wanted / pools + slotQuantum - 1) / slotQuantum * slotQuantum);
     const int nSlots = slotsPerPool * pools;
-    int code = ensureRenderState(scene, nSlots, (size_t)nUnits);
+    int code = ensureRenderState(scene, nSlots, (size_t)pass.nUnits);
     if (code != PATHED_OK) { return code; }
     if (pools > 1 && !scene->poolStreams[0]) {
         for (int h = 0; h < kMaxPools; h++) {
@@ -2588,11 +2349,12 @@ static int renderPass(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_
     const int nQueues = shadeBlocks < kUnitQueues ? shadeBlocks : kUnitQueues;
 
     RenderParams params[kMaxPools];
+    std::memset(params, 0, sizeof params);
     hipStream_t streams[kMaxPools] = { stream, stream, stream, stream };
     for (int h = 0; h < pools; h++) {
         RenderParams &q = params[h];
         const size_t slotBase = (size_t)h * slotsPerPool;
-        q.scene = scene->device;
+        if (!fillPassParams(q, scene, pass, h, pools, nQueues)) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
         q.state.rayO = scene->rayO.ptr + slotBase;
         q.state.rayD = scene->rayD.ptr + slotBase;
         q.state.hit = scene->hit.ptr + slotBase;
@@ -2603,7 +2365,6 @@ static int renderPass(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_
         q.state.acc = scene->acc.ptr + slotBase;
         q.state.shO = scene->shO.ptr + slotBase;
         q.state.shD = scene->shD.ptr + slotBase;
-        q.state.chunkBuf = scene->chunkBuf.ptr;
         if (scene->splitShade) {
             const size_t listEntries = (size_t)scene->listCap * kListShards * 64;
             for (int list = 0; list < 2; list++) {
@@ -2614,7 +2375,6 @@ static int renderPass(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_
             }
             q.listCap = scene->listCap;
         }
-        q.counters = scene->counters.ptr + (size_t)h * kCtrCount;
         const size_t traceWaves = (size_t)scene->traceGrid * kWavesPerBlock;
         q.suspendLanes = scene->bruteForce ? 0 : scene->suspendLanes;
         q.suspendPatience = scene->suspendPatience;
@@ -2628,21 +2388,7 @@ static int renderPass(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_
                 : scene->stackOverflow.ptr + (size_t)h * (size_t)scene->traceGrid * kBlock * (overflowRows ? overflowRows : 1);
             q.maxStack = scene->maxStack;
         }
-        q.stats = scene->stats.ptr;
-        q.accum = d_accum;
         q.nSlots = slotsPerPool;
-        q.nPixels = nPixels;
-        if (!fillUnitOrder(q, scene->unitOrder, scene->width, scene->height, chunksPerPixel, h, pools, nQueues)) {
-            return fail(PATHED_E_INVALID, "too many work units in one pass");
-        }
-        q.chunk = chunk;
-        q.chunksPerPixel = chunksPerPixel;
-        q.seedLo = (uint32_t)seed;
-        q.seedHi = (uint32_t)(seed >> 32);
-        q.sppBegin = begin;
-        q.sppEnd = begin + count;
-        q.startBounce = start_bounce;
-        q.lastBounce = last_bounce;
         // local rays (per-slot shade kernel only: the staged and split stages of the experiments build do not know them)
         q.localCount = (!scene->stagedShade && !scene->splitShade) ? scene->localCount : 0;
         q.localCounting = scene->countMode ? 1 : 0;
@@ -2769,9 +2515,11 @@ static int renderPass(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_
     HIP_TRY(hipGetLastError());
 
     scene->iterations += iteration;
-    scene->cameraSamples += (unsigned long long)count * (unsigned long long)nPixels;
+    scene->cameraSamples += (unsigned long long)pass.count * (unsigned long long)nPixels;
     return PATHED_OK;
 }
+
+extern "C" {
 
 int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
                              uint32_t spp_begin, uint32_t spp_count,
@@ -2819,20 +2567,29 @@ int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
     const bool hybridPath = scene->hybridPath && !usesVolumeKernel(scene) && !scene->countMode;
     scene->lastCallWave = wavePath && !hybridPath;
     scene->lastCallHybrid = hybridPath;
+    Pass pass;
+    pass.seed = seed;
+    pass.startBounce = start_bounce;
+    pass.lastBounce = last_bounce;
+    pass.accum = d_accum_rgb_sum;
+    pass.stream = stream;
+    pass.nPixels = scene->width * scene->height;
+    pass.chunk = scene->samplesPerUnit;
     uint32_t done = 0;
     while (done < spp_count) {
-        const uint32_t count = (spp_count - done < perPass) ? (spp_count - done) : perPass;
-        const int code = usesVolumeKernel(scene)
-            ? renderPassVolume(scene, seed, spp_begin + done, count, start_bounce, last_bounce, d_accum_rgb_sum, stream)
-            : scene->fusedPath
-                ? renderPassFused(scene, seed, spp_begin + done, count, start_bounce, last_bounce, d_accum_rgb_sum, stream)
-            : hybridPath
-                ? renderPassHybrid(scene, seed, spp_begin + done, count, start_bounce, last_bounce, d_accum_rgb_sum, stream)
-            : wavePath
-                ? renderPassWave(scene, seed, spp_begin + done, count, start_bounce, last_bounce, d_accum_rgb_sum, stream)
-                : renderPass(scene, seed, spp_begin + done, count, start_bounce, last_bounce, d_accum_rgb_sum, stream);
+        pass.begin = spp_begin + done;
+        pass.count = (spp_count - done < perPass) ? (spp_count - done) : perPass;
+        pass.chunksPerPixel = (int)((pass.count + (uint32_t)pass.chunk - 1) / (uint32_t)pass.chunk);
+        const unsigned long long nUnits = (unsigned long long)pass.nPixels * (unsigned long long)pass.chunksPerPixel;
+        if (nUnits >= 0xFFFFFFF0ull) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
+        pass.nUnits = (unsigned int)nUnits;
+        const int code = usesVolumeKernel(scene) ? renderPassVolume(scene, pass)
+            : scene->fusedPath ? renderPassFused(scene, pass)
+            : hybridPath ? renderPassHybrid(scene, pass)
+            : wavePath ? renderPassWave(scene, pass)
+            : renderPass(scene, pass);
         if (code != PATHED_OK) { return code; }
-        done += count;
+        done += pass.count;
     }
     if (scene->timeKernels) {
         scene->traceEvents.harvestAll();

@@ -79,6 +79,11 @@ def test_vgpr_budgets_of_the_hot_kernels(tmp_path):
     smooth = [v for k, v in hybrid.items() if "SceneTraitsILj49E" in k]
     assert len(smooth) == 1 and smooth[0]["ScratchSize"] <= 192, hybrid   # (parked-ray words and the burst state: 164 bytes today)
 
+    # everything the launch ladders of pathed_hip.hip instantiate: a rung that adds a symbol by accident (a counting variant of a
+    # set that has none, say) lengthens the build and fails here
+    totals = {name: sum(1 for k in usage if "%d%sI" % (len(name), name) in k) for name in ("k_path_small", "k_path_volume", "k_path_wave", "k_trace")}
+    assert totals == {"k_path_small": 20, "k_path_volume": 11, "k_path_wave": 5, "k_trace": 18}, totals
+
 
 @pytest.mark.skipif(not os.environ.get("PATHED_TEST_EXPERIMENTS"), reason="compiles the experiments build (minutes): set PATHED_TEST_EXPERIMENTS=1")
 def test_vgpr_budgets_of_the_experimental_kernels(tmp_path):
