@@ -401,6 +401,19 @@ int pathed_hip_trace(PathedScene *scene, const float *rays, size_t n,
  * Phase 1 is correct iff accepted is a subset of candidates for every ray. */
 int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out);
 
+/* Test hook onto the records that hold per-triangle and per-light constants of the shading code (built on the device at scene
+ * creation and again by a refit), next to what the per-vertex functions compute for the same triangles.
+ * triangles: n_triangles * 20 floats, host memory, per primitive
+ *       [0..3]   triangleSample's normal (xyz) and inverse pdf (the area)                   computed by the per-vertex functions
+ *       [4..7]   trianglePdfSolidAngle's area pdf 1 / area; sampleLightsTerm's invPDF and 1 / invPDF for the scene's light count; -
+ *       [8..11]  makeIsect's shading normal of a triangle without vertex normals (xyz); -
+ *       [12..15] the shading record's (normal xyz, 1 / area) read where a BSDF sample meets an emitter      the stored records
+ *       [16..19] the stored shading normal (xyz) of the plain-triangle record; -
+ * lights:    room for max_lights * 18 floats; *n_lights lights are written, each as kind, primitive (as floats), then its 64-byte
+ *       sampling record (p0, material bits) (p1, area) (p2, invPDF) (normal, 1 / invPDF); all zero for a light that is not a triangle.
+ * n_triangles must be the scene's triangle count; more lights than max_lights is PATHED_E_INVALID. */
+int pathed_hip_debug_light_records(PathedScene *scene, float *triangles, size_t n_triangles, float *lights, size_t max_lights, int *n_lights);
+
 /* 1 in libpathed_hip_experiments.so (`make experiments`), 0 in the product library.  The experiments build adds the
  * kernel organisations that were measured and rejected: shade_kernel 2 (staged) and 4 (split),
  * node_format 2 / 3 (compressed nodes), small_phase1 2 (matrix pipe) and pathed_hip_measure_valu_clocks; the product

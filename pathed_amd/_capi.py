@@ -190,6 +190,7 @@ HIP_SYMBOLS = [
     "pathed_hip_render_device",
     "pathed_hip_trace",
     "pathed_hip_debug_small_candidates",
+    "pathed_hip_debug_light_records",
     "pathed_hip_has_experiments",
     "pathed_hip_scene_refit",
     "pathed_hip_set_samples_per_unit",
@@ -290,6 +291,8 @@ def load_hip():
     lib.pathed_hip_trace.restype = C.c_int
     lib.pathed_hip_debug_small_candidates.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint64)]
     lib.pathed_hip_debug_small_candidates.restype = C.c_int
+    lib.pathed_hip_debug_light_records.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int)]
+    lib.pathed_hip_debug_light_records.restype = C.c_int
     lib.pathed_hip_scene_refit.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.pathed_hip_scene_refit.restype = C.c_int
     lib.pathed_hip_has_experiments.argtypes = []

@@ -28,9 +28,19 @@ static_assert(sizeof(DMaterial) == 96, "DMaterial is staged in LDS as 24 words")
 
 // per-triangle shading record, indexed by ORIGINAL primitive id (128 B = 8 x float4):
 //   q0 = (p0, material)  q1 = (p1, uv0.u)  q2 = (p2, uv0.v)
-//   q3 = (n0, uv1.u)     q4 = (n1, uv1.v)  q5 = (n2, uv2.u)  q6 = (uv2.v, -, -, -)  q7 = pad
+//   q3 = (n0, uv1.u)     q4 = (n1, uv1.v)  q5 = (n2, uv2.u)  q6 = (uv2.v, -, -, -)
+//   q7 = (normalized(cross(p1 - p0, p2 - p0)), 1 / triangleArea): what trianglePdfSolidAngle derives from the corners alone,
+//        read where a BSDF sample meets an emissive triangle (kernels.h: lightsPDF)
 static const int kTriShadeQuads = 8;
 static const int kMaxPlainRanges = 8;
+// per-primitive record of the plain ranges (32 B = 2 x float4), what makeIsect needs of such a triangle:
+//   c0 = (geometric normal, material)  c1 = (normalized(geometric normal): the shading normal, -)
+static const int kTriCompactQuads = 2;
+// per-light sampling record, indexed like DScene::lights (64 B = 4 x float4; triangle lights only, zero for the others):
+// the corners and what triangleSample and sampleLightsTerm derive from the triangle and the light count alone
+//   l0 = (p0, material)  l1 = (p1, area)  l2 = (p2, invPDF = area * (1 / lightChoicePDF))
+//   l3 = (normalized(cross(p1 - p0, p2 - p0)), 1 / invPDF)
+static const int kLightRecordQuads = 4;
 
 struct DSphere {
     float centerWorld[3];
@@ -88,7 +98,7 @@ struct DScene {
 
     // shading
     const float4 *triShade;    // kTriShadeQuads x float4 per original primitive
-    const float4 *triCompact;  // one float4 per original primitive: (geometric normal, material); valid for the primitives of the plain ranges
+    const float4 *triCompact;  // kTriCompactQuads x float4 per original primitive; valid for the primitives of the plain ranges
     // primitive-id ranges [begin, end) made of triangles without vertex normals and uvs ("plain": shaded from triCompact
     // alone).  Whole meshes, merged when adjacent; a scene with more ranges than fit keeps the first kMaxPlainRanges.
     int plainBegin[8], plainEnd[8];
@@ -96,6 +106,7 @@ struct DScene {
     const DMaterial *materials;
     int nMaterials;
     const DLight *lights;
+    const float4 *lightRecords;   // kLightRecordQuads x float4 per light
     int nLights;
     int hasEnv;
     DEnv env;

@@ -1390,23 +1390,6 @@ __global__ __launch_bounds__(kBlock) void k_trace_rays(
 
 // ------------------------------------------------------------------------- shade
 
-struct TriShade {
-    V3 p0, p1, p2;
-    int material;
-};
-
-__device__ inline TriShade loadTriCorners(const DScene &scene, int prim)
-{
-    const float4 *q = scene.triShade + (size_t)kTriShadeQuads * prim;
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
-    TriShade tri;
-    tri.p0 = v3(q0.x, q0.y, q0.z);
-    tri.p1 = v3(q1.x, q1.y, q1.z);
-    tri.p2 = v3(q2.x, q2.y, q2.z);
-    tri.material = floatAsInt(q0.w);
-    return tri;
-}
-
 // Ng = (v1-v0) x (v2-v0), normalised: ONE definition, used where a hit is shaded and where the 16-byte records are built
 __device__ inline V3 triangleNormal(V3 p0, V3 p1, V3 p2) { return normalized(xcross(p1 - p0, p2 - p0)); }
 
@@ -1428,14 +1411,17 @@ __device__ inline Isect makeIsect(const DScene &scene, V3 o, V3 d, float4 h)
 
     if (!TRAITS::spheres || prim < scene.nTris) {
         // A triangle without vertex normals and uvs (all exactly zero: the interpolated shading normal has length 0 and
-        // the geometric normal takes its place, uv = 0) is shaded from a 16-byte record.  Which primitives are plain is a
+        // the geometric normal takes its place, uv = 0) is shaded from a 32-byte record.  Which primitives are plain is a
         // few id ranges in the kernel arguments (scalar compares), so either load is issued at once.
         bool plain = false;
         for (int r = 0; r < scene.nPlainRanges; r++) { plain = plain || (prim >= scene.plainBegin[r] && prim < scene.plainEnd[r]); }
         if (plain) {
-            const float4 compact = scene.triCompact[prim];
-            material = floatAsInt(compact.w);
-            geometricNormal = v3(compact.x, compact.y, compact.z);
+            // ... whose second half is the shading normal such a triangle always ends with, normalized(geometricNormal)
+            const float4 *c = scene.triCompact + (size_t)kTriCompactQuads * prim;
+            const float4 c0 = c[0], c1 = c[1];
+            material = floatAsInt(c0.w);
+            geometricNormal = v3(c0.x, c0.y, c0.z);
+            shadingNormal = v3(c1.x, c1.y, c1.z);
         } else {
             const float4 *q = scene.triShade + (size_t)kTriShadeQuads * prim;
             const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6];
@@ -1450,21 +1436,22 @@ __device__ inline Isect makeIsect(const DScene &scene, V3 o, V3 d, float4 h)
                 fmaf(w, q3.z, fmaf(u, q4.z, v * q5.z)));
             geometricNormal = triangleNormal(p0, p1, p2);
             material = floatAsInt(q0.w);
+            if (length(shadingNormal) == 0.f) { shadingNormal = geometricNormal; }
+            shadingNormal = normalized(shadingNormal);
         }
     } else {
         const DSphere sphere = scene.spheres[prim - scene.nTris];
         const V3 point = o + d * t;
         geometricNormal = normalized(point - v3(sphere.centerWorld[0], sphere.centerWorld[1], sphere.centerWorld[2]));
         material = sphere.material;
+        shadingNormal = normalized(geometricNormal);   // no interpolated normal: length 0, the geometric normal takes its place
     }
-
-    if (length(shadingNormal) == 0.f) { shadingNormal = geometricNormal; }
 
     Isect isect;
     isect.point = o + d * t;  // Ray::at, src/ray.cpp:9-12
     isect.wo = -d;
     isect.normal = geometricNormal;
-    isect.shadingNormal = normalized(shadingNormal);
+    isect.shadingNormal = shadingNormal;
     isect.u = uvU;
     isect.v = uvV;
     isect.material = material;
@@ -1480,8 +1467,9 @@ __device__ inline float lightsPDF(const DScene &scene, V3 referencePoint, const 
 {
     float measurePDF;
     if (!TRAITS::spheres || lightIsect.prim < scene.nTris) {
-        const TriShade tri = loadTriCorners(scene, lightIsect.prim);
-        measurePDF = trianglePdfSolidAngle(tri.p0, tri.p1, tri.p2, lightIsect.point, referencePoint);
+        // trianglePdfSolidAngle with the triangle's own part (normal, 1 / area) from its shading record
+        const float4 q7 = scene.triShade[(size_t)kTriShadeQuads * lightIsect.prim + 7];
+        measurePDF = areaToSolidAngle(q7.w, referencePoint, lightIsect.point, v3(q7.x, q7.y, q7.z));
     } else {
         const DSphere sphere = scene.spheres[lightIsect.prim - scene.nTris];
         measurePDF = spherePdfSolidAngle(
@@ -1530,22 +1518,41 @@ __device__ inline Rgb sampleLightsTerm(
     DLight light;
     light.kind = 2;
     light.index = 0;
+    int lightIndex = 0;
     if (ENV_ONLY) {
         random.dimension++;   // the light choice: floor(u * 1) = 0
     } else {
-        int lightIndex = (int)floorf(random.next() * lightCount);
+        lightIndex = (int)floorf(random.next() * lightCount);
         lightIndex = imin(lightIndex, lightCount - 1);
         light = scene.lights[lightIndex];
     }
 
     SurfaceSample surfaceSample;
     int lightMaterial = 0;
+    // Instantiations whose lights are all triangles sample from the light records (device_scene.h): the normal, the area and
+    // 1 / invPDF are the values the statements here compute from the corners.  Those that also carry sphere or environment
+    // lights compute them: merged across the kinds' branches the record's values cost the generic kernels registers they do
+    // not have (24 more bytes of scratch per lane in the generic fused kernel: profiles/r6_light_records.log).
+    constexpr bool kRecords = !ENV_ONLY && TRAITS::triangleLights && !TRAITS::spheres && !TRAITS::env;
+    float pdfArea = 0.f;
     if (ENV_ONLY) {
         surfaceSample = envSample<TRAITS::pairedTrig>(scene.env, isect.point, random);
-    } else if (TRAITS::triangleLights && (light.kind == 0 || (!TRAITS::spheres && !TRAITS::env))) {
-        const TriShade tri = loadTriCorners(scene, light.index);
-        surfaceSample = triangleSample(tri.p0, tri.p1, tri.p2, random);
-        lightMaterial = tri.material;
+    } else if (!kRecords && TRAITS::triangleLights && light.kind == 0) {
+        const float4 *q = scene.triShade + (size_t)kTriShadeQuads * light.index;
+        const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+        surfaceSample = triangleSample(v3(q0.x, q0.y, q0.z), v3(q1.x, q1.y, q1.z), v3(q2.x, q2.y, q2.z), random);
+        lightMaterial = floatAsInt(q0.w);
+    } else if (kRecords) {
+        const float4 *l = scene.lightRecords + (size_t)kLightRecordQuads * lightIndex;
+        const float4 l0 = l[0], l1 = l[1], l2 = l[2];
+        surfaceSample = triangleSamplePoint(v3(l0.x, l0.y, l0.z), v3(l1.x, l1.y, l1.z), v3(l2.x, l2.y, l2.z), v3(0.f, 0.f, 0.f), l1.w, random);
+        // the corners are spent before the record's last quad is asked for (all four loads in flight at once: Oren-Nayar
+        // Cornell 1 712 against 1 743 Msamples/s, profiles/r6_light_records.log)
+        __builtin_amdgcn_sched_barrier(0);
+        const float4 l3 = l[3];
+        surfaceSample.normal = v3(l3.x, l3.y, l3.z);
+        lightMaterial = floatAsInt(l0.w);
+        pdfArea = l3.w;
     } else if (TRAITS::spheres && (light.kind == 1 || !TRAITS::env)) {
         const DSphere sphere = scene.spheres[light.index];
         surfaceSample = sphereSample<TRAITS::pairedTrig>(
@@ -1561,6 +1568,7 @@ __device__ inline Rgb sampleLightsTerm(
     }
     const float lightChoicePDF = 1.f / lightCount;
     const float invPDF = surfaceSample.invPDF * (1.f / lightChoicePDF);
+    if (!kRecords) { pdfArea = 1.f / invPDF; }
 
     const V3 lightDirection = surfaceSample.point - isect.point;
     const V3 wiWorld = normalized(lightDirection);
@@ -1572,12 +1580,12 @@ __device__ inline Rgb sampleLightsTerm(
     // LightSample::solidAnglePDF, include/scene.h:66-80
     float pdf;
     if (surfaceSample.solidAngle) {
-        pdf = 1.f / invPDF;
+        pdf = pdfArea;
     } else {
         const V3 lightWoForPdf = -normalized(lightDirection);
         const float distance2 = lightDistance * lightDistance;
         const float projectedArea = smax(0.f, dot(surfaceSample.normal, lightWoForPdf));
-        pdf = (1.f / invPDF) * distance2 / projectedArea;
+        pdf = pdfArea * distance2 / projectedArea;
     }
 
     float brdfPDF;
@@ -3389,9 +3397,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
             lightIndex = imin(lightIndex, lightCount - 1);
             light = scene.lights[lightIndex];
             if (TRAITS::triangleLights && light.kind == 0) {
-                const TriShade tri = loadTriCorners(scene, light.index);
-                surfaceSample = triangleSample(tri.p0, tri.p1, tri.p2, random);
-                lightMaterial = tri.material;
+                const LightRecord record = loadLightRecord(scene.lightRecords, lightIndex);
+                surfaceSample = triangleSamplePoint(record.p0, record.p1, record.p2, record.normal, record.area, random);
+                lightMaterial = record.material;
             } else if (TRAITS::spheres && light.kind == 1) {
                 const DSphere sphere = scene.spheres[light.index];
                 surfaceSample = sphereSample<TRAITS::pairedTrig>(v3(sphere.centerSample[0], sphere.centerSample[1], sphere.centerSample[2]), sphere.radius, isect.point, random);
@@ -3535,9 +3543,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
         SurfaceSample surfaceSample;
         int lightMaterial = 0;
         if (TRAITS::triangleLights && light.kind == 0) {
-            const TriShade tri = loadTriCorners(scene, light.index);
-            surfaceSample = triangleSample(tri.p0, tri.p1, tri.p2, random);
-            lightMaterial = tri.material;
+            const LightRecord record = loadLightRecord(scene.lightRecords, lightIndex);
+            surfaceSample = triangleSamplePoint(record.p0, record.p1, record.p2, record.normal, record.area, random);
+            lightMaterial = record.material;
         } else if (TRAITS::spheres && light.kind == 1) {
             const DSphere sphere = scene.spheres[light.index];
             surfaceSample = sphereSample<TRAITS::pairedTrig>(v3(sphere.centerSample[0], sphere.centerSample[1], sphere.centerSample[2]), sphere.radius, samplePoint, random);
@@ -3722,16 +3730,71 @@ __global__ __launch_bounds__(kBlock) void k_build_tri_shade(
         const float value = uvs[2 * (size_t)indices[3 * i + uvCorner] + component];
         if (q == 6) { x = value; } else { w = value; }
     }
-    triShade[(size_t)kTriShadeQuads * i + q] = make_float4(x, y, z, w);
-    // the 16-byte record (makeIsect): geometric normal + material, read for the triangles of the scene's plain ranges.
-    // Lanes 0..2 of the group hold the corners: lane 0 collects them.
+    // Lanes 0..2 of the group hold the corners.  The constants of the triangle are derived here, once, by the very functions
+    // the path kernels would otherwise run at every vertex (same inputs, same operations: same bits).
     const int lane = threadIdx.x & 63, base = lane & ~7;
-    const float x1 = __shfl(x, base + 1), y1 = __shfl(y, base + 1), z1 = __shfl(z, base + 1);
-    const float x2 = __shfl(x, base + 2), y2 = __shfl(y, base + 2), z2 = __shfl(z, base + 2);
-    if (q == 0) {
-        const V3 normal = triangleNormal(v3(x, y, z), v3(x1, y1, z1), v3(x2, y2, z2));
-        triCompact[i] = make_float4(normal.x, normal.y, normal.z, w);
+    const V3 p0 = v3(__shfl(x, base), __shfl(y, base), __shfl(z, base));
+    const V3 p1 = v3(__shfl(x, base + 1), __shfl(y, base + 1), __shfl(z, base + 1));
+    const V3 p2 = v3(__shfl(x, base + 2), __shfl(y, base + 2), __shfl(z, base + 2));
+    if (q == 7) {
+        // q7 (lightsPDF): trianglePdfSolidAngle's normal and areaPDF
+        const V3 normal = triangleSampleNormal(p0, p1, p2);
+        x = normal.x; y = normal.y; z = normal.z;
+        w = 1.f / triangleArea(p0, p1, p2);
     }
+    triShade[(size_t)kTriShadeQuads * i + q] = make_float4(x, y, z, w);
+    // the 32-byte record (makeIsect), read for the triangles of the scene's plain ranges: geometric normal + material, and the
+    // shading normal makeIsect gives a triangle without vertex normals
+    if (q == 0) {
+        const V3 normal = triangleNormal(p0, p1, p2);
+        const V3 shadingNormal = normalized(normal);
+        triCompact[(size_t)kTriCompactQuads * i] = make_float4(normal.x, normal.y, normal.z, w);
+        triCompact[(size_t)kTriCompactQuads * i + 1] = make_float4(shadingNormal.x, shadingNormal.y, shadingNormal.z, 0.f);
+    }
+}
+
+// The per-light sampling records (device_scene.h: kLightRecordQuads) from the shading records: after k_build_tri_shade,
+// wherever that runs.
+__global__ __launch_bounds__(kBlock) void k_build_light_records(const DLight *lights, int nLights, const float4 *triShade, float4 *lightRecords)
+{
+    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (i >= nLights) { return; }
+    float4 *l = lightRecords + (size_t)kLightRecordQuads * i;
+    const DLight light = lights[i];
+    if (light.kind != 0) {
+        l[0] = l[1] = l[2] = l[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float4 *q = triShade + (size_t)kTriShadeQuads * light.index;
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+    const LightRecord record = makeLightRecord(v3(q0.x, q0.y, q0.z), v3(q1.x, q1.y, q1.z), v3(q2.x, q2.y, q2.z), floatAsInt(q0.w), nLights);
+    l[0] = make_float4(record.p0.x, record.p0.y, record.p0.z, intAsFloat(record.material));
+    l[1] = make_float4(record.p1.x, record.p1.y, record.p1.z, record.area);
+    l[2] = make_float4(record.p2.x, record.p2.y, record.p2.z, record.invPDF);
+    l[3] = make_float4(record.normal.x, record.normal.y, record.normal.z, record.pdfArea);
+}
+
+// Test hook behind pathed_hip_debug_light_records: per triangle, what the per-vertex functions derive from the corners
+// (triangleSample, trianglePdfSolidAngle's own part, makeIsect's shading normal of a triangle without vertex normals, and
+// sampleLightsTerm's invPDF and 1 / invPDF for `lightCount` lights): 12 floats
+//   (sample normal xyz, area) (1 / area, invPDF, 1 / invPDF, -) (normalized(triangleNormal) xyz, -)
+__global__ __launch_bounds__(kBlock) void k_debug_per_vertex_constants(const float4 *triShade, int nTriangles, int lightCount, float4 *out)
+{
+    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (i >= nTriangles) { return; }
+    const float4 *q = triShade + (size_t)kTriShadeQuads * i;
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+    const V3 p0 = v3(q0.x, q0.y, q0.z), p1 = v3(q1.x, q1.y, q1.z), p2 = v3(q2.x, q2.y, q2.z);
+    Rng random;
+    random.k0 = 0; random.k1 = 0; random.dimension = 0;
+    const SurfaceSample surfaceSample = triangleSample(p0, p1, p2, random);
+    const float lightChoicePDF = 1.f / lightCount;
+    const float invPDF = surfaceSample.invPDF * (1.f / lightChoicePDF);
+    const float areaPDF = 1.f / triangleArea(p0, p1, p2);
+    const V3 shadingNormal = normalized(triangleNormal(p0, p1, p2));
+    out[3 * (size_t)i] = make_float4(surfaceSample.normal.x, surfaceSample.normal.y, surfaceSample.normal.z, surfaceSample.invPDF);
+    out[3 * (size_t)i + 1] = make_float4(areaPDF, invPDF, 1.f / invPDF, 0.f);
+    out[3 * (size_t)i + 2] = make_float4(shadingNormal.x, shadingNormal.y, shadingNormal.z, 0.f);
 }
 
 // ------------------------------------------------------------------------- refit

@@ -198,7 +198,7 @@ struct PathedScene {
     int bvhBuilder = PATHED_BVH_SAH_HOST;
     double bvhBuildMs = 0.0;
 
-    DeviceBuffer<float4> nodes, nodesQ, leafTris, triShade, triCompact, envRgba, texels;
+    DeviceBuffer<float4> nodes, nodesQ, leafTris, triShade, triCompact, lightRecords, envRgba, texels;
     DeviceBuffer<DSphere> spheres;
     float spherePairs[8][4][2] = {};   // RenderParams.spherePairs: the spheres two by two for the fused kernel's packed pre-test
     DeviceBuffer<DMaterial> materials;
@@ -1403,6 +1403,16 @@ static hipError_t buildHybrid(PathedScene *scene, const PathedSceneDesc *desc)
 }
 
 // Which compile-time scene sets (shading.h: SceneTraits) contain the scene.  generic_kernels = 1 leaves every flag off.
+// The light sampling records (device_scene.h) from the shading records in scene->triShade: at scene creation and after every
+// refit, behind k_build_tri_shade on the same stream.
+static hipError_t buildLightRecords(PathedScene *scene, int nLights)
+{
+    if (nLights <= 0) { return hipSuccess; }
+    hipLaunchKernelGGL(k_build_light_records, dim3((unsigned)((nLights + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                       scene->lights.ptr, nLights, scene->triShade.ptr, scene->lightRecords.ptr);
+    return hipGetLastError();
+}
+
 static SceneTraitFlags sceneTraits(const PathedSceneDesc *desc, const std::vector<DMaterial> &materials, const std::vector<DLight> &lights,
                                    const PathedSceneOptions &options)
 {
@@ -1675,7 +1685,7 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
         if (status == hipSuccess) { status = deviceIndices.allocate(3 * nt); }
         if (status == hipSuccess) { status = deviceTriMaterial.allocate(nt); }
         if (status == hipSuccess) { status = scene->triShade.allocate((size_t)kTriShadeQuads * nt); }
-        if (status == hipSuccess) { status = scene->triCompact.allocate(nt); }
+        if (status == hipSuccess) { status = scene->triCompact.allocate((size_t)kTriCompactQuads * nt); }
         if (status == hipSuccess) { status = hipMemcpy(devicePositions.ptr, desc->positions, 3 * nv * sizeof(float), hipMemcpyHostToDevice); }
         if (status == hipSuccess) { status = hipMemcpy(deviceNormals.ptr, desc->normals, 3 * nv * sizeof(float), hipMemcpyHostToDevice); }
         if (status == hipSuccess) { status = hipMemcpy(deviceUvs.ptr, desc->uvs, 2 * nv * sizeof(float), hipMemcpyHostToDevice); }
@@ -1752,6 +1762,8 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
     if ((status = scene->spheres.upload(spheres)) != hipSuccess) { return fail_cleanup(status, "upload spheres"); }
     if ((status = scene->materials.upload(materials)) != hipSuccess) { return fail_cleanup(status, "upload materials"); }
     if ((status = scene->lights.upload(lights)) != hipSuccess) { return fail_cleanup(status, "upload lights"); }
+    if ((status = scene->lightRecords.allocate((size_t)kLightRecordQuads * lights.size())) != hipSuccess) { return fail_cleanup(status, "allocate light records"); }
+    if ((status = buildLightRecords(scene, (int)lights.size())) != hipSuccess) { return fail_cleanup(status, "build light records"); }
     {
         // participating media and every primitive's internal medium (Surface::getInternalMedium), triangles then spheres
         std::vector<DMedium> media(desc->n_media);
@@ -1821,6 +1833,7 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
     d.materials = scene->materials.ptr;
     d.nMaterials = (int)desc->n_materials;
     d.lights = scene->lights.ptr;
+    d.lightRecords = scene->lightRecords.ptr;
     d.nLights = (int)lights.size();
     scene->traits = sceneTraits(desc, materials, lights, options);
     d.media = scene->media.ptr;
@@ -2744,6 +2757,44 @@ int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, siz
     return PATHED_OK;
 }
 
+int pathed_hip_debug_light_records(PathedScene *scene, float *triangles, size_t n_triangles, float *lights, size_t max_lights, int *n_lights)
+{
+    if (!scene || !triangles || !lights || !n_lights) { return fail(PATHED_E_INVALID, "null scene or output buffer"); }
+    SELECT_DEVICE(scene);
+    const size_t nTris = (size_t)scene->device.nTris, nLights = (size_t)scene->device.nLights;
+    if (n_triangles != nTris) { return fail(PATHED_E_INVALID, "n_triangles must be the scene's triangle count"); }
+    if (max_lights < nLights) { return fail(PATHED_E_INVALID, "the scene has more lights than the buffer holds"); }
+    *n_lights = (int)nLights;
+    if (nTris > 0) {
+        DeviceBuffer<float4> perVertex;
+        HIP_TRY(perVertex.allocate(3 * nTris));
+        hipLaunchKernelGGL(k_debug_per_vertex_constants, dim3((unsigned)((nTris + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                           scene->triShade.ptr, (int)nTris, (int)nLights, perVertex.ptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        std::vector<float4> constants(3 * nTris), shade((size_t)kTriShadeQuads * nTris), compact((size_t)kTriCompactQuads * nTris);
+        HIP_TRY(hipMemcpy(constants.data(), perVertex.ptr, constants.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(shade.data(), scene->triShade.ptr, shade.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(compact.data(), scene->triCompact.ptr, compact.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nTris; i++) {
+            float4 *row = reinterpret_cast<float4 *>(triangles) + 5 * i;
+            row[0] = constants[3 * i]; row[1] = constants[3 * i + 1]; row[2] = constants[3 * i + 2];
+            row[3] = shade[(size_t)kTriShadeQuads * i + 7];
+            row[4] = compact[(size_t)kTriCompactQuads * i + 1];
+        }
+    }
+    if (nLights > 0) {
+        std::vector<DLight> kinds(nLights);
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(kinds.data(), scene->lights.ptr, nLights * sizeof(DLight), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nLights; i++) { lights[18 * i] = (float)kinds[i].kind; lights[18 * i + 1] = (float)kinds[i].index; }
+        std::vector<float4> records((size_t)kLightRecordQuads * nLights);
+        HIP_TRY(hipMemcpy(records.data(), scene->lightRecords.ptr, records.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nLights; i++) { std::memcpy(lights + 18 * i + 2, &records[(size_t)kLightRecordQuads * i], 16 * sizeof(float)); }
+    }
+    return PATHED_OK;
+}
+
 int pathed_hip_scene_refit(PathedScene *scene, const float *positions, const float *normals, uint32_t n_vertices, float *device_ms)
 {
     if (!scene || !positions) { return fail(PATHED_E_INVALID, "null scene or positions"); }
@@ -2771,6 +2822,9 @@ int pathed_hip_scene_refit(PathedScene *scene, const float *positions, const flo
         hipLaunchKernelGGL(k_build_tri_shade, dim3((unsigned)((8 * nTris + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
                            scene->soupPositions.ptr, scene->soupNormals.ptr, scene->soupUvs.ptr, scene->soupIndices.ptr, scene->soupTriMaterial.ptr,
                            (uint32_t)nTris, scene->triShade.ptr, scene->triCompact.ptr);
+        status = buildLightRecords(scene, scene->device.nLights);   // an emitter that moved is sampled where it is now
+    }
+    if (status == hipSuccess) {
         status = hipMemsetAsync(scene->refitReady.ptr, 0, 2 * (size_t)nNodes, nullptr);
     }
     int passes = 0;

@@ -854,8 +854,11 @@ __device__ inline float triangleArea(V3 p0, V3 p1, V3 p2)
     return fabsf(length(cross(e1, e2)) / 2.f);
 }
 
-// src/triangle.cpp:16-38
-__device__ inline SurfaceSample triangleSample(V3 p0, V3 p1, V3 p2, Rng &random)
+// the normal of Triangle::sample and Triangle::pdf (src/triangle.cpp:33, :57): cross(), where the hit normal uses xcross()
+__device__ inline V3 triangleSampleNormal(V3 p0, V3 p1, V3 p2) { return normalized(cross(p1 - p0, p2 - p0)); }
+
+// src/triangle.cpp:16-38, the part that depends on the random numbers; normal and area are constants of the triangle
+__device__ inline SurfaceSample triangleSamplePoint(V3 p0, V3 p1, V3 p2, V3 normal, float area, Rng &random)
 {
     const float r1 = random.next();
     const float r2 = random.next();
@@ -866,10 +869,54 @@ __device__ inline SurfaceSample triangleSample(V3 p0, V3 p1, V3 p2, Rng &random)
 
     SurfaceSample sample;
     sample.point = p0 * a + p1 * b + p2 * c;
-    sample.normal = normalized(cross(p1 - p0, p2 - p0));
-    sample.invPDF = triangleArea(p0, p1, p2);
+    sample.normal = normal;
+    sample.invPDF = area;
     sample.solidAngle = 0;
     return sample;
+}
+
+// src/triangle.cpp:16-38 from the corners alone: what the light records (device_scene.h) are checked against
+__device__ inline SurfaceSample triangleSample(V3 p0, V3 p1, V3 p2, Rng &random)
+{
+    return triangleSamplePoint(p0, p1, p2, triangleSampleNormal(p0, p1, p2), triangleArea(p0, p1, p2), random);
+}
+
+// The per-light record (device_scene.h: kLightRecordQuads) as the sampling code reads it.
+struct LightRecord {
+    V3 p0, p1, p2, normal;
+    int material;
+    float area, invPDF, pdfArea;   // triangleArea; area * (1 / lightChoicePDF); 1 / invPDF
+};
+
+// Scene::sampleDirectLights' constants for one triangle light, src/scene.cpp:446-467 and include/scene.h:66-80: the
+// expressions of triangleSample and sampleLightsTerm on values that do not change from vertex to vertex.
+__device__ inline LightRecord makeLightRecord(V3 p0, V3 p1, V3 p2, int material, int lightCount)
+{
+    LightRecord record;
+    record.p0 = p0; record.p1 = p1; record.p2 = p2;
+    record.material = material;
+    record.normal = triangleSampleNormal(p0, p1, p2);
+    record.area = triangleArea(p0, p1, p2);
+    const float lightChoicePDF = 1.f / lightCount;
+    record.invPDF = record.area * (1.f / lightChoicePDF);
+    record.pdfArea = 1.f / record.invPDF;
+    return record;
+}
+
+__device__ inline LightRecord loadLightRecord(const float4 *records, int lightIndex)
+{
+    const float4 *l = records + (size_t)kLightRecordQuads * lightIndex;
+    const float4 l0 = l[0], l1 = l[1], l2 = l[2], l3 = l[3];
+    LightRecord record;
+    record.p0 = v3(l0.x, l0.y, l0.z);
+    record.p1 = v3(l1.x, l1.y, l1.z);
+    record.p2 = v3(l2.x, l2.y, l2.z);
+    record.normal = v3(l3.x, l3.y, l3.z);
+    record.material = floatAsInt(l0.w);
+    record.area = l1.w;
+    record.invPDF = l2.w;
+    record.pdfArea = l3.w;
+    return record;
 }
 
 // include/measure.h:13-28
@@ -887,7 +934,7 @@ __device__ inline float areaToSolidAngle(float areaPDF, V3 referencePoint, V3 su
 __device__ inline float trianglePdfSolidAngle(V3 p0, V3 p1, V3 p2, V3 point, V3 referencePoint)
 {
     const float areaPDF = 1.f / triangleArea(p0, p1, p2);
-    const V3 normal = normalized(cross(p1 - p0, p2 - p0));
+    const V3 normal = triangleSampleNormal(p0, p1, p2);
     return areaToSolidAngle(areaPDF, referencePoint, point, normal);
 }
 

@@ -149,6 +149,18 @@ class HipScene:
         _check(self._lib, code, "pathed_hip_debug_small_candidates")
         return out
 
+    def light_records(self, n_triangles, max_lights):
+        """The stored per-triangle and per-light constants beside what the per-vertex functions compute
+        (pathed_hip_debug_light_records): (n_triangles, 20) and (the scene's light count, 18) float32."""
+        triangles = np.zeros((n_triangles, 20), dtype=np.float32)
+        lights = np.zeros((max_lights, 18), dtype=np.float32)
+        count = C.c_int(0)
+        code = self._lib.pathed_hip_debug_light_records(
+            self._handle, triangles.ctypes.data_as(C.POINTER(C.c_float)), n_triangles,
+            lights.ctypes.data_as(C.POINTER(C.c_float)), max_lights, C.byref(count))
+        _check(self._lib, code, "pathed_hip_debug_light_records")
+        return triangles, lights[:count.value]
+
     def refit(self, positions, normals=None):
         """New vertex positions (and normals) over the same topology (pathed_hip_scene_refit; scenes created with refittable=1).
         Returns the device time of the refit kernels in milliseconds."""

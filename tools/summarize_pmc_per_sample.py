@@ -50,7 +50,7 @@ def kernel_class(kernel):
         return "trace"
     if "k_path" in kernel:
         return "path"
-    if "k_build_tri_shade" in kernel or "k_lbvh" in kernel or "k_ploc" in kernel:
+    if "k_build_tri_shade" in kernel or "k_build_light_records" in kernel or "k_lbvh" in kernel or "k_ploc" in kernel:
         return "setup"
     return "shade"
 
