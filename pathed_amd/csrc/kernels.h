@@ -1851,6 +1851,8 @@ struct MaterialAccess {
     __device__ inline const DMaterial &operator[](int index) const { return table[index]; }
 };
 
+#include "path_common.h"
+
 #ifndef PATHED_SHADE_TRIM
 // 1: a slot that regenerates skips the reset of mod / thr / pend (its camera ray's vertex reads none of them) and, with one
 // sample per unit, the `acc` stream: 80 bytes less per regenerated slot -- and SLOWER (teapot 1 731 against 1 762, the mesh
@@ -2726,76 +2728,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
         for (int i = threadIdx.x; i < kMfmaTableFloats; i += kBlock) { mfmaRows[i] = p.mfmaTable[i]; }
         if (!LDS_MATERIALS) { __syncthreads(); }
     }
-    MaterialAccess<LDS_MATERIALS> materials;
-    if (LDS_MATERIALS) {
-        const int words = p.scene.nMaterials * (int)(sizeof(DMaterial) / 4);
-        const int *source = reinterpret_cast<const int *>(p.scene.materials);
-        int *target = reinterpret_cast<int *>(ldsDynamic);
-        for (int i = threadIdx.x; i < words; i += kBlock) { target[i] = source[i]; }
-        __syncthreads();
-        materials.table = reinterpret_cast<const DMaterial *>(ldsDynamic);
-    } else {
-        materials.table = p.scene.materials;
-    }
-
-    TraceGeometry geometry;
-    geometry.nodes = nullptr;
-    geometry.tris = p.scene.leafTris;
-    geometry.nNodes = 0;
-    geometry.nTris = p.scene.nTris;
-    geometry.spheres = p.scene.spheres;
-    geometry.nSpheres = p.scene.nLinearSpheres;
+    const MaterialAccess<LDS_MATERIALS> materials = stageMaterials<LDS_MATERIALS>(p, ldsDynamic);
+    const TraceGeometry geometry = sceneGeometry(p.scene, false);
 
     const DScene &scene = p.scene;
     const int lane = threadIdx.x & 63;
     const unsigned int waveId = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int nTris = p.scene.nTris;
     const uint64_t seed = ((uint64_t)p.seedHi << 32) | p.seedLo;
-
-    // ---- work units: the wave reserves p.unitGrab consecutive units of a queue at a time (wave-uniform state)
-    unsigned int queue = waveId % (unsigned int)p.nQueues, queuesTried = 0;
-    unsigned int reservedNext = 0, reservedEnd = 0;
-    // hands a unit to every lane that wants one, in lane order; 0xFFFFFFFF once the pass is dealt out
-    auto takeUnits = [&](bool want) -> unsigned int {
-        unsigned int mine = 0xFFFFFFFFu;
-        unsigned long long wanting = __ballot(want);
-        while (wanting != 0ull) {
-            if (reservedNext == reservedEnd) {
-                if (queuesTried >= (unsigned int)p.nQueues) { break; }   // every queue is dealt out
-                unsigned int ticket = 0;
-                if (lane == 0) { ticket = atomicAdd(&p.counters[kCtrUnitCursor + queue * kCursorStride], (unsigned int)p.unitGrab); }
-                ticket = (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket);
-                const unsigned int limit = p.queueUnits[queue];   // unit ids of queue q: q * unitsPerQueue + [0, limit)
-                if (ticket >= limit) {
-                    queue = (queue + 1u) % (unsigned int)p.nQueues;
-                    queuesTried++;
-                    continue;
-                }
-                reservedNext = ticket;
-                reservedEnd = ticket + (unsigned int)p.unitGrab < limit ? ticket + (unsigned int)p.unitGrab : limit;
-            }
-            const unsigned int available = reservedEnd - reservedNext;
-            const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(wanting >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)wanting, 0u));
-            const bool served = ((wanting >> lane) & 1ull) != 0ull && rank < available;
-            if (served) { mine = queue * p.unitsPerQueue + reservedNext + rank; }
-            const unsigned int count = (unsigned int)__popcll(wanting);
-            reservedNext += count < available ? count : available;
-            wanting &= ~__ballot(served);
-        }
-        return mine;
-    };
+    UnitTaker units(p, waveId);
 
     // ---- the path a lane carries
     bool alive = false;
     unsigned int unit = 0xFFFFFFFFu;
     uint32_t pixel = 0, sample = 0, endSample = 0;   // sample: absolute index of the sample in flight
-    Rng random;
-    random.k0 = 0u; random.k1 = 0u; random.dimension = 0u;
-    V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f);
-    int st = 0;                      // device_scene.h state word: vertex that spawned the ray + eligible / delta / continue
-    int firstEmitMaterial = -1;
-    Rgb result = rgb(0.f), modulation = rgb(1.f), throughput = rgb(0.f), pend = rgb(0.f);
-    float bsdfPdf = 1.f, cosTheta = 0.f;
+    PathRegisters path = idlePath();
     float4 partial = make_float4(0.f, 0.f, 0.f, 0.f);
     bool pendingShadow = false;      // the vertex the ray left asked for an occlusion query along shadowDirection
     V3 shadowDirection = v3(0.f, 0.f, 1.f);
@@ -2803,38 +2750,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
 
     unsigned int closestRays = 0, shadowRays = 0, trisTested = 0;
 
-    // Camera::generateRay(int,int) for (pixel, sample), src/camera.cpp:49-55: one inlined copy, reached from the
-    // initial fill and from the end of every sample
+    // the camera ray: one inlined copy, reached from the initial fill and from the end of every sample
     bool startNext = false;
-    {
-        unit = takeUnits(true);
-        if (unit != 0xFFFFFFFFu) {
-            unitSamples(p, unit, &pixel, &sample, &endSample);
-            alive = true;
-            startNext = true;
-        }
-    }
+    firstUnits(p, units, lane, unit, pixel, sample, endSample, alive, startNext);
 
     while (true) {
         SHADE_REGION(0, alive);        // (profile builds, tools/fused_profile.py) iterations / live lanes
         SHADE_REGION(1, startNext);    // camera ray
         if (startNext) {
-            makeKey(seed, pixel, sample, &random.k0, &random.k1);
-            random.dimension = 0;
-            const int width = scene.camera.resX;
-            const int row = (int)fastDivide((unsigned int)pixel, p.divWidth);   // pixel / width, exactly
-            const int col = (int)pixel - row * width;
-            const float jitterX = random.next() - 0.5f;
-            const float jitterY = random.next() - 0.5f;
-            cameraRay(scene.camera, row + jitterY, col + jitterX, &o, &d);
-            st = 0;
-            firstEmitMaterial = -1;
-            result = rgb(0.f);
-            modulation = rgb(1.f);
-            throughput = rgb(0.f);
-            pend = rgb(0.f);
-            bsdfPdf = 1.f;
-            cosTheta = 0.f;
+            startCameraSample(p, seed, pixel, sample, path);
             startNext = false;
         }
         if (__ballot(alive) == 0ull) { break; }
@@ -2843,25 +2767,25 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
         // vertex it leaves (Scene::testOcclusion's rtcOccluded1): an occluded light sample contributes nothing
         if (QUADS) {
             float4 *stash = stashRows + threadIdx.x;
-            stash[0 * kBlock] = make_float4(result.r, result.g, result.b, bsdfPdf);
-            stash[1 * kBlock] = make_float4(modulation.r, modulation.g, modulation.b, cosTheta);
-            stash[2 * kBlock] = make_float4(throughput.r, throughput.g, throughput.b, intAsFloat(st));
+            stash[0 * kBlock] = make_float4(path.result.r, path.result.g, path.result.b, path.bsdfPdf);
+            stash[1 * kBlock] = make_float4(path.modulation.r, path.modulation.g, path.modulation.b, path.cosTheta);
+            stash[2 * kBlock] = make_float4(path.throughput.r, path.throughput.g, path.throughput.b, intAsFloat(path.st));
             stash[3 * kBlock] = partial;
             stash[4 * kBlock] = make_float4(intAsFloat((int)pixel), intAsFloat((int)sample), intAsFloat((int)endSample), intAsFloat((int)unit));
-            stash[5 * kBlock] = make_float4(intAsFloat((int)random.k0), intAsFloat((int)random.k1), intAsFloat(firstEmitMaterial), intAsFloat((int)random.dimension));
+            stash[5 * kBlock] = make_float4(intAsFloat((int)path.random.k0), intAsFloat((int)path.random.k1), intAsFloat(path.firstEmitMaterial), intAsFloat((int)path.random.dimension));
             asm volatile("" ::: "memory");   // the values below are re-read from LDS: the registers are free for the pass
         }
         LaneRay ray;
-        laneRayInit(ray, o, d, PATHED_TNEAR, PATHED_TFAR, false);
+        laneRayInit(ray, path.o, path.d, PATHED_TNEAR, PATHED_TFAR, false);
         {
             const bool traceShadow = alive && pendingShadow;
             LaneRay shadowRay;
-            laneRayInit(shadowRay, o, shadowDirection, PATHED_TNEAR, shadowTfar, true);
+            laneRayInit(shadowRay, path.o, shadowDirection, PATHED_TNEAR, shadowTfar, true);
             unsigned int candidatesLow = 0, candidatesHigh = 0, shadowLow = 0, shadowHigh = 0;
             SHADE_REGION(2, traceShadow);   // passes that carry shadow rays / lanes with one
             if (MFMA) {
                 // every lane takes part (the matrix instructions are the wave's); words: even / odd triangles
-                mfmaCandidatesPair(mfmaRows, nTris, p.mfmaFrame, __ballot(traceShadow) != 0ull, o, d, shadowDirection,
+                mfmaCandidatesPair(mfmaRows, nTris, p.mfmaFrame, __ballot(traceShadow) != 0ull, path.o, path.d, shadowDirection,
                                    candidateNear(PATHED_TNEAR), candidateFar(shadowTfar), &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh);
                 if (!alive) { candidatesLow = 0u; candidatesHigh = 0u; }
                 if (!traceShadow) { shadowLow = 0u; shadowHigh = 0u; }
@@ -2869,19 +2793,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                 // one instantiation of the pass: a wave without a single shadow ray is rare (3 % of the passes) and pays for
                 // the second ray's arithmetic rather than for a second copy of the loop's registers
                 if (alive) {
-                    smallCandidatesItems<true, true, true>(smallTris.data, p.smallQuads, nTris, p.smallKappaT, o, d, shadowDirection,
+                    smallCandidatesItems<true, true, true>(smallTris.data, p.smallQuads, nTris, p.smallKappaT, path.o, path.d, shadowDirection,
                                                             &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh,
                                                             candidateNear(PATHED_TNEAR), candidateFar(shadowTfar));
                     if (!traceShadow) { shadowLow = 0u; shadowHigh = 0u; }
                 }
             } else if (__ballot(traceShadow) != 0ull) {
                 if (alive) {
-                    smallCandidatesPair(smallTris.data, nTris, o, d, shadowDirection, &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh,
+                    smallCandidatesPair(smallTris.data, nTris, path.o, path.d, shadowDirection, &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh,
                                         candidateNear(PATHED_TNEAR), candidateFar(shadowTfar));
                     if (!traceShadow) { shadowLow = 0u; shadowHigh = 0u; }
                 }
             } else if (alive) {
-                smallCandidates(smallTris.data, nTris, o, d, &candidatesLow, &candidatesHigh, candidateNear(PATHED_TNEAR));
+                smallCandidates(smallTris.data, nTris, path.o, path.d, &candidatesLow, &candidatesHigh, candidateNear(PATHED_TNEAR));
             }
             if (COUNT && alive) {
                 trisTested += (unsigned int)nTris * (traceShadow ? 2u : 1u);
@@ -2902,7 +2826,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                 // spheres (the Veach scene's lights): a packed line-misses-sphere test for both rays, the exact tests on the shared list
                 unsigned int sphereCandidates = 0u, shadowSphereCandidates = 0u;
                 if (TRAITS::spheres && geometry.nSpheres > 0 && alive) {
-                    smallSphereCandidates(p, geometry.nSpheres, o, d, shadowDirection, &sphereCandidates, &shadowSphereCandidates);
+                    smallSphereCandidates(p, geometry.nSpheres, path.o, path.d, shadowDirection, &sphereCandidates, &shadowSphereCandidates);
                     if (!traceShadow) { shadowSphereCandidates = 0u; }
                 }
                 spheresDone = smallResolveShared<kResolveCapacity, PATHED_RESOLVE_SHARED != 2, TRAITS::spheres>(
@@ -2914,7 +2838,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
             if (alive && !spheresDone) { finishRay(geometry, ray); }
             if (traceShadow) {
                 if (!spheresDone) { finishRay(geometry, shadowRay); }
-                if (shadowRay.occluded) { pend = rgb(0.f); }
+                if (shadowRay.occluded) { path.pend = rgb(0.f); }
             }
             pendingShadow = false;
         }
@@ -2922,182 +2846,31 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
             asm volatile("" ::: "memory");
             const float4 *stash = stashRows + threadIdx.x;
             const float4 s0 = stash[0 * kBlock], s1 = stash[1 * kBlock], s2 = stash[2 * kBlock], s4 = stash[4 * kBlock], s5 = stash[5 * kBlock];
-            result = rgb(0.f); result.r = s0.x; result.g = s0.y; result.b = s0.z; bsdfPdf = s0.w;
-            modulation.r = s1.x; modulation.g = s1.y; modulation.b = s1.z; cosTheta = s1.w;
-            throughput.r = s2.x; throughput.g = s2.y; throughput.b = s2.z; st = floatAsInt(s2.w);
+            path.result = rgb(0.f); path.result.r = s0.x; path.result.g = s0.y; path.result.b = s0.z; path.bsdfPdf = s0.w;
+            path.modulation.r = s1.x; path.modulation.g = s1.y; path.modulation.b = s1.z; path.cosTheta = s1.w;
+            path.throughput.r = s2.x; path.throughput.g = s2.y; path.throughput.b = s2.z; path.st = floatAsInt(s2.w);
             partial = stash[3 * kBlock];
             pixel = (uint32_t)floatAsInt(s4.x); sample = (uint32_t)floatAsInt(s4.y); endSample = (uint32_t)floatAsInt(s4.z); unit = (unsigned int)floatAsInt(s4.w);
-            random.k0 = (uint32_t)floatAsInt(s5.x); random.k1 = (uint32_t)floatAsInt(s5.y); firstEmitMaterial = floatAsInt(s5.z); random.dimension = (uint32_t)floatAsInt(s5.w);
+            path.random.k0 = (uint32_t)floatAsInt(s5.x); path.random.k1 = (uint32_t)floatAsInt(s5.y); path.firstEmitMaterial = floatAsInt(s5.z); path.random.dimension = (uint32_t)floatAsInt(s5.w);
         }
-        const bool miss = ray.bestPrim < 0;
         const float4 h = make_float4(ray.best, ray.bestU, ray.bestV, intAsFloat(ray.bestPrim));
 
-        // ---- the vertex: k_shade's body on register state
-        ShadowRequest shadow;
-        shadow.push = false;
-        shadow.origin = v3(0.f, 0.f, 0.f);
-        shadow.direction = v3(0.f, 0.f, 1.f);
-        shadow.tfar = 0.f;
+        // ---- the vertex
         bool finished = false;
         Rgb color = rgb(0.f);
         if (alive) {
-            const int rayBounce = st & kStBounceMask;  // vertex that spawned this ray, 0 = camera
-            bool haveVertex = false;
-            Isect isect;
-            const int vertex = rayBounce + 1;
-            SHADE_REGION(3, !miss);        // makeIsect
-            if (!miss) { isect = makeIsect<TRAITS>(scene, o, d, h); }
-
-            SHADE_REGION(4, rayBounce == 0);   // camera-ray vertex
-            if (rayBounce == 0) {
-                // SampleIntegrator::samplePixel, src/sample_integrator.cpp:18-59
-                if (miss) {
-                    color = rgb(0.f) + environmentL<TRAITS>(scene, d);
-                    finished = true;
-                } else {
-                    firstEmitMaterial = -1;
-                    if (checkCounts(p.startBounce, p.lastBounce, 0)) {
-                        const Rgb emit = matEmit(materials[isect.material]);
-                        const bool backside = dot(isect.normal, isect.wo) < 0.f;
-                        if (!isBlack(emit) && !backside) { firstEmitMaterial = isect.material; }
-                    }
-                    result = rgb(0.f);
-                    haveVertex = true;
-                }
-            } else {
-                // the ray left vertex `rayBounce` along its BSDF sample
-                if (st & kStEligible) {
-                    // PathTracer::directSampleBSDF, src/path_tracer.cpp:167-216
-                    Rgb bsdfTerm = rgb(0.f);
-                    if (!miss) {
-                        const Rgb emit = matEmit(materials[isect.material]);
-                        SHADE_REGION(5, !isBlack(emit) && dot(isect.wo, isect.shadingNormal) >= 0.f);   // BSDF sample met an emitter: lightsPDF
-                        if (!isBlack(emit) && dot(isect.wo, isect.shadingNormal) >= 0.f) {
-                            const float lightPDF = lightsPDF<TRAITS>(scene, o, isect);
-                            const float brdfWeight = (st & kStDelta)
-                                ? 1.f
-                                : (1 * bsdfPdf) / (1 * bsdfPdf + 1 * lightPDF);
-                            bsdfTerm = emit * brdfWeight * throughput * cosTheta / bsdfPdf;
-                        }
-                    } else {
-                        const Rgb environmentLight = environmentL<TRAITS>(scene, d);
-                        if (TRAITS::env && !isBlack(environmentLight)) {
-                            // Scene::environmentPDF, src/scene.cpp:494-502
-                            const float lightPDF = envEmitPDF(scene.env, d) / scene.nLights;
-                            const float brdfWeight = (st & kStDelta)
-                                ? 1.f
-                                : (1 * bsdfPdf) / (1 * bsdfPdf + 1 * lightPDF);
-                            bsdfTerm = environmentLight * brdfWeight * throughput * cosTheta / bsdfPdf;
-                        }
-                    }
-                    const Rgb Ld = pend + bsdfTerm;
-                    if (rayBounce == 1) { result = Ld; }
-                    else { result = result + Ld * modulation; }
-                }
-
-                // PathTracer::L loop body, src/path_tracer.cpp:41-58
-                if (!(st & kStContinue) || miss) {
-                    finished = true;
-                } else {
-                    const float invPDF = 1.f / bsdfPdf;
-                    modulation = modulation * (throughput * cosTheta * invPDF);
-                    if (isBlack(modulation)) { finished = true; }
-                    else { haveVertex = true; }
-                }
-                if (finished) {
-                    Rgb first = rgb(0.f);
-                    if (firstEmitMaterial >= 0) { first = first + matEmit(materials[firstEmitMaterial]); }
-                    color = first + result;
-                }
-            }
-
-            SHADE_REGION(6, haveVertex);   // new vertex: BSDF sample
-            if (haveVertex) {
-                // PathTracer::L: sample the BSDF, then direct(), src/path_tracer.cpp:30-36, 60-73
-                const DMaterial &material = materials[isect.material];
-                prepareLobes<TRAITS>(material, isect);
-
-                random.dimension = vertexBase(vertex);
-                const BSDFSample bsdfSample = materialSample<TRAITS>(material, isect, random);
-
-                const bool counts = checkCounts(p.startBounce, p.lastBounce, vertex);
-                const bool emissive = !isBlack(matEmit(material));
-                const bool wantDirect = counts && !emissive;  // direct() returns 0 on emitters (:86-90)
-                const bool wantContinue = !checkDone(p.lastBounce, vertex + 1);
-
-                Rgb lightTerm = rgb(0.f);
-                SHADE_REGION(7, wantDirect);   // light sampling
-                if (wantDirect) {
-                    random.dimension = vertexBase(vertex) + 3;
-                    lightTerm = sampleLightsTerm<false, TRAITS>(scene, materials, isect, material, random, &shadow);
-                }
-
-                // see k_shade: a vertex with nothing pending whose BSDF sample has exactly black throughput ends the sample
-                const bool deadEnd = isBlack(bsdfSample.throughput) && bsdfSample.pdf > 0.f && bsdfSample.pdf < 3e38f
-                    && !shadow.push && isBlack(lightTerm);
-                if ((!wantDirect && !wantContinue) || deadEnd) {
-                    finished = true;
-                    Rgb first = rgb(0.f);
-                    if (firstEmitMaterial >= 0) { first = first + matEmit(materials[firstEmitMaterial]); }
-                    color = first + result;
-                    shadow.push = false;
-                } else {
-                    int nextState = vertex;
-                    if (wantDirect) { nextState |= kStEligible; }
-                    if (isDeltaT<TRAITS>(material)) { nextState |= kStDelta; }
-                    if (wantContinue) { nextState |= kStContinue; }
-                    st = nextState;
-                    o = isect.point;
-                    d = bsdfSample.wiWorld;
-                    bsdfPdf = bsdfSample.pdf;
-                    throughput = bsdfSample.throughput;
-                    cosTheta = fabsf(dot(isect.shadingNormal, bsdfSample.wiWorld));
-                    pend = lightTerm;
-                }
+            ShadowRequest shadow;
+            finished = pathVertex<TRAITS, true>(p, scene, materials, path, h, &shadow, &color);
+            // the vertex's shadow ray leaves isect.point like the continuation ray: both are traced in the next pass
+            if (shadow.push) {
+                pendingShadow = true;
+                shadowDirection = shadow.direction;
+                shadowTfar = shadow.tfar;
             }
         }
 
-        // the vertex's shadow ray leaves isect.point like the continuation ray: both are traced in the next pass
-        if (alive && shadow.push) {
-            pendingShadow = true;
-            shadowDirection = shadow.direction;
-            shadowTfar = shadow.tfar;
-        }
-
-        // ---- end of a sample: radianceLookup += color (src/sample_integrator.cpp:61-63; non-finite samples
-        // dropped), then the unit's next sample or the next unit
-        bool needUnit = false;
         SHADE_REGION(8, alive && finished);   // sample finished
-        if (alive && finished) {
-            const bool finite = isfinite(color.r) && isfinite(color.g) && isfinite(color.b);
-            if (finite) {
-                partial.x += color.r;
-                partial.y += color.g;
-                partial.z += color.b;
-            } else {
-                atomicAdd(&p.stats[kStatDropped], 1ull);
-            }
-            sample++;
-            if (sample < endSample) {
-                startNext = true;
-            } else {
-                p.state.chunkBuf[partialIndex(p, unit)] = partial;
-                partial = make_float4(0.f, 0.f, 0.f, 0.f);
-                needUnit = true;
-            }
-        }
-        if (__ballot(needUnit) != 0ull) {
-            const unsigned int newUnit = takeUnits(needUnit);
-            if (needUnit) {
-                unit = newUnit;
-                if (newUnit != 0xFFFFFFFFu) {
-                    unitSamples(p, newUnit, &pixel, &sample, &endSample);
-                    startNext = true;
-                } else {
-                    alive = false;
-                }
-            }
-        }
+        finishSample(p, units, lane, alive && finished, color, partial, unit, pixel, sample, endSample, alive, startNext);
     }
 
     if (COUNT) {
@@ -3281,7 +3054,7 @@ __device__ __forceinline__ void volumeQueryPairSmall(const VolumeContext<Materia
 }
 
 // k_path_volume: SampleIntegrator::samplePixel + VolumePathTracer::L (see volume.h), one path per lane, persistent waves,
-// work units as in k_path_small.  Arithmetic on a path's values follows the reference statement by statement; on a
+// work units from UnitTaker (path_common.h).  Arithmetic on a path's values follows the reference statement by statement; on a
 // scene without media the result is PathTracer's, bit for bit (the two share their direct-lighting arithmetic; GPU test).
 #ifndef PATHED_VOLUME_WAVES
 #define PATHED_VOLUME_WAVES 4   // 128 registers per lane + scratch; 3 / 4 / 5 waves: 787 / 845 / 799 (Cornell), 732 / 787 / 707 (cornell-medium), 368 / 388 / 382 (teapot) Msamples/s; uncapped the kernel takes 220-260 registers and runs one or two waves; with one pass per vertex (round 3) 3 / 4 waves: 1 139 / 1 225 (Cornell), 901 / 985 (cornell-medium)
@@ -3291,27 +3064,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
 {
     extern __shared__ float4 ldsRaw[];
     // LDS: [STACK + 1][kBlock] traversal stack rows, then (LDS_MATERIALS) the material table
-    MaterialAccess<LDS_MATERIALS> materials;
-    if (LDS_MATERIALS) {
-        float4 *table = ldsRaw + ((STACK + 1) * kBlock) / 4;
-        const int words = p.scene.nMaterials * (int)(sizeof(DMaterial) / 4);
-        const int *source = reinterpret_cast<const int *>(p.scene.materials);
-        int *target = reinterpret_cast<int *>(table);
-        for (int i = threadIdx.x; i < words; i += kBlock) { target[i] = source[i]; }
-        materials.table = reinterpret_cast<const DMaterial *>(table);
-    } else {
-        materials.table = p.scene.materials;
-    }
-    if (LDS_MATERIALS) { __syncthreads(); }
+    const MaterialAccess<LDS_MATERIALS> materials = stageMaterials<LDS_MATERIALS>(p, ldsRaw + ((STACK + 1) * kBlock) / 4);
 
     const DScene &scene = p.scene;
     VolumeContext<MaterialAccess<LDS_MATERIALS>> context;
-    context.geometry.nodes = scene.nodes;
-    context.geometry.tris = scene.leafTris;
-    context.geometry.nNodes = scene.nNodes;
-    context.geometry.nTris = scene.nTris;
-    context.geometry.spheres = scene.spheres;
-    context.geometry.nSpheres = scene.nLinearSpheres;
+    context.geometry = sceneGeometry(scene, true);
     context.stack.lds = reinterpret_cast<int *>(ldsRaw) + threadIdx.x;
     context.stack.overflowStride = (size_t)gridDim.x * kBlock;
     context.stack.overflow = p.stackOverflow + ((size_t)blockIdx.x * kBlock + threadIdx.x);
@@ -3325,37 +3082,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
     const unsigned int waveId = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const uint64_t seed = ((uint64_t)p.seedHi << 32) | p.seedLo;
 
-    // ---- work units, as in k_path_small
-    unsigned int queue = waveId % (unsigned int)p.nQueues, queuesTried = 0;
-    unsigned int reservedNext = 0, reservedEnd = 0;
-    auto takeUnits = [&](bool want) -> unsigned int {
-        unsigned int mine = 0xFFFFFFFFu;
-        unsigned long long wanting = __ballot(want);
-        while (wanting != 0ull) {
-            if (reservedNext == reservedEnd) {
-                if (queuesTried >= (unsigned int)p.nQueues) { break; }
-                unsigned int ticket = 0;
-                if (lane == 0) { ticket = atomicAdd(&p.counters[kCtrUnitCursor + queue * kCursorStride], (unsigned int)p.unitGrab); }
-                ticket = (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket);
-                const unsigned int limit = p.queueUnits[queue];
-                if (ticket >= limit) {
-                    queue = (queue + 1u) % (unsigned int)p.nQueues;
-                    queuesTried++;
-                    continue;
-                }
-                reservedNext = ticket;
-                reservedEnd = ticket + (unsigned int)p.unitGrab < limit ? ticket + (unsigned int)p.unitGrab : limit;
-            }
-            const unsigned int available = reservedEnd - reservedNext;
-            const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(wanting >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)wanting, 0u));
-            const bool served = ((wanting >> lane) & 1ull) != 0ull && rank < available;
-            if (served) { mine = queue * p.unitsPerQueue + reservedNext + rank; }
-            const unsigned int count = (unsigned int)__popcll(wanting);
-            reservedNext += count < available ? count : available;
-            wanting &= ~__ballot(served);
-        }
-        return mine;
-    };
+    UnitTaker units(p, waveId);   // work units as in the other path kernels (path_common.h)
 
     // one ray query: the all-triangles intersector (SMALL) or the per-lane walk of the 4-wide tree
     auto query = [&](int mode, V3 origin, V3 direction, float tfar, RayHit *hit, VolumeEvents *events) -> bool {
@@ -3589,15 +3316,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
     auto samplePixel = [&](uint32_t pixel, uint32_t sample) -> Rgb {
         segmentKnown = false;
         Rng random;
-        makeKey(seed, pixel, sample, &random.k0, &random.k1);
-        random.dimension = 0;
-        const int width = scene.camera.resX;
-        const int row = (int)fastDivide((unsigned int)pixel, p.divWidth);   // pixel / width, exactly
-        const int col = (int)pixel - row * width;
-        const float jitterX = random.next() - 0.5f;
-        const float jitterY = random.next() - 0.5f;
         V3 rayOrigin, rayDirection;
-        cameraRay(scene.camera, row + jitterY, col + jitterX, &rayOrigin, &rayDirection);
+        cameraSampleRay(p, seed, pixel, sample, random, &rayOrigin, &rayDirection);
 
         Rgb color = rgb(0.f);
         RayHit hit;
@@ -3678,7 +3398,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
 
     unsigned long long samplesDone = 0;
     while (true) {
-        const unsigned int unit = takeUnits(true);
+        const unsigned int unit = units.take(p, lane, true);
         if (__ballot(unit != 0xFFFFFFFFu) == 0ull) { break; }
         if (unit != 0xFFFFFFFFu) {
             uint32_t pixel, first, end;

@@ -18,8 +18,8 @@
 //     next pass out, and the next burst carries them on (k_path_wave's rule, path_wave.h).
 // Hits are the full-tree walk's bit for bit: every triangle is tested by intersectTriangle with the ray's own (o, d), the
 // acceptance rule is "smallest t, then smallest primitive id" whatever the order candidates arrive in, and the two parts are
-// merged by that rule; an occlusion query is the OR of the parts.  The vertex code is pathVertex (path_wave.h), the unit
-// decomposition k_path_small's: images are the wavefront kernels' bit for bit (tests/test_gpu_hybrid.py).
+// merged by that rule; an occlusion query is the OR of the parts.  The vertex code is pathVertex, the unit
+// decomposition UnitTaker's (path_common.h): images are the wavefront kernels' bit for bit (tests/test_gpu_hybrid.py).
 //
 // Replaces rtcIntersect1 / rtcOccluded1 (reference src/scene.cpp:113, :374) under PathTracer::L (src/path_tracer.cpp:19-216).
 // Included by kernels.h inside namespace pathed.
@@ -57,15 +57,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_H
     __shared__ float4 stashRows[kHybridStashRows * kBlock];
     __shared__ unsigned int waveWords[kWavesPerBlock * kHybridWaveWords];
 
-    MaterialAccess<true> materials;
-    {
-        const int words = p.scene.nMaterials * (int)(sizeof(DMaterial) / 4);
-        const int *source = reinterpret_cast<const int *>(p.scene.materials);
-        int *target = reinterpret_cast<int *>(ldsDynamic);
-        for (int i = threadIdx.x; i < words; i += kBlock) { target[i] = source[i]; }
-        __syncthreads();
-        materials.table = reinterpret_cast<const DMaterial *>(ldsDynamic);
-    }
+    const MaterialAccess<true> materials = stageMaterials<true>(p, ldsDynamic);
 
     const DScene &scene = p.scene;
     const int lane = threadIdx.x & 63;
@@ -106,49 +98,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_H
     scratch.occluded = scratchWords + 128 + 2 * kHybridResolveItems + kHybridResolveItems / 2;             // 64 words
     scratch.count = scratch.occluded + 64;
 
-    // ---- work units: as k_path_small
-    unsigned int queue = waveId % (unsigned int)p.nQueues, queuesTried = 0;
-    unsigned int reservedNext = 0, reservedEnd = 0;
-    auto takeUnits = [&](bool want) -> unsigned int {
-        unsigned int taken = 0xFFFFFFFFu;
-        unsigned long long wanting = __ballot(want);
-        while (wanting != 0ull) {
-            if (reservedNext == reservedEnd) {
-                if (queuesTried >= (unsigned int)p.nQueues) { break; }   // every queue is dealt out
-                unsigned int ticket = 0;
-                if (lane == 0) { ticket = atomicAdd(&p.counters[kCtrUnitCursor + queue * kCursorStride], (unsigned int)p.unitGrab); }
-                ticket = (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket);
-                const unsigned int limit = p.queueUnits[queue];
-                if (ticket >= limit) {
-                    queue = (queue + 1u) % (unsigned int)p.nQueues;
-                    queuesTried++;
-                    continue;
-                }
-                reservedNext = ticket;
-                reservedEnd = ticket + (unsigned int)p.unitGrab < limit ? ticket + (unsigned int)p.unitGrab : limit;
-            }
-            const unsigned int available = reservedEnd - reservedNext;
-            const unsigned int rank = laneRank(wanting);
-            const bool served = ((wanting >> lane) & 1ull) != 0ull && rank < available;
-            if (served) { taken = queue * p.unitsPerQueue + reservedNext + rank; }
-            const unsigned int count = (unsigned int)__popcll(wanting);
-            reservedNext += count < available ? count : available;
-            wanting &= ~__ballot(served);
-        }
-        return taken;
-    };
+    UnitTaker units(p, waveId);
 
     // ---- the path a lane carries
     bool alive = false;
     unsigned int unit = 0xFFFFFFFFu;
     uint32_t pixel = 0, sample = 0, endSample = 0;
-    PathRegisters path;
-    path.random.k0 = 0u; path.random.k1 = 0u; path.random.dimension = 0u;
-    path.o = v3(0.f, 0.f, 0.f); path.d = v3(0.f, 0.f, 1.f);
-    path.st = 0;
-    path.firstEmitMaterial = -1;
-    path.result = rgb(0.f); path.modulation = rgb(1.f); path.throughput = rgb(0.f); path.pend = rgb(0.f);
-    path.bsdfPdf = 1.f; path.cosTheta = 0.f;
+    PathRegisters path = idlePath();
     float4 partial = make_float4(0.f, 0.f, 0.f, 0.f);
     bool pendingShadow = false;
     V3 shadowDirection = v3(0.f, 0.f, 1.f);
@@ -169,33 +125,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_H
     unsigned long long profShaded = 0, profLeft = 0;
 #endif
     bool startNext = false;
-    {
-        unit = takeUnits(true);
-        if (unit != 0xFFFFFFFFu) {
-            unitSamples(p, unit, &pixel, &sample, &endSample);
-            alive = true;
-            startNext = true;
-        }
-    }
+    firstUnits(p, units, lane, unit, pixel, sample, endSample, alive, startNext);
 
     while (true) {
         if (startNext) {
-            makeKey(seed, pixel, sample, &path.random.k0, &path.random.k1);
-            path.random.dimension = 0;
-            const int width = scene.camera.resX;
-            const int row = (int)fastDivide((unsigned int)pixel, p.divWidth);
-            const int col = (int)pixel - row * width;
-            const float jitterX = path.random.next() - 0.5f;
-            const float jitterY = path.random.next() - 0.5f;
-            cameraRay(scene.camera, row + jitterY, col + jitterX, &path.o, &path.d);
-            path.st = 0;
-            path.firstEmitMaterial = -1;
-            path.result = rgb(0.f);
-            path.modulation = rgb(1.f);
-            path.throughput = rgb(0.f);
-            path.pend = rgb(0.f);
-            path.bsdfPdf = 1.f;
-            path.cosTheta = 0.f;
+            startCameraSample(p, seed, pixel, sample, path);
             startNext = false;
             pendingShadow = false;
         }
@@ -421,7 +355,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_H
             makeKey(seed, pixel, sample, &path.random.k0, &path.random.k1);
         }
 
-        // ---- the vertex (path_wave.h: pathVertex = k_path_small's vertex code)
+        // ---- the vertex (path_common.h)
         bool finished = false;
         Rgb color = rgb(0.f);
         if (shade) {
@@ -434,38 +368,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_H
             }
         }
 
-        // ---- end of a sample (k_path_small)
-        bool needUnit = false;
-        if (shade && finished) {
-            const bool finite = isfinite(color.r) && isfinite(color.g) && isfinite(color.b);
-            if (finite) {
-                partial.x += color.r;
-                partial.y += color.g;
-                partial.z += color.b;
-            } else {
-                atomicAdd(&p.stats[kStatDropped], 1ull);
-            }
-            sample++;
-            if (sample < endSample) {
-                startNext = true;
-            } else {
-                p.state.chunkBuf[partialIndex(p, unit)] = partial;
-                partial = make_float4(0.f, 0.f, 0.f, 0.f);
-                needUnit = true;
-            }
-        }
-        if (__ballot(needUnit) != 0ull) {
-            const unsigned int newUnit = takeUnits(needUnit);
-            if (needUnit) {
-                unit = newUnit;
-                if (newUnit != 0xFFFFFFFFu) {
-                    unitSamples(p, newUnit, &pixel, &sample, &endSample);
-                    startNext = true;
-                } else {
-                    alive = false;
-                }
-            }
-        }
+        finishSample(p, units, lane, shade && finished, color, partial, unit, pixel, sample, endSample, alive, startNext);
 #ifdef PATHED_SHADE_PROFILE
         profShadeCycles += __builtin_amdgcn_s_memtime() - profStamp;
 #endif

@@ -9,150 +9,11 @@
 // still in flight the burst ends: those rays stay on their lanes (registers + the lane's stack rows) across the shade
 // burst, the paths that wait for them sit it out, and the next burst carries them on together with the new rays.
 //
-// Every operation on a path's values is k_shade's, in k_shade's order (pathVertex below is k_path_small's vertex code), the
+// Every operation on a path's values is k_shade's, in k_shade's order (pathVertex, path_common.h: the vertex code of all the path kernels), the
 // traversal is k_trace's (trace.h), and the unit decomposition fixes the summation order: images are the wavefront
 // kernels' bit for bit.
 //
 // Included by kernels.h inside namespace pathed.
-
-struct PathRegisters {
-    V3 o, d;                         // the ray in flight (the one whose hit the next vertex shades)
-    int st;                          // device_scene.h state word: vertex that spawned the ray + eligible / delta / continue
-    int firstEmitMaterial;
-    Rgb result, modulation, throughput, pend;
-    float bsdfPdf, cosTheta;
-    Rng random;
-};
-
-// One vertex of one path: SampleIntegrator::samplePixel / PathTracer::L on register state -- the code of k_path_small's loop
-// body between "the vertex" and "end of a sample" (kernels.h), as a function.  `h` is the hit of the ray (path.o, path.d).
-// Returns true when the sample is finished (*color is its value); otherwise path.o / path.d hold the next ray and *shadow
-// the vertex's occlusion query, if any.
-template <typename TRAITS, typename MATERIALS>
-__device__ __forceinline__ bool pathVertex(const RenderParams &p, const DScene &scene, const MATERIALS &materials, PathRegisters &path,
-                                           float4 h, ShadowRequest *shadowOut, Rgb *color)
-{
-    ShadowRequest shadow;
-    shadow.push = false;
-    shadow.origin = v3(0.f, 0.f, 0.f);
-    shadow.direction = v3(0.f, 0.f, 1.f);
-    shadow.tfar = 0.f;
-    bool finished = false;
-    *color = rgb(0.f);
-    const bool miss = floatAsInt(h.w) < 0;
-    const int st = path.st;
-    const int rayBounce = st & kStBounceMask;  // vertex that spawned this ray, 0 = camera
-    bool haveVertex = false;
-    Isect isect;
-    const int vertex = rayBounce + 1;
-    if (!miss) { isect = makeIsect<TRAITS>(scene, path.o, path.d, h); }
-
-    if (rayBounce == 0) {
-        // SampleIntegrator::samplePixel, src/sample_integrator.cpp:18-59
-        if (miss) {
-            *color = rgb(0.f) + environmentL<TRAITS>(scene, path.d);
-            finished = true;
-        } else {
-            path.firstEmitMaterial = -1;
-            if (checkCounts(p.startBounce, p.lastBounce, 0)) {
-                const Rgb emit = matEmit(materials[isect.material]);
-                const bool backside = dot(isect.normal, isect.wo) < 0.f;
-                if (!isBlack(emit) && !backside) { path.firstEmitMaterial = isect.material; }
-            }
-            path.result = rgb(0.f);
-            haveVertex = true;
-        }
-    } else {
-        // the ray left vertex `rayBounce` along its BSDF sample
-        if (st & kStEligible) {
-            // PathTracer::directSampleBSDF, src/path_tracer.cpp:167-216
-            Rgb bsdfTerm = rgb(0.f);
-            if (!miss) {
-                const Rgb emit = matEmit(materials[isect.material]);
-                if (!isBlack(emit) && dot(isect.wo, isect.shadingNormal) >= 0.f) {
-                    const float lightPDF = lightsPDF<TRAITS>(scene, path.o, isect);
-                    const float brdfWeight = (st & kStDelta)
-                        ? 1.f
-                        : (1 * path.bsdfPdf) / (1 * path.bsdfPdf + 1 * lightPDF);
-                    bsdfTerm = emit * brdfWeight * path.throughput * path.cosTheta / path.bsdfPdf;
-                }
-            } else {
-                const Rgb environmentLight = environmentL<TRAITS>(scene, path.d);
-                if (TRAITS::env && !isBlack(environmentLight)) {
-                    // Scene::environmentPDF, src/scene.cpp:494-502
-                    const float lightPDF = envEmitPDF(scene.env, path.d) / scene.nLights;
-                    const float brdfWeight = (st & kStDelta)
-                        ? 1.f
-                        : (1 * path.bsdfPdf) / (1 * path.bsdfPdf + 1 * lightPDF);
-                    bsdfTerm = environmentLight * brdfWeight * path.throughput * path.cosTheta / path.bsdfPdf;
-                }
-            }
-            const Rgb Ld = path.pend + bsdfTerm;
-            if (rayBounce == 1) { path.result = Ld; }
-            else { path.result = path.result + Ld * path.modulation; }
-        }
-
-        // PathTracer::L loop body, src/path_tracer.cpp:41-58
-        if (!(st & kStContinue) || miss) {
-            finished = true;
-        } else {
-            const float invPDF = 1.f / path.bsdfPdf;
-            path.modulation = path.modulation * (path.throughput * path.cosTheta * invPDF);
-            if (isBlack(path.modulation)) { finished = true; }
-            else { haveVertex = true; }
-        }
-        if (finished) {
-            Rgb first = rgb(0.f);
-            if (path.firstEmitMaterial >= 0) { first = first + matEmit(materials[path.firstEmitMaterial]); }
-            *color = first + path.result;
-        }
-    }
-
-    if (haveVertex) {
-        // PathTracer::L: sample the BSDF, then direct(), src/path_tracer.cpp:30-36, 60-73
-        const DMaterial &material = materials[isect.material];
-        prepareLobes<TRAITS>(material, isect);
-
-        path.random.dimension = vertexBase(vertex);
-        const BSDFSample bsdfSample = materialSample<TRAITS>(material, isect, path.random);
-
-        const bool counts = checkCounts(p.startBounce, p.lastBounce, vertex);
-        const bool emissive = !isBlack(matEmit(material));
-        const bool wantDirect = counts && !emissive;  // direct() returns 0 on emitters (:86-90)
-        const bool wantContinue = !checkDone(p.lastBounce, vertex + 1);
-
-        Rgb lightTerm = rgb(0.f);
-        if (wantDirect) {
-            path.random.dimension = vertexBase(vertex) + 3;
-            lightTerm = sampleLightsTerm<false, TRAITS>(scene, materials, isect, material, path.random, &shadow);
-        }
-
-        // see k_shade: a vertex with nothing pending whose BSDF sample has exactly black throughput ends the sample
-        const bool deadEnd = isBlack(bsdfSample.throughput) && bsdfSample.pdf > 0.f && bsdfSample.pdf < 3e38f
-            && !shadow.push && isBlack(lightTerm);
-        if ((!wantDirect && !wantContinue) || deadEnd) {
-            finished = true;
-            Rgb first = rgb(0.f);
-            if (path.firstEmitMaterial >= 0) { first = first + matEmit(materials[path.firstEmitMaterial]); }
-            *color = first + path.result;
-            shadow.push = false;
-        } else {
-            int nextState = vertex;
-            if (wantDirect) { nextState |= kStEligible; }
-            if (isDeltaT<TRAITS>(material)) { nextState |= kStDelta; }
-            if (wantContinue) { nextState |= kStContinue; }
-            path.st = nextState;
-            path.o = isect.point;
-            path.d = bsdfSample.wiWorld;
-            path.bsdfPdf = bsdfSample.pdf;
-            path.throughput = bsdfSample.throughput;
-            path.cosTheta = fabsf(dot(isect.shadingNormal, bsdfSample.wiWorld));
-            path.pend = lightTerm;
-        }
-    }
-    *shadowOut = shadow;
-    return finished;
-}
 
 #ifndef PATHED_WAVE_WAVES
 #define PATHED_WAVE_WAVES 3   // blocks per CU = waves per SIMD: what 160 KB of LDS holds of stacks + ray lists (168 VGPRs each)
@@ -203,73 +64,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_W
         __syncthreads();
     }
 
-    MaterialAccess<LDS_MATERIALS> materials;
-    if (LDS_MATERIALS) {
-        const int words = p.scene.nMaterials * (int)(sizeof(DMaterial) / 4);
-        const int *source = reinterpret_cast<const int *>(p.scene.materials);
-        int *target = reinterpret_cast<int *>(ldsRaw + ((STACK + 1) * kBlock) / 4 + kWavesPerBlock * 2 * kWaveListRays + kBlock + kBlock / 4 + (BLOCK ? (kWaveRing + 4) / 4 : 0));
-        for (int i = threadIdx.x; i < words; i += kBlock) { target[i] = source[i]; }
-        __syncthreads();
-        materials.table = reinterpret_cast<const DMaterial *>(target);
-    } else {
-        materials.table = p.scene.materials;
-    }
-
-    TraceGeometry geometry;
-    geometry.nodes = p.scene.nodes;
-    geometry.tris = p.scene.leafTris;
-    geometry.nNodes = p.scene.nNodes;
-    geometry.nTris = p.scene.nTris;
-    geometry.spheres = p.scene.spheres;
-    geometry.nSpheres = p.scene.nLinearSpheres;
+    const MaterialAccess<LDS_MATERIALS> materials = stageMaterials<LDS_MATERIALS>(
+        p, ldsRaw + ((STACK + 1) * kBlock) / 4 + kWavesPerBlock * 2 * kWaveListRays + kBlock + kBlock / 4 + (BLOCK ? (kWaveRing + 4) / 4 : 0));
+    const TraceGeometry geometry = sceneGeometry(p.scene, true);
 
     const DScene &scene = p.scene;
     const unsigned int waveId = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const uint64_t seed = ((uint64_t)p.seedHi << 32) | p.seedLo;
-
-    // ---- work units: as k_path_small
-    unsigned int queue = waveId % (unsigned int)p.nQueues, queuesTried = 0;
-    unsigned int reservedNext = 0, reservedEnd = 0;
-    auto takeUnits = [&](bool want) -> unsigned int {
-        unsigned int mine = 0xFFFFFFFFu;
-        unsigned long long wanting = __ballot(want);
-        while (wanting != 0ull) {
-            if (reservedNext == reservedEnd) {
-                if (queuesTried >= (unsigned int)p.nQueues) { break; }   // every queue is dealt out
-                unsigned int ticket = 0;
-                if (lane == 0) { ticket = atomicAdd(&p.counters[kCtrUnitCursor + queue * kCursorStride], (unsigned int)p.unitGrab); }
-                ticket = (unsigned int)__builtin_amdgcn_readfirstlane((int)ticket);
-                const unsigned int limit = p.queueUnits[queue];
-                if (ticket >= limit) {
-                    queue = (queue + 1u) % (unsigned int)p.nQueues;
-                    queuesTried++;
-                    continue;
-                }
-                reservedNext = ticket;
-                reservedEnd = ticket + (unsigned int)p.unitGrab < limit ? ticket + (unsigned int)p.unitGrab : limit;
-            }
-            const unsigned int available = reservedEnd - reservedNext;
-            const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(wanting >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)wanting, 0u));
-            const bool served = ((wanting >> lane) & 1ull) != 0ull && rank < available;
-            if (served) { mine = queue * p.unitsPerQueue + reservedNext + rank; }
-            const unsigned int count = (unsigned int)__popcll(wanting);
-            reservedNext += count < available ? count : available;
-            wanting &= ~__ballot(served);
-        }
-        return mine;
-    };
+    UnitTaker units(p, waveId);
 
     // ---- the path a lane owns
     bool alive = false;
     unsigned int unit = 0xFFFFFFFFu;
     uint32_t pixel = 0, sample = 0, endSample = 0;
-    PathRegisters path;
-    path.random.k0 = 0u; path.random.k1 = 0u; path.random.dimension = 0u;
-    path.o = v3(0.f, 0.f, 0.f); path.d = v3(0.f, 0.f, 1.f);
-    path.st = 0;
-    path.firstEmitMaterial = -1;
-    path.result = rgb(0.f); path.modulation = rgb(1.f); path.throughput = rgb(0.f); path.pend = rgb(0.f);
-    path.bsdfPdf = 1.f; path.cosTheta = 0.f;
+    PathRegisters path = idlePath();
     float4 partial = make_float4(0.f, 0.f, 0.f, 0.f);
     bool fresh = false;              // path.o / path.d (and the shadow request) are new: post them
     bool pendingShadow = false;
@@ -289,33 +97,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_W
     unsigned long long profBurstCycles = 0, profShadeCycles = 0, profStart = __builtin_amdgcn_s_memtime(), profStamp = 0;
 #endif
     bool startNext = false;
-    {
-        unit = takeUnits(true);
-        if (unit != 0xFFFFFFFFu) {
-            unitSamples(p, unit, &pixel, &sample, &endSample);
-            alive = true;
-            startNext = true;
-        }
-    }
+    firstUnits(p, units, lane, unit, pixel, sample, endSample, alive, startNext);
 
     while (true) {
         if (startNext) {
-            makeKey(seed, pixel, sample, &path.random.k0, &path.random.k1);
-            path.random.dimension = 0;
-            const int width = scene.camera.resX;
-            const int row = (int)fastDivide((unsigned int)pixel, p.divWidth);
-            const int col = (int)pixel - row * width;
-            const float jitterX = path.random.next() - 0.5f;
-            const float jitterY = path.random.next() - 0.5f;
-            cameraRay(scene.camera, row + jitterY, col + jitterX, &path.o, &path.d);
-            path.st = 0;
-            path.firstEmitMaterial = -1;
-            path.result = rgb(0.f);
-            path.modulation = rgb(1.f);
-            path.throughput = rgb(0.f);
-            path.pend = rgb(0.f);
-            path.bsdfPdf = 1.f;
-            path.cosTheta = 0.f;
+            startCameraSample(p, seed, pixel, sample, path);
             startNext = false;
             fresh = true;
             pendingShadow = false;
@@ -584,38 +370,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_W
             }
         }
 
-        // ---- end of a sample (k_path_small)
-        bool needUnit = false;
-        if (ready && finished) {
-            const bool finite = isfinite(color.r) && isfinite(color.g) && isfinite(color.b);
-            if (finite) {
-                partial.x += color.r;
-                partial.y += color.g;
-                partial.z += color.b;
-            } else {
-                atomicAdd(&p.stats[kStatDropped], 1ull);
-            }
-            sample++;
-            if (sample < endSample) {
-                startNext = true;
-            } else {
-                p.state.chunkBuf[partialIndex(p, unit)] = partial;
-                partial = make_float4(0.f, 0.f, 0.f, 0.f);
-                needUnit = true;
-            }
-        }
-        if (__ballot(needUnit) != 0ull) {
-            const unsigned int newUnit = takeUnits(needUnit);
-            if (needUnit) {
-                unit = newUnit;
-                if (newUnit != 0xFFFFFFFFu) {
-                    unitSamples(p, newUnit, &pixel, &sample, &endSample);
-                    startNext = true;
-                } else {
-                    alive = false;
-                }
-            }
-        }
+        finishSample(p, units, lane, ready && finished, color, partial, unit, pixel, sample, endSample, alive, startNext);
 #ifdef PATHED_SHADE_PROFILE
         profShadeCycles += __builtin_amdgcn_s_memtime() - profStamp;
 #endif
