@@ -39,7 +39,8 @@ extern "C" {
                                 *    PathedSceneOptions.build_threads; pathed_hip_comm_* (RCCL reduce of the radiance sums) */
 /* Additions that leave PathedSceneDesc unchanged (no version bump): PathedSceneOptions /
  * pathed_hip_scene_create_ex (per-scene device and tuning), pathed_hip_measure_valu,
- * pathed_hip_accum_add / pathed_hip_accum_copy_peer (multi-GPU fan-in of the radiance sums). */
+ * pathed_hip_accum_add / pathed_hip_accum_copy_peer (multi-GPU fan-in of the radiance sums),
+ * PathedFeatureBuffers / pathed_hip_render_features[_device] (first-hit feature images), PATHED_INTEGRATOR_ALBEDO. */
 
 /* error codes */
 #define PATHED_OK            0
@@ -218,7 +219,9 @@ typedef struct PathedStats {
                                       4 volume path kernel (PATHED_INTEGRATOR_VOLUME_PATH_TRACER),
                                       5 wavefront with the split shade stage (k_vertex + k_regen over the trace kernel's lists),
                                       6 wave path kernel (BVH scenes, the last render call),
-                                      7 hybrid path kernel (scenes of 65 .. 4096 triangles, the last render call) */
+                                      7 hybrid path kernel (scenes of 65 .. 4096 triangles, the last render call),
+                                      8 feature kernel (the last call was pathed_hip_render_features[_device], or a render call
+                                        of PATHED_INTEGRATOR_ALBEDO; its samples count in camera_samples and closest_rays) */
     uint32_t reserved0;
     uint64_t local_closest_rays;   /* closest-hit queries the shade kernel resolved itself (rays that cannot meet anything but the
                                       scene's few large triangles, PathedSceneOptions.local_rays) -- stats mode; NOT in closest_rays */
@@ -367,9 +370,17 @@ int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
  *   PATHED_INTEGRATOR_VOLUME_PATH_TRACER  VolumePathTracer::L (src/volume_path_tracer.cpp:14-131) with
  *                                         DirectLightingHelper::Ld (src/direct_lighting_helper.cpp:37-187): participating
  *                                         media behind PATHED_MAT_PASSTHROUGH containers, single scattering per segment.
+ *   PATHED_INTEGRATOR_ALBEDO              AlbedoIntegrator::L (src/albedo_integrator.cpp:3-11): a sample is the first hit's emission
+ *                                         (when the bounce window counts bounce 0 and the hit is no backside) plus
+ *                                         Material::albedo -- a Lambertian's albedo lookup, (1, 0, 0) for EVERY other material, as
+ *                                         in the reference (include/material.h:52-54) -- or the environment on a miss.  The render
+ *                                         calls run the feature kernel: last_bounce is ignored, start_bounce only decides the
+ *                                         emission, and a pixel's samples are summed one by one in sample order whatever
+ *                                         pathed_hip_set_samples_per_unit says.
  * Scenes that contain PATHED_MAT_PASSTHROUGH materials render with the volume integrator only. */
 #define PATHED_INTEGRATOR_PATH_TRACER 0
 #define PATHED_INTEGRATOR_VOLUME_PATH_TRACER 1
+#define PATHED_INTEGRATOR_ALBEDO 2
 int pathed_hip_set_integrator(PathedScene *scene, int integrator);
 
 /* Summation granularity.  A pixel's samples are summed in sample order in groups of
@@ -379,6 +390,30 @@ int pathed_hip_set_integrator(PathedScene *scene, int integrator);
  * it is also the finest grain of the work queue (a render call drains its last UNITS).
  * Larger groups write fewer partial sums (16 bytes per unit).  Range [1, 128]. */
 int pathed_hip_set_samples_per_unit(PathedScene *scene, int samples);
+
+/* First-hit feature images, rendered with the camera samples of the render calls (same seed, same sample indices: the ray
+ * of pixel p, sample s is the render's): what a denoiser or a compositor wants beside the radiance sums.  Per sample whose
+ * camera ray hits something in [1e-3, 1e5]:
+ *   albedo_sum += the diffuse colour through the material's albedo kind (Lambertian, OrenNayar, Plastic), (1, 1, 1) for
+ *                 Microfacet, Glass and Mirror
+ *   normal_sum += the shading normal of the hit, world space, not flipped towards the viewer
+ *   depth_sum  += t          hit_count += 1
+ * and nothing on a miss.  A pixel's samples are added IN SAMPLE ORDER onto what the buffers hold, so any split of
+ * [0, n) into calls gives the same floats.  The call follows pathed_hip_scene_set_camera and pathed_hip_scene_refit.
+ * Scenes with PATHED_MAT_PASSTHROUGH materials: PATHED_E_UNSUPPORTED. */
+typedef struct PathedFeatureBuffers {   /* device pointers; any may be NULL = not wanted (all NULL: PATHED_E_INVALID) */
+    float *albedo_sum;   /* 3*W*H, layout of the radiance sums */
+    float *normal_sum;   /* 3*W*H */
+    float *depth_sum;    /* W*H   */
+    float *hit_count;    /* W*H, samples that hit something (as float) */
+} PathedFeatureBuffers;
+/* buffers in DEVICE memory, work enqueued on `stream` (a hipStream_t, NULL = default stream); returns when it has completed */
+int pathed_hip_render_features_device(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                                      const PathedFeatureBuffers *buffers, void *stream);
+/* buffers in HOST memory (any may be NULL); ADDS the call's samples to them like pathed_hip_render -- one by one, in sample
+ * order, onto what they hold: 3 + 5 samples in two calls are the 8 of one call, bit for bit */
+int pathed_hip_render_features(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                               float *albedo, float *normal, float *depth, float *hits);
 
 /* Test hook onto the intersector that stands in for Embree.
  * rays: n * 8 floats (ox,oy,oz,tnear, dx,dy,dz,tfar), host memory.

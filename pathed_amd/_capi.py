@@ -14,7 +14,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 PATHED_ABI_VERSION = 4
 
 MAT_LAMBERTIAN, MAT_OREN_NAYAR, MAT_MICROFACET, MAT_PLASTIC, MAT_GLASS, MAT_MIRROR, MAT_PASSTHROUGH = range(7)
-INTEGRATOR_PATH_TRACER, INTEGRATOR_VOLUME_PATH_TRACER = 0, 1
+INTEGRATOR_PATH_TRACER, INTEGRATOR_VOLUME_PATH_TRACER, INTEGRATOR_ALBEDO = 0, 1, 2
 ALBEDO_CONSTANT, ALBEDO_CHECKERBOARD, ALBEDO_TEXTURE = 0, 1, 2
 GEOM_MESH, GEOM_SPHERE = 0, 1
 
@@ -170,6 +170,10 @@ class PathedSceneOptions(C.Structure):
     ]
 
 
+class PathedFeatureBuffers(C.Structure):
+    _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p)]
+
+
 class PathedValuClocks(C.Structure):
     _fields_ = [(name, C.c_double) for name in (
         "rate", "shader_clock_mhz", "wall_clock_mhz", "peak_clock_mhz", "wave_ticks_per_instruction",
@@ -188,6 +192,8 @@ HIP_SYMBOLS = [
     "pathed_hip_scene_destroy",
     "pathed_hip_render",
     "pathed_hip_render_device",
+    "pathed_hip_render_features",
+    "pathed_hip_render_features_device",
     "pathed_hip_trace",
     "pathed_hip_debug_small_candidates",
     "pathed_hip_debug_light_records",
@@ -287,6 +293,10 @@ def load_hip():
     lib.pathed_hip_render.restype = C.c_int
     lib.pathed_hip_render_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, vp, C.c_int]
     lib.pathed_hip_render_device.restype = C.c_int
+    lib.pathed_hip_render_features.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, fp, fp, fp, fp]
+    lib.pathed_hip_render_features.restype = C.c_int
+    lib.pathed_hip_render_features_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(PathedFeatureBuffers), vp]
+    lib.pathed_hip_render_features_device.restype = C.c_int
     lib.pathed_hip_trace.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, vp]
     lib.pathed_hip_trace.restype = C.c_int
     lib.pathed_hip_debug_small_candidates.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint64)]

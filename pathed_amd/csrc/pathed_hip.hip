@@ -5,6 +5,7 @@
 
 #include "bvh_build.h"
 #include "kernels.h"
+#include "features.h"
 #if PATHED_EXPERIMENTS
 #include "kernels_experiments.h"
 #endif
@@ -240,6 +241,8 @@ struct PathedScene {
     bool waveAvailable = false;   // ... and the scene is one it serves
     bool lastCallWave = false;    // what the last render call ran (PathedStats.path_kernel)
     bool lastCallHybrid = false;
+    bool lastCallFeatures = false;   // ... k_features (features.h): a feature call, or a render call of the albedo integrator
+    unsigned long long featureRays = 0;   // closest-hit queries of k_features since reset_stats (one per camera sample)
     unsigned long long waveMaxSamples = 48ull << 20;   // calls of fewer camera samples than this take it (waveMode 0)
     int waveStragglers = 24;      // its traversal bursts end once fewer rays than this are in flight
     bool waveBlock = false;       // the block's waves share one ray ring (k_path_wave<.., BLOCK>; PATHED_WAVE_BLOCK=1)
@@ -2532,6 +2535,70 @@ static int renderPass(PathedScene *scene, const Pass &pass)
     return PATHED_OK;
 }
 
+// k_features (features.h) over samples [begin, begin + count) of every pixel: the feature sums of `out`, or -- reference: the
+// albedo integrator -- rgb sums into `accum`.  One launch; returns when it has completed.
+static int launchFeatures(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_t count, int startBounce, int lastBounce,
+                          bool reference, float *accum, const FeatureBuffers &out, hipStream_t stream)
+{
+    if (!scene->stats.ptr) {
+        HIP_TRY(scene->stats.allocate(kStatCount));
+        HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
+    }
+    // a wave per 8 x 8 tile; the grid is what the kernel's register budget keeps resident (four blocks per CU) or fewer
+    const unsigned long long tiles = (unsigned long long)((scene->width + 7) / 8) * (unsigned long long)((scene->height + 7) / 8);
+    unsigned long long blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+    const unsigned long long resident = (unsigned long long)scene->computeUnits * 4ull;
+    if (blocks > resident) { blocks = resident; }
+    if (blocks < 1) { blocks = 1; }
+
+    RenderParams params;
+    std::memset(&params, 0, sizeof params);
+    const size_t overflowRows = (size_t)(scene->maxStack > scene->stackRows ? scene->maxStack - scene->stackRows : 0);
+    const size_t overflowInts = (size_t)blocks * kBlock * (overflowRows ? overflowRows : 1);
+    if (scene->volumeOverflow.count < overflowInts) { HIP_TRY(scene->volumeOverflow.allocate(overflowInts)); }
+    params.stackOverflow = scene->volumeOverflow.ptr;
+    params.maxStack = scene->maxStack;
+    params.scene = scene->device;
+    params.stats = scene->stats.ptr;
+    params.accum = accum;
+    params.nPixels = scene->width * scene->height;
+    params.divWidth = makeFastDiv((unsigned int)scene->width);
+    params.seedLo = (uint32_t)seed;
+    params.seedHi = (uint32_t)(seed >> 32);
+    params.sppBegin = begin;
+    params.sppEnd = begin + count;
+    params.startBounce = startBounce;
+    params.lastBounce = lastBounce;
+
+    int timed = -1;
+    if (scene->timeKernels) {
+        HIP_TRY(scene->traceEvents.create());
+        timed = scene->traceEvents.acquire();
+        (void)hipEventRecord(scene->traceEvents.start[timed], stream);
+    }
+    const dim3 grid((unsigned)blocks), block(kBlock);
+    const size_t lds = (size_t)(scene->stackRows + 1) * kBlock * sizeof(int);
+    withBool(reference, [&](auto REFERENCE) {
+        switch (scene->stackRows) {
+        case 8: hipLaunchKernelGGL((k_features<8, REFERENCE>), grid, block, lds, stream, params, out); break;
+        case 16: hipLaunchKernelGGL((k_features<16, REFERENCE>), grid, block, lds, stream, params, out); break;
+        default: hipLaunchKernelGGL((k_features<22, REFERENCE>), grid, block, lds, stream, params, out); break;
+        }
+    });
+    if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], stream); }
+    scene->traceLaunchesAll++;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (scene->timeKernels) { scene->traceEvents.harvestAll(); }
+
+    const unsigned long long samples = (unsigned long long)count * (unsigned long long)scene->width * (unsigned long long)scene->height;
+    scene->iterations += 1;
+    scene->cameraSamples += samples;
+    scene->featureRays += samples;
+    scene->lastCallFeatures = true;
+    return PATHED_OK;
+}
+
 extern "C" {
 
 int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
@@ -2546,10 +2613,18 @@ int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
     }
     if (spp_count == 0) { return PATHED_OK; }
     if ((uint64_t)spp_begin + spp_count > 0x7fffffffull) { return fail(PATHED_E_INVALID, "sample index overflow"); }
+    if (scene->integrator == PATHED_INTEGRATOR_ALBEDO) {
+        // AlbedoIntegrator::L never looks at the bounce window: last_bounce is ignored, start_bounce decides bounce 0's emission
+        if (scene->hasContainers) { return fail(PATHED_E_UNSUPPORTED, "the albedo integrator does not render scenes with passthrough (medium container) surfaces"); }
+        SELECT_DEVICE(scene);
+        FeatureBuffers none = { nullptr, nullptr, nullptr, nullptr };
+        return launchFeatures(scene, seed, spp_begin, spp_count, start_bounce, -1, true, d_accum_rgb_sum, none, (hipStream_t)stream_handle);
+    }
     if (scene->hasContainers && scene->integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER) {
         return fail(PATHED_E_UNSUPPORTED, "the scene has passthrough (medium container) surfaces: select the VolumePathTracer integrator (pathed_hip_set_integrator)");
     }
     SELECT_DEVICE(scene);
+    scene->lastCallFeatures = false;
 
     if (scene->timeKernels) {
         HIP_TRY(scene->traceEvents.create());
@@ -2627,7 +2702,7 @@ int pathed_hip_scene_set_camera(PathedScene *scene, const PathedCamera *camera)
 int pathed_hip_set_integrator(PathedScene *scene, int integrator)
 {
     if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
-    if (integrator != PATHED_INTEGRATOR_PATH_TRACER && integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER) {
+    if (integrator != PATHED_INTEGRATOR_PATH_TRACER && integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER && integrator != PATHED_INTEGRATOR_ALBEDO) {
         return fail(PATHED_E_INVALID, "unknown integrator");
     }
     scene->integrator = integrator;
@@ -2663,6 +2738,51 @@ int pathed_hip_render(PathedScene *scene, uint64_t seed,
     (void)hipFree(deviceAccum);
     if (status != hipSuccess) { return fail(PATHED_E_DEVICE, hipGetErrorString(status)); }
     for (size_t i = 0; i < count; i++) { accum_rgb_sum[i] += host[i]; }
+    return PATHED_OK;
+}
+
+int pathed_hip_render_features_device(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                                      const PathedFeatureBuffers *buffers, void *stream_handle)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (!buffers || (!buffers->albedo_sum && !buffers->normal_sum && !buffers->depth_sum && !buffers->hit_count)) {
+        return fail(PATHED_E_INVALID, "no feature buffer: pass at least one of albedo, normal, depth, hits");
+    }
+    if (spp_count == 0) { return PATHED_OK; }
+    if ((uint64_t)spp_begin + spp_count > 0x7fffffffull) { return fail(PATHED_E_INVALID, "sample index overflow"); }
+    if (scene->hasContainers) { return fail(PATHED_E_UNSUPPORTED, "feature images do not cover scenes with passthrough (medium container) surfaces"); }
+    SELECT_DEVICE(scene);
+    const FeatureBuffers out = { buffers->albedo_sum, buffers->normal_sum, buffers->depth_sum, buffers->hit_count };
+    return launchFeatures(scene, seed, spp_begin, spp_count, 0, -1, false, nullptr, out, (hipStream_t)stream_handle);
+}
+
+int pathed_hip_render_features(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                               float *albedo, float *normal, float *depth, float *hits)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (!albedo && !normal && !depth && !hits) { return fail(PATHED_E_INVALID, "no feature buffer: pass at least one of albedo, normal, depth, hits"); }
+    SELECT_DEVICE(scene);
+    // one device buffer, the wanted images side by side; the sums continue from what the caller's arrays hold
+    const size_t pixels = (size_t)scene->width * scene->height;
+    float *host[4] = { albedo, normal, depth, hits };
+    const size_t floats[4] = { 3 * pixels, 3 * pixels, pixels, pixels };
+    size_t offset[4], total = 0;
+    for (int i = 0; i < 4; i++) { offset[i] = total; if (host[i]) { total += floats[i]; } }
+    DeviceBuffer<float> device;
+    HIP_TRY(device.allocate(total));
+    for (int i = 0; i < 4; i++) {
+        if (host[i]) { HIP_TRY(hipMemcpy(device.ptr + offset[i], host[i], floats[i] * sizeof(float), hipMemcpyHostToDevice)); }
+    }
+    PathedFeatureBuffers buffers;
+    buffers.albedo_sum = albedo ? device.ptr + offset[0] : nullptr;
+    buffers.normal_sum = normal ? device.ptr + offset[1] : nullptr;
+    buffers.depth_sum = depth ? device.ptr + offset[2] : nullptr;
+    buffers.hit_count = hits ? device.ptr + offset[3] : nullptr;
+    const int code = pathed_hip_render_features_device(scene, seed, spp_begin, spp_count, &buffers, nullptr);
+    if (code != PATHED_OK) { return code; }
+    for (int i = 0; i < 4; i++) {
+        if (host[i]) { HIP_TRY(hipMemcpy(host[i], device.ptr + offset[i], floats[i] * sizeof(float), hipMemcpyDeviceToHost)); }
+    }
     return PATHED_OK;
 }
 
@@ -2882,6 +3002,7 @@ int pathed_hip_reset_stats(PathedScene *scene)
     scene->iterations = 0;
     scene->traceLaunchesAll = 0;
     scene->cameraSamples = 0;
+    scene->featureRays = 0;
     scene->traceEvents.totalMs = 0.0;
     scene->traceEvents.launches = 0;
     scene->shadeEvents.totalMs = 0.0;
@@ -2899,7 +3020,7 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
         HIP_TRY(hipMemcpy(device, scene->stats.ptr, sizeof device, hipMemcpyDeviceToHost));
     }
     out->camera_samples = scene->cameraSamples;
-    out->closest_rays = device[kStatClosest];
+    out->closest_rays = device[kStatClosest] + scene->featureRays;
     out->shadow_rays = device[kStatShadow];
     out->nodes_visited = device[kStatBoxes];
     out->tris_tested = device[kStatTris];
@@ -2919,7 +3040,7 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
     out->bvh_build_ms = scene->bvhBuildMs;
     out->bvh_builder = (uint32_t)scene->bvhBuilder;
     out->trace_launches_all = (uint32_t)scene->traceLaunchesAll;
-    out->path_kernel = usesVolumeKernel(scene) ? 4u : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
+    out->path_kernel = scene->lastCallFeatures ? 8u : usesVolumeKernel(scene) ? 4u : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
     if (tuningEnv("PATHED_SHADE_PROFILE")) {   // counters exist in -DPATHED_SHADE_PROFILE builds only
         static const char *regions[11] = { "all waves", "active slots", "makeIsect (hit)", "camera-ray vertex", "finish previous MIS term",
                                            "new vertex: BSDF sample", "light sampling", "sample finished", "startSample (regeneration)", "shadow ray pushed",

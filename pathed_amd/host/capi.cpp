@@ -147,6 +147,7 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
     using namespace pathed;
     try {
         Job job(jobPath);
+        const std::vector<std::string> features = job.features();   // (a bad name stops the job before it touches the output directory)
         job.init();
 
         const int width = job.width();
@@ -202,6 +203,7 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
             integrator->setStateIdentity(job.scene() + "|" + job.integratorName() + "|" + assetRoot + "|" + builder + "|" + sceneDigest);
         }
         integrator->setUseRccl(reduce == "rccl");
+        integrator->setFeatures(features);
         if (earlyComm) { integrator->adoptComm(earlyComm); earlyComm = nullptr; }
         const std::string metricsLevel = job.metricsLevel();
         if (metricsLevel != "full" && metricsLevel != "basic") { throw std::runtime_error("job: \"metrics\" must be \"full\" or \"basic\""); }

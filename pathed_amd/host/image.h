@@ -27,6 +27,7 @@ public:
     const std::vector<float> &raw() const { return m_raw; }
     int width() const { return m_width; }
     int height() const { return m_height; }
+    const std::string &outputDirectory() const { return m_outputDirectory; }
 
 private:
     void save(const std::string &filestem, bool saveCheckpoint);

@@ -266,6 +266,54 @@ void Integrator::run(
         }
     }
 
+    // feature images (setFeatures): sums on replica 0's device -- albedo, normal, depth, hits side by side -- that follow `done`
+    // whenever an image is published
+    const size_t pixels = (size_t)width * height;
+    const bool wantFeatures = !m_features.empty();
+    float *featureSums = nullptr;
+    struct FeatureCleanup {
+        Scene &scene;
+        float *&sums;
+        ~FeatureCleanup() { if (sums) { pathed_hip_accum_free(scene.handle(0), sums); } }
+    } featureCleanup{ scene, featureSums };
+    int featuresDone = 0;
+    std::vector<float> featureHost;
+    auto publishFeatures = [&](int upTo, bool checkpoint) {
+        if (!wantFeatures) { return; }
+        if (!featureSums && pathed_hip_accum_alloc(scene.handle(0), 8 * pixels, &featureSums) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_alloc")); }
+        PathedFeatureBuffers buffers = { featureSums, featureSums + 3 * pixels, featureSums + 6 * pixels, featureSums + 7 * pixels };
+        while (featuresDone < upTo) {
+            const int count = std::min(m_sppPerLaunch, upTo - featuresDone);
+            if (pathed_hip_render_features_device(scene.handle(0), m_seed, (uint32_t)featuresDone, (uint32_t)count, &buffers, nullptr) != PATHED_OK) {
+                throw std::runtime_error(hipError("pathed_hip_render_features_device"));
+            }
+            featuresDone += count;
+        }
+        featureHost.resize(8 * pixels);
+        if (pathed_hip_accum_download(scene.handle(0), featureSums, 8 * pixels, featureHost.data()) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_download")); }
+        for (const std::string &name : m_features) {
+            Image featureImage(width, height, image.outputDirectory());
+            featureImage.setSpp(upTo);
+            for (int row = 0; row < height; row++) {
+                for (int col = 0; col < width; col++) {
+                    const size_t pixel = (size_t)row * width + col;
+                    if (name == "depth") {
+                        // mean distance of the samples that hit something, 0 where none did
+                        const float hits = featureHost[7 * pixels + pixel];
+                        const float depth = hits > 0.f ? featureHost[6 * pixels + pixel] / hits : 0.f;
+                        featureImage.set(row, col, depth, depth, depth);
+                    } else {
+                        // albedo and normal: sum / samples (misses count as zero; normals stay unnormalised)
+                        const float *sums = featureHost.data() + (name == "albedo" ? 0 : 3 * pixels) + 3 * pixel;
+                        featureImage.set(row, col, sums[0] / upTo, sums[1] / upTo, sums[2] / upTo);
+                    }
+                }
+            }
+            if (checkpoint) { featureImage.saveCheckpoint("auto-" + name); }
+            else { featureImage.save("auto-" + name); }
+        }
+    };
+
     m_metrics.replicas = (int)replicas;
     m_metrics.firstSample = done;
     m_metrics.replicaSeconds.assign(replicas, 0.0);
@@ -339,6 +387,7 @@ void Integrator::run(
             // rendered is in a file (no numbered checkpoint for it).  python -m pathed_amd.run_job does exactly the same.
             if (checkpoint) { image.saveCheckpoint("auto"); }
             else if (done == primarySamples) { image.save("auto"); }
+            if (checkpoint || done == primarySamples) { publishFeatures(done, checkpoint); }
             saveState(radianceLookup, width, height, done);
         }
 

@@ -105,6 +105,11 @@ public:
     // that a machine without a usable RCCL stops the job in its first second, not after N BVH builds): run() uses it instead
     // of making its own, and destroys it when it is done.
     void adoptComm(PathedComm *comm) { m_adoptedComm = comm; }
+    // job key "features": first-hit feature images ("albedo", "normal", "depth") of the same camera samples, written as
+    // auto-<name>*.exr wherever run() writes auto*.exr.  Rendered on replica 0 alone over [0, done) in batches as the images
+    // fall due -- one ray per sample -- so N GPUs give one GPU's feature images bit for bit.  The sums are not in auto.state:
+    // a resumed run renders [0, done) of them again first (the random stream is counter-based: the straight run's bits).
+    void setFeatures(const std::vector<std::string> &names) { m_features = names; }
     const RenderMetrics &metrics() const { return m_metrics; }
 
 protected:
@@ -127,6 +132,7 @@ protected:
     unsigned long long m_stateDigest = 0;
     std::string m_statePath;
     std::string m_logPrefix;
+    std::vector<std::string> m_features;
     RenderMetrics m_metrics;
 };
 

@@ -51,6 +51,25 @@ std::vector<int> Job::devices() const
     return ids;
 }
 
+std::vector<std::string> Job::features() const
+{
+    const Json &wanted = m_json["features"];
+    std::vector<std::string> names;
+    if (wanted.isNull()) { return names; }
+    if (!wanted.isArray()) { throw std::runtime_error("job: \"features\" must be a list of names out of albedo, normal, depth"); }
+    bool want[3] = { false, false, false };
+    static const char *known[3] = { "albedo", "normal", "depth" };
+    for (size_t i = 0; i < wanted.size(); i++) {
+        if (!wanted[i].isString()) { throw std::runtime_error("job: \"features\" must be a list of names out of albedo, normal, depth"); }
+        const std::string &name = wanted[i].asString();
+        bool found = false;
+        for (int k = 0; k < 3; k++) { if (name == known[k]) { want[k] = true; found = true; } }
+        if (!found) { throw std::runtime_error("job: unknown feature \"" + name + "\" (known: albedo, normal, depth)"); }
+    }
+    for (int k = 0; k < 3; k++) { if (want[k]) { names.push_back(known[k]); } }
+    return names;
+}
+
 std::shared_ptr<Integrator> Job::integrator() const
 {
     const std::string name = integratorName();
@@ -59,6 +78,9 @@ std::shared_ptr<Integrator> Job::integrator() const
     } else if (name == "VolumePathTracer") {
         // src/job.cpp:71-72: participating media behind passthrough containers
         return std::make_shared<HipPathTracer>(m_bounceController, PATHED_INTEGRATOR_VOLUME_PATH_TRACER);
+    } else if (name == "AlbedoIntegrator") {
+        // src/job.cpp:91: a SampleIntegrator whose L is material->albedo(intersection)
+        return std::make_shared<HipPathTracer>(m_bounceController, PATHED_INTEGRATOR_ALBEDO);
     } else if (name == "DataParallelIntegrator") {
         // the reference's stage-wise integrator needs its external sampler server; its
         // wavefront STRUCTURE is what HipPathTracer implements

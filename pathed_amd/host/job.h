@@ -10,7 +10,10 @@
 //               N replicas would otherwise run N host builds side by side, seconds of serial time before the first sample),
 //   "gpus" (1): a count N -> devices gpu .. gpu+N-1, or an explicit list of device ids (an id may
 //               repeat: several replicas on one GPU); the samples of every batch are split over them,
-//   "resume" (false): continue from <output_directory>/auto.state if it exists.
+//   "resume" (false): continue from <output_directory>/auto.state if it exists,
+//   "features" (absent): a list out of "albedo", "normal", "depth" -- first-hit feature images of the same camera samples
+//               (include/pathed_hip.h: pathed_hip_render_features), written beside every auto*.exr as auto-albedo*.exr,
+//               auto-normal*.exr, auto-depth*.exr.  An unknown name is an error.
 #pragma once
 
 #include "bounce_controller.h"
@@ -64,6 +67,7 @@ public:
     }
     bool resume() const { return m_json["resume"].isBool() && m_json["resume"].asBool(); }
     std::vector<int> devices() const;
+    std::vector<std::string> features() const;   // in the order albedo, normal, depth
     int gpu() const { return m_json["gpu"].isNumber() ? m_json["gpu"].asInt() : 0; }
     std::string assetRoot() const { return m_json["asset_root"].isString() ? m_json["asset_root"].asString() : ""; }
     std::string bvhBuilder() const { return m_json["bvh_builder"].isString() ? m_json["bvh_builder"].asString() : "auto"; }

@@ -129,6 +129,34 @@ class HipScene:
             C.c_void_p(device_pointer), C.c_void_p(stream), 1)
         _check(self._lib, code, "pathed_hip_render_device")
 
+    def render_features(self, seed, spp_begin, spp_count, albedo=None, normal=None, depth=None, hits=None):
+        """First-hit feature sums of samples [spp_begin, spp_begin + spp_count) (pathed_hip_render_features): albedo and normal
+        (H, W, 3), depth and hits (H, W), float32 host arrays the call adds its samples to, one by one in sample order.  With no array given all four are made and
+        returned; otherwise only the ones passed are rendered (the others come back None)."""
+        if albedo is None and normal is None and depth is None and hits is None:
+            albedo = np.zeros((self.height, self.width, 3), dtype=np.float32)
+            normal = np.zeros((self.height, self.width, 3), dtype=np.float32)
+            depth = np.zeros((self.height, self.width), dtype=np.float32)
+            hits = np.zeros((self.height, self.width), dtype=np.float32)
+        pointers = []
+        for array, channels in ((albedo, 3), (normal, 3), (depth, 1), (hits, 1)):
+            if array is None:
+                pointers.append(None)
+                continue
+            assert array.dtype == np.float32 and array.flags["C_CONTIGUOUS"] and array.size == channels * self.width * self.height
+            pointers.append(array.ctypes.data_as(C.POINTER(C.c_float)))
+        code = self._lib.pathed_hip_render_features(self._handle, C.c_uint64(seed), spp_begin, spp_count, *pointers)
+        _check(self._lib, code, "pathed_hip_render_features")
+        return albedo, normal, depth, hits
+
+    def render_features_device(self, seed, spp_begin, spp_count, albedo=0, normal=0, depth=0, hits=0, stream=0):
+        """Same, onto caller-owned device memory (e.g. tensor.data_ptr(); 0 = not wanted) on `stream`: the sums CONTINUE from
+        the buffers' contents, in sample order."""
+        buffers = _capi.PathedFeatureBuffers(albedo or None, normal or None, depth or None, hits or None)
+        code = self._lib.pathed_hip_render_features_device(
+            self._handle, C.c_uint64(seed), spp_begin, spp_count, C.byref(buffers), C.c_void_p(stream))
+        _check(self._lib, code, "pathed_hip_render_features_device")
+
     def trace(self, rays, any_hit=False):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         n = rays.shape[0]
@@ -186,9 +214,9 @@ class HipScene:
         _check(self._lib, self._lib.pathed_hip_scene_set_camera(self._handle, C.byref(camera)), "pathed_hip_scene_set_camera")
 
     def set_integrator(self, name):
-        """"PathTracer" (default) or "VolumePathTracer" (reference src/job.cpp:65-97)."""
+        """"PathTracer" (default), "VolumePathTracer" or "AlbedoIntegrator" (reference src/job.cpp:65-97)."""
         code = {"PathTracer": _capi.INTEGRATOR_PATH_TRACER, "DataParallelIntegrator": _capi.INTEGRATOR_PATH_TRACER,
-                "VolumePathTracer": _capi.INTEGRATOR_VOLUME_PATH_TRACER}[name]
+                "VolumePathTracer": _capi.INTEGRATOR_VOLUME_PATH_TRACER, "AlbedoIntegrator": _capi.INTEGRATOR_ALBEDO}[name]
         _check(self._lib, self._lib.pathed_hip_set_integrator(self._handle, code), "pathed_hip_set_integrator")
 
     def set_stats_mode(self, count=False, time_kernels=False, time_sampled=False):
@@ -285,10 +313,25 @@ class PathTracer:
         return image
 
 
+INTEGRATOR_NAMES = ("PathTracer", "DataParallelIntegrator", "VolumePathTracer", "AlbedoIntegrator")
+FEATURE_NAMES = ("albedo", "normal", "depth")
+
+
+def features_from_job(job):
+    """The job key "features": a list drawn from FEATURE_NAMES, absent = none.  An unknown name is an error that names it."""
+    wanted = job.get("features", [])
+    if not isinstance(wanted, (list, tuple)):
+        raise PathedError("job: \"features\" must be a list of names out of %s" % ", ".join(FEATURE_NAMES))
+    for name in wanted:
+        if name not in FEATURE_NAMES:
+            raise PathedError("job: unknown feature \"%s\" (known: %s)" % (name, ", ".join(FEATURE_NAMES)))
+    return [name for name in FEATURE_NAMES if name in wanted]
+
+
 def integrator_from_job(job, **kwargs):
     """reference Job::integrator(), src/job.cpp:65-97 — only the hot-path integrator exists here."""
     name = job["integrator"]
-    if name in ("PathTracer", "DataParallelIntegrator", "VolumePathTracer"):
+    if name in INTEGRATOR_NAMES:
         # the caller selects the arithmetic on the scene: HipScene.set_integrator(name)
         return PathTracer(BounceController(job["startBounce"], job["lastBounce"]),
                           spp=job["spp"] if job["spp"] > 0 else 9999999, **kwargs)

@@ -31,7 +31,7 @@ def main(argv=None):
     import torch.distributed as dist
 
     from . import _capi, parallel
-    from .integrator import BounceController, HipScene
+    from .integrator import INTEGRATOR_NAMES, BounceController, HipScene, PathedError, features_from_job
     from .scene import LoadedScene
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -50,8 +50,12 @@ def main(argv=None):
     spp = job["spp"] if job["spp"] > 0 else 9999999
     seed = int(job.get("seed", 1))
     bounces = BounceController(job["startBounce"], job["lastBounce"])
-    if job["integrator"] not in ("PathTracer", "DataParallelIntegrator", "VolumePathTracer"):
+    if job["integrator"] not in INTEGRATOR_NAMES:
         raise SystemExit("Unimplemented")  # the reference throws "Unimplemented" (src/job.cpp:96)
+    try:
+        features = features_from_job(job)   # "features": first-hit feature images beside every auto*.exr
+    except PathedError as error:
+        raise SystemExit("pathed_amd.run_job: %s" % error)
     out_dir = job["output_directory"] + "/"
     # keys of the C++ host this runner does not implement are refused, not ignored: a job file must not behave
     # differently between the two runners (here the GPUs are the ranks of torch.distributed.run, and there is no auto.state)
@@ -97,6 +101,15 @@ def main(argv=None):
     # (pathed_amd/host/integrator.cpp) the loop renders ALL `spp` samples; numbered files appear at the powers of two only,
     # and when spp is not one the end of the run refreshes auto.exr with all of them -- the same files, sample counts and
     # timings whichever launcher ran the job.
+    # Feature images: rank 0 alone renders them, over [0, done) in batches as the images fall due (one ray per sample), so any
+    # number of ranks writes the feature files of one GPU, bit for bit.
+    feature_sums = None
+    features_done = 0
+    if features and rank == 0:
+        feature_sums = {"albedo": torch.zeros((height, width, 3), dtype=torch.float32, device="cuda"),
+                        "normal": torch.zeros((height, width, 3), dtype=torch.float32, device="cuda"),
+                        "depth": torch.zeros((height, width), dtype=torch.float32, device="cuda"),
+                        "hits": torch.zeros((height, width), dtype=torch.float32, device="cuda")}
     accum = torch.zeros((height, width, 3), dtype=torch.float32, device="cuda")
     total = torch.zeros_like(accum)
     done = 0
@@ -125,6 +138,25 @@ def main(argv=None):
                     if host.pathed_host_write_exr_half_bgr(path.encode(), width, height, pointer) != 0:
                         raise RuntimeError(host.pathed_host_last_error().decode())
                     print("Saved exr file. [ %s ] " % path)
+                if feature_sums is not None:
+                    while features_done < done:
+                        batch = min(spp_per_launch, done - features_done)
+                        gpu.render_features_device(seed, features_done, batch, stream=stream,
+                                                   **{name: tensor.data_ptr() for name, tensor in feature_sums.items()})
+                        features_done += batch
+                    hit_count = feature_sums["hits"]
+                    for feature in features:
+                        if feature == "depth":   # mean distance of the samples that hit something, 0 where none did
+                            depth = torch.where(hit_count > 0, feature_sums["depth"] / hit_count.clamp(min=1.0), torch.zeros_like(hit_count))
+                            planes = depth.unsqueeze(-1).expand(height, width, 3).contiguous().cpu().numpy()
+                        else:                    # sum / samples; normals stay unnormalised
+                            planes = (feature_sums[feature] / float(done)).cpu().numpy()
+                        pointer = planes.ctypes.data_as(C.POINTER(C.c_float))
+                        for name in (("auto-%s.exr" % feature, "auto-%s-%05dspp.exr" % (feature, done)) if checkpoint else ("auto-%s.exr" % feature,)):
+                            path = os.path.join(out_dir, name)
+                            if host.pathed_host_write_exr_half_bgr(path.encode(), width, height, pointer) != 0:
+                                raise RuntimeError(host.pathed_host_last_error().decode())
+                            print("Saved exr file. [ %s ] " % path)
             print("[%s] sample: %d/%d (%.1fs elapsed)" % (out_dir, done, spp, elapsed), flush=True)
 
     if world_size > 1:
