@@ -1680,8 +1680,9 @@ struct OracleSceneImpl {
      * those are depends on Embree's traversal order: a container beyond the final opaque hit is reported if it is
      * met first and culled if it is met later.  Here the events of a closest-hit query are the container hits
      * with tnear < t < t(final hit), those of an occlusion query the container hits inside the query interval;
-     * equal t are recorded once (scene.cpp:72-77), and the first two in order of t are used (the reference asserts
-     * there are one or two, volume_helper.cpp:43, 83, 101).
+     * equal t are recorded once (scene.cpp:72-77) with the lowest medium index met there (addEvent), and the
+     * first two in order of t are used (the reference asserts there are one or two, volume_helper.cpp:43, 83,
+     * 101).
      * ====================================================================================================== */
 
     struct VolumeEvent { float t; int medium; };
@@ -1711,9 +1712,12 @@ struct OracleSceneImpl {
         }
     }
 
+    /* Equal t count once; the event's medium is the LOWEST MEDIUM INDEX among the containers hit at that t (two
+     * containers that share a face).  A stated rule rather than "the first one met": the kernels meet hits in tree or
+     * item order (pathed_amd/csrc/volume.h: eventsAdd applies the same rule). */
     static void addEvent(std::vector<VolumeEvent> &events, float t, int medium)
     {
-        for (const VolumeEvent &existing : events) { if (existing.t == t) { return; } }
+        for (VolumeEvent &existing : events) { if (existing.t == t) { existing.medium = std::min(existing.medium, medium); return; } }
         events.push_back({ t, medium });
     }
 

@@ -11,7 +11,8 @@
 // an intersection filter that records (t, medium) for every container hit Embree REPORTS (src/scene.cpp:42-83);
 // which hits those are depends on Embree's traversal order.  Here, as in the oracle, the events of a closest-hit
 // query are the container hits with tnear < t < t(final hit), those of an occlusion query the ones inside the query
-// interval; equal t count once, the two nearest are used (the reference asserts there are one or two).
+// interval; equal t count once (lowest medium index: eventsAdd), the two nearest are used (the reference asserts
+// there are one or two).
 #pragma once
 
 #include "shading.h"
@@ -42,10 +43,13 @@ __device__ inline void eventsClear(VolumeEvents &e)
     e.containerT = 0.f; e.containerU = 0.f; e.containerV = 0.f; e.containerPrim = -1;
 }
 
+// Equal t count once, and the event's medium is the LOWEST MEDIUM INDEX among the containers hit at that t (two
+// containers that share a face): a rule that does not depend on the order hits are met in, which differs between the
+// tree walk, the all-triangles intersector and the builders.  The oracle's addEvent states the same rule.
 __device__ inline void eventsAdd(VolumeEvents &e, float t, int medium)
 {
-    if (e.count >= 1 && t == e.t0) { return; }
-    if (e.count >= 2 && t == e.t1) { return; }
+    if (e.count >= 1 && t == e.t0) { e.m0 = imin(e.m0, medium); return; }
+    if (e.count >= 2 && t == e.t1) { e.m1 = imin(e.m1, medium); return; }
     if (e.count == 0) { e.t0 = t; e.m0 = medium; e.count = 1; return; }
     if (t < e.t0) { e.t1 = e.t0; e.m1 = e.m0; e.t0 = t; e.m0 = medium; e.count = 2; return; }
     if (e.count == 1 || t < e.t1) { e.t1 = t; e.m1 = medium; e.count = 2; }
