@@ -415,6 +415,37 @@ int pathed_hip_render_features_device(PathedScene *scene, uint64_t seed, uint32_
 int pathed_hip_render_features(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
                                float *albedo, float *normal, float *depth, float *hits);
 
+/* Heterogeneous media: the reference's GridMedium (src/grid_medium.cpp), a voxel grid of extinction densities that is
+ * looked up trilinearly and walked cell by cell (pathed_amd/csrc/grid_medium.h).  PathedSceneDesc and PathedMedium do not
+ * know it: a grid is set on a medium slot of a CREATED scene.
+ *   cells_*          grid points per axis, each >= 2 (UniformGrid; cells_x * cells_y * cells_z < 2^31)
+ *   bounds           min x, y, z, max x, y, z of the grid's box in MODEL space (the .vol file's order), max > min
+ *   data             cells_x * cells_y * cells_z floats, index = (z * cells_y + y) * cells_x + x; host memory, copied
+ *   albedo, scale    GridMedium's: sigma_t = density * scale, sigma_s = sigma_t * albedo
+ *   world_to_model   row-major 4x4 and its inverse (the scene file's "transform" is model_to_world)
+ * pathed_hip_scene_set_grid_medium turns medium slot `medium_index` into a grid medium (its sigma_t / sigma_s are ignored
+ * from then on); called again on the same slot it replaces the grid.  It uploads the grid and rebuilds nothing else.
+ * PATHED_E_INVALID: index out of range or a scene without media, cells < 2, bounds or data not finite, struct_size wrong.
+ * A scene with a grid renders as PATHED_INTEGRATOR_VOLUME_PATH_TRACER only; every other render or feature call returns
+ * PATHED_E_UNSUPPORTED. */
+typedef struct PathedGridMedium {
+    uint32_t struct_size;   /* sizeof(PathedGridMedium) */
+    uint32_t cells_x, cells_y, cells_z;
+    float bounds[6];
+    const float *data;
+    float albedo;
+    float scale;
+    float world_to_model[16];
+    float model_to_world[16];
+} PathedGridMedium;
+int pathed_hip_scene_set_grid_medium(PathedScene *scene, int medium_index, const PathedGridMedium *grid);
+
+/* Test hook onto the grid code: for each of n segments (a, b: n * 3 floats each, world space, host memory) one thread runs
+ * GridMedium::transmittance(a, b) and GridMedium::findTransmittance(a, b, target) on the grid of medium slot `medium_index`:
+ * transmittance[i], and distance[i] (-1 where the reference's result is invalid). */
+int pathed_hip_grid_queries(PathedScene *scene, int medium_index, size_t n, const float *a, const float *b, const float *target,
+                            float *transmittance, float *distance);
+
 /* Test hook onto the intersector that stands in for Embree.
  * rays: n * 8 floats (ox,oy,oz,tnear, dx,dy,dz,tfar), host memory.
  * any_hit == 0: closest hit (rtcIntersect1, reference src/scene.cpp:91-117):

@@ -65,6 +65,21 @@ class PathedMedium(C.Structure):
     _fields_ = [("sigma_t", C.c_float * 3), ("sigma_s", C.c_float * 3)]
 
 
+class PathedGridMedium(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("cells_x", C.c_uint32),
+        ("cells_y", C.c_uint32),
+        ("cells_z", C.c_uint32),
+        ("bounds", C.c_float * 6),
+        ("data", C.POINTER(C.c_float)),
+        ("albedo", C.c_float),
+        ("scale", C.c_float),
+        ("world_to_model", C.c_float * 16),
+        ("model_to_world", C.c_float * 16),
+    ]
+
+
 class PathedEnvLight(C.Structure):
     _fields_ = [
         ("width", C.c_int32),
@@ -189,6 +204,8 @@ HIP_SYMBOLS = [
     "pathed_hip_scene_create_ex",
     "pathed_hip_scene_device",
     "pathed_hip_scene_set_camera",
+    "pathed_hip_scene_set_grid_medium",
+    "pathed_hip_grid_queries",
     "pathed_hip_scene_destroy",
     "pathed_hip_render",
     "pathed_hip_render_device",
@@ -262,6 +279,11 @@ def load_hip():
     lib.pathed_hip_scene_device.restype = C.c_int
     lib.pathed_hip_scene_set_camera.argtypes = [vp, C.POINTER(PathedCamera)]
     lib.pathed_hip_scene_set_camera.restype = C.c_int
+    if hasattr(lib, "pathed_hip_scene_set_grid_medium"):   # (PATHED_HIP_LIB may name an older build of the same ABI: tools/rates.py --lib)
+        lib.pathed_hip_scene_set_grid_medium.argtypes = [vp, C.c_int, C.POINTER(PathedGridMedium)]
+        lib.pathed_hip_scene_set_grid_medium.restype = C.c_int
+        lib.pathed_hip_grid_queries.argtypes = [vp, C.c_int, C.c_size_t] + [C.POINTER(C.c_float)] * 5
+        lib.pathed_hip_grid_queries.restype = C.c_int
     lib.pathed_hip_measure_valu.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.pathed_hip_measure_valu.restype = C.c_int
     lib.pathed_hip_measure_valu_modes.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
@@ -351,6 +373,10 @@ def load_host():
     lib.pathed_host_scene_desc.restype = C.POINTER(PathedSceneDesc)
     lib.pathed_host_free_scene.argtypes = [C.c_void_p]
     lib.pathed_host_free_scene.restype = None
+    lib.pathed_host_scene_grid_count.argtypes = [C.c_void_p]
+    lib.pathed_host_scene_grid_count.restype = C.c_int
+    lib.pathed_host_scene_grid.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.pathed_host_scene_grid.restype = C.POINTER(PathedGridMedium)
     lib.pathed_host_last_error.argtypes = []
     lib.pathed_host_last_error.restype = C.c_char_p
     if hasattr(lib, "pathed_host_run_job"):

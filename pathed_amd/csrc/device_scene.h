@@ -115,6 +115,9 @@ struct DScene {
     const struct DMedium *media;
     const int *primMedium;     // per primitive (triangles, then spheres): its surface's internal medium, -1 none
     int nMedia;
+    // voxel-grid media (grid_medium.h): one record per grid, and the cells of all grids in one array
+    const struct DGrid *grids;
+    const float *gridData;
 };
 
 // path state word (rayD.w)

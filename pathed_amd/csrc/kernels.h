@@ -3059,8 +3059,12 @@ __device__ __forceinline__ void volumeQueryPairSmall(const VolumeContext<Materia
 #ifndef PATHED_VOLUME_WAVES
 #define PATHED_VOLUME_WAVES 4   // 128 registers per lane + scratch; 3 / 4 / 5 waves: 787 / 845 / 799 (Cornell), 732 / 787 / 707 (cornell-medium), 368 / 388 / 382 (teapot) Msamples/s; uncapped the kernel takes 220-260 registers and runs one or two waves; with one pass per vertex (round 3) 3 / 4 waves: 1 139 / 1 225 (Cornell), 901 / 985 (cornell-medium)
 #endif
-template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS = TraitsAll, bool QUADS = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_volume(RenderParams p, SmallTris smallTris)
+// The kernel's body.  GRID: media of kind kMediumGrid exist (grid_medium.h); the instantiations without it contain no grid code and
+// are the kernels of scenes without a grid (k_path_volume), those with it are k_path_volume_grid.  A medium is read in three
+// places: the segment transmittance of the bounce loop, rayTransmission / the shadow transmittance of scatter, and scatter's
+// distance sample -- `transmit`, `transmission` and the head of `scatter` below.
+template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS, bool QUADS, bool GRID>
+__device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTris &smallTris)
 {
     extern __shared__ float4 ldsRaw[];
     // LDS: [STACK + 1][kBlock] traversal stack rows, then (LDS_MATERIALS) the material table
@@ -3088,6 +3092,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
     auto query = [&](int mode, V3 origin, V3 direction, float tfar, RayHit *hit, VolumeEvents *events) -> bool {
         if constexpr (SMALL) { return volumeQuerySmall<QUADS>(context, (const f2 *)smallTris.data, p.smallQuads, p.smallKappaT, mode, origin, direction, tfar, hit, events); }
         else { return volumeQuery<STACK>(context, mode, origin, direction, tfar, hit, events); }
+    };
+
+    // Medium::transmittance of medium `index` (HomogeneousMedium or GridMedium), and VolumeHelper::rayTransmission over it
+    auto transmit = [&](int index, V3 pointA, V3 pointB) -> Rgb {
+        if constexpr (GRID) {
+            const DMedium &record = context.media[index];
+            if (record.kind == kMediumGrid) {
+                const float channel = gridTransmittance(scene.grids[record.grid], scene.gridData, pointA, pointB);
+                return rgb(channel, channel, channel);
+            }
+        }
+        return mediumTransmittance(context.media[index], pointA, pointB);
+    };
+    auto transmission = [&](V3 origin, V3 direction, const VolumeEvents &events, int medium) -> Rgb {
+        if constexpr (GRID) { return rayTransmissionOver(transmit, origin, direction, events, medium); }
+        else { return rayTransmission(context.media, origin, direction, events, medium); }
     };
 
     // The reference traces the ray (vertex, BSDF sample) twice: directSampleBSDF asks for the nearest NON-container surface
@@ -3158,7 +3178,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
         // directSampleLights, :74-134, from its occlusion query on
         auto finishLight = [&]() -> Rgb {
             if (!wantShadow || occluded) { return rgb(0.f); }
-            const Rgb transmittance = rayTransmission(context.media, isect.point, wiWorld, events, medium);
+            const Rgb transmittance = transmission(isect.point, wiWorld, events, medium);
             float pdf;
             if (surfaceSample.solidAngle) {
                 pdf = 1.f / invPDF;
@@ -3255,13 +3275,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
     // (src/volume_path_tracer.cpp:114-131, src/homogeneous_medium.cpp:36-66, src/volume_helper.cpp:12-69)
     auto scatter = [&](int medium, V3 entry, V3 exitPoint, Rng &random) -> Rgb {
         if (medium < 0) { return rgb(0.f); }
-        const float sigmaT = context.media[medium].sigmaT[0];
-        const V3 travel = exitPoint - entry;
-        const float distance = length(travel);
-        const float xi = random.next();
-        const float sampleT = -logf(1 - xi) / sigmaT;
-        if (sampleT >= distance) { return rgb(0.f); }
-        const V3 samplePoint = entry + normalized(travel) * sampleT;
+        V3 samplePoint;
+        bool gridMedium = false;
+        if constexpr (GRID) {
+            // GridMedium::integrate, src/grid_medium.cpp:170-198
+            const DMedium &record = context.media[medium];
+            gridMedium = record.kind == kMediumGrid;
+            if (gridMedium && !gridSamplePoint(scene.grids[record.grid], scene.gridData, entry, exitPoint, random, &samplePoint)) { return rgb(0.f); }
+        }
+        if (!gridMedium) {
+            const float sigmaT = context.media[medium].sigmaT[0];
+            const V3 travel = exitPoint - entry;
+            const float distance = length(travel);
+            const float xi = random.next();
+            const float sampleT = -logf(1 - xi) / sigmaT;
+            if (sampleT >= distance) { return rgb(0.f); }
+            samplePoint = entry + normalized(travel) * sampleT;
+        }
         if (scene.nLights == 0) { return rgb(0.f); }
         const int lightCount = scene.nLights;
         int lightIndex = (int)floorf(random.next() * lightCount);
@@ -3303,8 +3333,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
         }
         const V3 lightWo = -normalized(sampleDirection);
         Rgb shadowTransmittance = rgb(0.f);
-        if (events.count == 1) { shadowTransmittance = mediumTransmittance(context.media[medium], samplePoint, samplePoint + wiWorld * events.t0); }
-        else if (events.count >= 2) { shadowTransmittance = mediumTransmittance(context.media[medium], samplePoint + wiWorld * events.t0, samplePoint + wiWorld * events.t1); }
+        if (events.count == 1) { shadowTransmittance = transmit(medium, samplePoint, samplePoint + wiWorld * events.t0); }
+        else if (events.count >= 2) { shadowTransmittance = transmit(medium, samplePoint + wiWorld * events.t0, samplePoint + wiWorld * events.t1); }
         Rgb emitted;
         if (TRAITS::env && light.kind == 2) { emitted = envEmit(scene.env, lightWo); }
         else { emitted = matEmit(materials[lightMaterial]); }
@@ -3336,7 +3366,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
                 RayHit through;
                 SHADE_REGION(8, true);   // what is seen through a container
                 const bool found = query(kQueryVolumeClosest, rayOrigin, rayDirection, PATHED_TFAR, &through, &events);
-                const Rgb transmittance = rayTransmission(context.media, rayOrigin, rayDirection, events, -1);
+                const Rgb transmittance = transmission(rayOrigin, rayDirection, events, -1);
                 if (found) { color = color + matEmit(materials[primMaterial(context, through.prim)]) * transmittance; }
                 else { color = color + environmentL<TRAITS>(scene, rayDirection) * transmittance; }
             }
@@ -3378,7 +3408,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
             random.dimension = mediumBase(bounce);
             const Rgb Ls = scatter(medium, last.point, next.point, random);
             result = result + Ls * modulation;
-            if (medium >= 0) { modulation = modulation * mediumTransmittance(context.media[medium], last.point, next.point); }
+            if (medium >= 0) { modulation = modulation * transmit(medium, last.point, next.point); }
             else { modulation = modulation * rgb(1.f); }
             if (isBlack(modulation)) { break; }
 
@@ -3421,6 +3451,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
         }
     }
     (void)samplesDone;
+}
+
+template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS = TraitsAll, bool QUADS = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_volume(RenderParams p, SmallTris smallTris)
+{
+    pathVolume<LDS_MATERIALS, STACK, SMALL, TRAITS, QUADS, false>(p, smallTris);
+}
+
+// ... of scenes with a voxel-grid medium (pathed_hip_scene_set_grid_medium): generic traits, pair-of-triangles phase 1, the
+// material table read from memory; SMALL (the all-triangles intersector) or the tree walk with STACK rows
+template <int STACK, bool SMALL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_volume_grid(RenderParams p, SmallTris smallTris)
+{
+    pathVolume<false, STACK, SMALL, TraitsAll, false, true>(p, smallTris);
 }
 
 // ------------------------------------------------------------------------- scene set-up

@@ -209,6 +209,13 @@ struct PathedScene {
     DeviceBuffer<float4> thetaRecords, phiRecords;
     DeviceBuffer<DMedium> media;
     DeviceBuffer<int> primMedium;
+    // voxel-grid media (grid_medium.h; pathed_hip_scene_set_grid_medium): the records, every grid's cells, and the host copies
+    // the device arrays are rebuilt from when a grid is set or replaced
+    DeviceBuffer<DGrid> grids;
+    DeviceBuffer<float> gridData;
+    std::vector<DMedium> mediaHost;
+    std::vector<DGrid> gridsHost;
+    std::vector<std::vector<float>> gridCells;   // per grid
     DeviceBuffer<int> volumeOverflow;   // the volume kernel's traversal-stack spill, per thread
 
     // render state, allocated on first use
@@ -1788,6 +1795,7 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
         }
         for (uint32_t i = 0; i < desc->n_materials; i++) { scene->hasContainers = scene->hasContainers || desc->materials[i].type == PATHED_MAT_PASSTHROUGH; }
         if ((status = scene->media.upload(media)) != hipSuccess) { return fail_cleanup(status, "upload media"); }
+        scene->mediaHost = media;
         if ((status = scene->primMedium.upload(primMedium)) != hipSuccess) { return fail_cleanup(status, "upload media"); }
     }
     if ((status = scene->envRgba.upload(envRgba)) != hipSuccess) { return fail_cleanup(status, "upload env map"); }
@@ -2246,7 +2254,24 @@ static int renderPassVolume(PathedScene *scene, const Pass &pass)
         const auto run = [&](void (*kernel)(RenderParams, SmallTris)) {
             hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, quads ? scene->smallItems : scene->smallTris);
         };
-        if (small && ldsMaterials && scene->traits.lambertianGlassContainer) {   // the reference's own volume scene kinds
+        if (!scene->gridsHost.empty()) {
+            // a voxel-grid medium: the generic set, pair-of-triangles phase 1, the material table read from memory (four
+            // instantiations in all; params.smallQuads is 0 where no instantiation reads the item records)
+            params.smallQuads = 0;
+            params.scene.leafTris = scene->leafTris.ptr;
+            const size_t gridLds = (size_t)((small ? 8 : scene->stackRows) + 1) * kBlock * sizeof(int);
+            const auto runGrid = [&](void (*kernel)(RenderParams, SmallTris)) {
+                hipLaunchKernelGGL(kernel, grid, dim3(kBlock), gridLds, stream, params, scene->smallTris);
+            };
+            if (small) { runGrid(k_path_volume_grid<8, true>); }
+            else {
+                switch (scene->stackRows) {
+                case 8: runGrid(k_path_volume_grid<8, false>); break;
+                case 16: runGrid(k_path_volume_grid<16, false>); break;
+                default: runGrid(k_path_volume_grid<22, false>); break;
+                }
+            }
+        } else if (small && ldsMaterials && scene->traits.lambertianGlassContainer) {   // the reference's own volume scene kinds
             withBool(quads, [&](auto QUADS) { run(k_path_volume<true, 8, true, TraitsLambertianGlassContainer, QUADS>); });
         } else if (quads) {
             run(k_path_volume<true, 8, true, TraitsAll, true>);
@@ -2616,12 +2641,16 @@ int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
     if (scene->integrator == PATHED_INTEGRATOR_ALBEDO) {
         // AlbedoIntegrator::L never looks at the bounce window: last_bounce is ignored, start_bounce decides bounce 0's emission
         if (scene->hasContainers) { return fail(PATHED_E_UNSUPPORTED, "the albedo integrator does not render scenes with passthrough (medium container) surfaces"); }
+        if (!scene->gridsHost.empty()) { return fail(PATHED_E_UNSUPPORTED, "a scene with a voxel-grid medium renders with the VolumePathTracer integrator only"); }
         SELECT_DEVICE(scene);
         FeatureBuffers none = { nullptr, nullptr, nullptr, nullptr };
         return launchFeatures(scene, seed, spp_begin, spp_count, start_bounce, -1, true, d_accum_rgb_sum, none, (hipStream_t)stream_handle);
     }
     if (scene->hasContainers && scene->integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER) {
         return fail(PATHED_E_UNSUPPORTED, "the scene has passthrough (medium container) surfaces: select the VolumePathTracer integrator (pathed_hip_set_integrator)");
+    }
+    if (!scene->gridsHost.empty() && scene->integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER) {
+        return fail(PATHED_E_UNSUPPORTED, "a scene with a voxel-grid medium renders with the VolumePathTracer integrator only (pathed_hip_set_integrator)");
     }
     SELECT_DEVICE(scene);
     scene->lastCallFeatures = false;
@@ -2751,6 +2780,7 @@ int pathed_hip_render_features_device(PathedScene *scene, uint64_t seed, uint32_
     if (spp_count == 0) { return PATHED_OK; }
     if ((uint64_t)spp_begin + spp_count > 0x7fffffffull) { return fail(PATHED_E_INVALID, "sample index overflow"); }
     if (scene->hasContainers) { return fail(PATHED_E_UNSUPPORTED, "feature images do not cover scenes with passthrough (medium container) surfaces"); }
+    if (!scene->gridsHost.empty()) { return fail(PATHED_E_UNSUPPORTED, "feature images do not cover scenes with a voxel-grid medium"); }
     SELECT_DEVICE(scene);
     const FeatureBuffers out = { buffers->albedo_sum, buffers->normal_sum, buffers->depth_sum, buffers->hit_count };
     return launchFeatures(scene, seed, spp_begin, spp_count, 0, -1, false, nullptr, out, (hipStream_t)stream_handle);
@@ -2836,6 +2866,106 @@ int pathed_hip_trace(PathedScene *scene, const float *rays, size_t n, int any_hi
     if (deviceOccluded) { (void)hipFree(deviceOccluded); }
     if (deviceOverflow) { (void)hipFree(deviceOverflow); }
     if (status != hipSuccess) { return fail(PATHED_E_DEVICE, hipGetErrorString(status)); }
+    return PATHED_OK;
+}
+
+int pathed_hip_scene_set_grid_medium(PathedScene *scene, int medium_index, const PathedGridMedium *grid)
+{
+    if (!scene || !grid) { return fail(PATHED_E_INVALID, "null scene or grid"); }
+    if (grid->struct_size != sizeof(PathedGridMedium)) { return fail(PATHED_E_INVALID, "PathedGridMedium.struct_size does not match this library"); }
+    if (scene->mediaHost.empty()) { return fail(PATHED_E_INVALID, "the scene has no media: a grid is set on a medium slot of the scene description"); }
+    if (medium_index < 0 || (size_t)medium_index >= scene->mediaHost.size()) { return fail(PATHED_E_INVALID, "grid medium: medium index out of range"); }
+    if (grid->cells_x < 2 || grid->cells_y < 2 || grid->cells_z < 2) { return fail(PATHED_E_INVALID, "grid medium: a grid needs at least 2 cells on every axis"); }
+    const unsigned long long cellCount = (unsigned long long)grid->cells_x * grid->cells_y * grid->cells_z;
+    if (grid->cells_x >= (1u << 20) || grid->cells_y >= (1u << 20) || grid->cells_z >= (1u << 20) || cellCount >= (1ull << 31)) {
+        return fail(PATHED_E_INVALID, "grid medium: too many cells (the product must stay below 2^31)");
+    }
+    if (!grid->data) { return fail(PATHED_E_INVALID, "grid medium: data missing"); }
+    for (int k = 0; k < 6; k++) {
+        if (!std::isfinite(grid->bounds[k])) { return fail(PATHED_E_INVALID, "grid medium: bounds must be finite"); }
+    }
+    for (int k = 0; k < 3; k++) {
+        if (!(grid->bounds[k + 3] > grid->bounds[k])) { return fail(PATHED_E_INVALID, "grid medium: bounds must be (min x, y, z, max x, y, z) with max > min"); }
+    }
+    if (!std::isfinite(grid->albedo) || !std::isfinite(grid->scale)) { return fail(PATHED_E_INVALID, "grid medium: albedo and scale must be finite"); }
+    for (int k = 0; k < 16; k++) {
+        if (!std::isfinite(grid->world_to_model[k]) || !std::isfinite(grid->model_to_world[k])) { return fail(PATHED_E_INVALID, "grid medium: the transform must be finite"); }
+    }
+    for (unsigned long long i = 0; i < cellCount; i++) {
+        if (!std::isfinite(grid->data[i])) { return fail(PATHED_E_INVALID, "grid medium: data must be finite"); }
+    }
+    SELECT_DEVICE(scene);
+
+    DGrid record;
+    std::memset(&record, 0, sizeof record);
+    record.cellsX = (int)grid->cells_x; record.cellsY = (int)grid->cells_y; record.cellsZ = (int)grid->cells_z;
+    record.minX = grid->bounds[0]; record.minY = grid->bounds[1]; record.minZ = grid->bounds[2];
+    record.maxX = grid->bounds[3]; record.maxY = grid->bounds[4]; record.maxZ = grid->bounds[5];
+    record.widthX = record.maxX - record.minX;   // GridInfo::widthX, include/uniform_grid.h:22-24
+    record.widthY = record.maxY - record.minY;
+    record.widthZ = record.maxZ - record.minZ;
+    record.albedo = grid->albedo;
+    record.scale = grid->scale;
+    std::memcpy(record.worldToModel, grid->world_to_model, sizeof record.worldToModel);
+    std::memcpy(record.modelToWorld, grid->model_to_world, sizeof record.modelToWorld);
+
+    // the new tables, built beside the old ones: a failure leaves the scene as it was
+    std::vector<DMedium> media = scene->mediaHost;
+    std::vector<DGrid> records = scene->gridsHost;
+    std::vector<std::vector<float>> cells = scene->gridCells;
+    int slot;
+    if (media[(size_t)medium_index].kind == kMediumGrid) {
+        slot = media[(size_t)medium_index].grid;   // replace
+    } else {
+        slot = (int)records.size();
+        records.push_back(record);
+        cells.emplace_back();
+        media[(size_t)medium_index].kind = kMediumGrid;
+        media[(size_t)medium_index].grid = slot;
+    }
+    records[(size_t)slot] = record;
+    cells[(size_t)slot].assign(grid->data, grid->data + cellCount);
+    std::vector<float> all;
+    for (size_t g = 0; g < records.size(); g++) {
+        if (all.size() + cells[g].size() >= ((size_t)1 << 32)) { return fail(PATHED_E_INVALID, "grid medium: the scene's grids hold more than 2^32 cells"); }
+        records[g].dataOffset = (unsigned int)all.size();
+        all.insert(all.end(), cells[g].begin(), cells[g].end());
+    }
+    HIP_TRY(hipDeviceSynchronize());   // nothing of this scene runs (render calls return when they have completed); other streams of the caller may
+    HIP_TRY(scene->grids.upload(records));
+    HIP_TRY(scene->gridData.upload(all));
+    HIP_TRY(hipMemcpy(scene->media.ptr, media.data(), media.size() * sizeof(DMedium), hipMemcpyHostToDevice));
+    scene->mediaHost.swap(media);
+    scene->gridsHost.swap(records);
+    scene->gridCells.swap(cells);
+    scene->device.grids = scene->grids.ptr;
+    scene->device.gridData = scene->gridData.ptr;
+    return PATHED_OK;
+}
+
+int pathed_hip_grid_queries(PathedScene *scene, int medium_index, size_t n, const float *a, const float *b, const float *target,
+                            float *transmittance, float *distance)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (medium_index < 0 || (size_t)medium_index >= scene->mediaHost.size() || scene->mediaHost[(size_t)medium_index].kind != kMediumGrid) {
+        return fail(PATHED_E_INVALID, "grid queries: the medium slot holds no grid");
+    }
+    if (n == 0) { return PATHED_OK; }
+    if (!a || !b || !target || !transmittance || !distance) { return fail(PATHED_E_INVALID, "null segment or result buffer"); }
+    if (n > (size_t)1 << 24) { return fail(PATHED_E_INVALID, "too many segments in one call"); }
+    SELECT_DEVICE(scene);
+    DeviceBuffer<float> deviceA, deviceB, deviceTarget, deviceTransmittance, deviceDistance;
+    HIP_TRY(deviceA.upload(std::vector<float>(a, a + 3 * n)));
+    HIP_TRY(deviceB.upload(std::vector<float>(b, b + 3 * n)));
+    HIP_TRY(deviceTarget.upload(std::vector<float>(target, target + n)));
+    HIP_TRY(deviceTransmittance.allocate(n));
+    HIP_TRY(deviceDistance.allocate(n));
+    hipLaunchKernelGGL(k_grid_queries, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, scene->grids.ptr, scene->gridData.ptr,
+                       scene->mediaHost[(size_t)medium_index].grid, (int)n, deviceA.ptr, deviceB.ptr, deviceTarget.ptr, deviceTransmittance.ptr, deviceDistance.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(transmittance, deviceTransmittance.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(distance, deviceDistance.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
     return PATHED_OK;
 }
 

@@ -15,6 +15,7 @@
 // there are one or two).
 #pragma once
 
+#include "grid_medium.h"
 #include "shading.h"
 #include "trace.h"
 
@@ -23,8 +24,10 @@ namespace pathed {
 struct DMedium {
     float sigmaT[3];
     float sigmaS[3];
-    float pad[2];
+    int kind;    // kMediumHomogeneous (0) or kMediumGrid (grid_medium.h): a grid medium ignores the two sigmas
+    int grid;    // ... and this is its record in DScene::grids
 };
+static_assert(sizeof(DMedium) == 32, "DMedium is 32 bytes");
 
 // the two nearest distinct-t events met so far
 struct VolumeEvents {
@@ -200,6 +203,22 @@ __device__ inline Rgb rayTransmission(const DMedium *media, V3 o, V3 d, const Vo
     } else {
         if (events.count >= 2) { transmittance = transmittance * mediumTransmittance(media[events.m0], o + d * events.t0, o + d * events.t1); }
         else { transmittance = transmittance * mediumTransmittance(media[events.m0], o, o + d * events.t0); }
+    }
+    return transmittance;
+}
+
+// ... over media of either kind: transmit(index, a, b) is Medium::transmittance of medium `index` (kernels.h: pathVolume<GRID>)
+template <typename Transmit>
+__device__ inline Rgb rayTransmissionOver(const Transmit &transmit, V3 o, V3 d, const VolumeEvents &events, int medium)
+{
+    Rgb transmittance = rgb(1.f);
+    if (events.count == 0) { return transmittance; }
+    if (medium >= 0) {
+        if (events.count == 1) { transmittance = transmittance * transmit(medium, o, o + d * events.t0); }
+        else { transmittance = transmittance * transmit(medium, o + d * events.t0, o + d * events.t1); }
+    } else {
+        if (events.count >= 2) { transmittance = transmittance * transmit(events.m0, o + d * events.t0, o + d * events.t1); }
+        else { transmittance = transmittance * transmit(events.m0, o, o + d * events.t0); }
     }
     return transmittance;
 }

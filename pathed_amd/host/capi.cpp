@@ -41,6 +41,22 @@ const PathedSceneDesc *pathed_host_scene_desc(void *handle)
     return &((LoadedScene *)handle)->desc;
 }
 
+// the voxel-grid media of a loaded scene (scene_loader.h: FlatGrid): how many, and grid i with the medium slot it belongs to
+int pathed_host_scene_grid_count(void *handle)
+{
+    if (!handle) { return 0; }
+    return (int)((LoadedScene *)handle)->scene.grids.size();
+}
+
+const PathedGridMedium *pathed_host_scene_grid(void *handle, int index, int *mediumIndex)
+{
+    if (!handle) { return nullptr; }
+    const pathed::FlatScene &scene = ((LoadedScene *)handle)->scene;
+    if (index < 0 || (size_t)index >= scene.grids.size()) { return nullptr; }
+    if (mediumIndex) { *mediumIndex = scene.grids[(size_t)index].medium; }
+    return scene.gridDesc((size_t)index);
+}
+
 void pathed_host_free_scene(void *handle)
 {
     delete (LoadedScene *)handle;
@@ -105,8 +121,9 @@ int pathed_host_parse_mtl(const char *path, char *out, size_t capacity)
 #include <thread>
 
 // FNV-1a over everything of a loaded scene that a radiance sum depends on (the camera's resolution is in the state header)
-static std::string flatSceneDigest(const PathedSceneDesc &desc)
+static std::string flatSceneDigest(const pathed::FlatScene &flat)
 {
+    const PathedSceneDesc desc = flat.desc();
     unsigned long long hash = 1469598103934665603ull;
     auto add = [&](const void *data, size_t bytes) {
         const unsigned char *p = static_cast<const unsigned char *>(data);
@@ -137,6 +154,14 @@ static std::string flatSceneDigest(const PathedSceneDesc &desc)
         add(desc.textures[i].rgb, (size_t)3 * desc.textures[i].width * desc.textures[i].height);
     }
     add(desc.media, sizeof(PathedMedium) * desc.n_media);
+    for (const pathed::FlatGrid &grid : flat.grids) {   // the .vol file's bytes as loaded, and what the scene file says about the medium
+        add(&grid.medium, sizeof grid.medium);
+        add(&grid.desc.cells_x, sizeof(uint32_t)); add(&grid.desc.cells_y, sizeof(uint32_t)); add(&grid.desc.cells_z, sizeof(uint32_t));
+        add(grid.desc.bounds, sizeof grid.desc.bounds);
+        add(&grid.desc.albedo, sizeof(float)); add(&grid.desc.scale, sizeof(float));
+        add(grid.desc.world_to_model, sizeof grid.desc.world_to_model); add(grid.desc.model_to_world, sizeof grid.desc.model_to_world);
+        add(grid.data.data(), sizeof(float) * grid.data.size());
+    }
     char text[32];
     snprintf(text, sizeof text, "%016llx", hash);
     return text;
@@ -179,7 +204,7 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
         struct CommGuard { PathedComm *&comm; ~CommGuard() { if (comm) { pathed_hip_comm_destroy(comm); } } } commGuard{ earlyComm };
         const auto loadBegin = std::chrono::steady_clock::now();
         FlatScene flat = loadScene(job.scene(), width, height, assetRoot);
-        const std::string sceneDigest = flatSceneDigest(flat.desc());
+        const std::string sceneDigest = flatSceneDigest(flat);
         if (builder == "auto") {
             // several replicas of a large mesh: each GPU builds its own tree in milliseconds (PLOC) instead of N host SAH
             // builds competing for the cores before the first sample (include/pathed_hip.h: PATHED_BVH_*)

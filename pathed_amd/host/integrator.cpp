@@ -134,6 +134,7 @@ void Scene::upload(int bvhBuilderPlusOne)
 {
     m_handles.assign(m_devices.size(), nullptr);
     const PathedSceneDesc desc = m_flat.desc();
+    for (size_t i = 0; i < m_flat.grids.size(); i++) { (void)m_flat.gridDesc(i); }   // (sets the data pointers once, before the replica threads read them)
     try {
         // every device builds / uploads its own replica, in parallel
         ReplicaWorkers workers(m_devices.size());
@@ -145,6 +146,11 @@ void Scene::upload(int bvhBuilderPlusOne)
             options.bvh_builder = bvhBuilderPlusOne;
             if (pathed_hip_scene_create_ex(&desc, &options, &m_handles[r]) != PATHED_OK) {
                 throw std::runtime_error(hipError("pathed_hip_scene_create_ex"));
+            }
+            for (size_t i = 0; i < m_flat.grids.size(); i++) {   // the scene file's voxel-grid media, each on its medium slot
+                if (pathed_hip_scene_set_grid_medium(m_handles[r], m_flat.grids[i].medium, m_flat.gridDesc(i)) != PATHED_OK) {
+                    throw std::runtime_error(hipError("pathed_hip_scene_set_grid_medium"));
+                }
             }
         });
     } catch (...) {

@@ -840,6 +840,53 @@ PathedMaterial makeLambertian(const float diffuse[3], const float emit[3])
     return material;
 }
 
+const PathedGridMedium *FlatScene::gridDesc(size_t i) const
+{
+    FlatGrid &grid = const_cast<FlatScene *>(this)->grids[i];
+    grid.desc.struct_size = (uint32_t)sizeof(PathedGridMedium);
+    grid.desc.data = grid.data.data();   // valid after the FlatScene has been copied or moved
+    return &grid.desc;
+}
+
+// VolParser::parse, src/vol_parser.cpp:10-58, with the checks it lacks
+VolFile readVolFile(const std::string &path)
+{
+    std::ifstream stream(path, std::ifstream::binary);
+    if (!stream) { throw SceneLoadError("vol: cannot open " + path); }
+    stream.seekg(0, std::ios::end);
+    const unsigned long long length = (unsigned long long)stream.tellg();
+    stream.seekg(0, std::ios::beg);
+
+    const unsigned long long headerBytes = 3 + 1 + 5 * sizeof(uint32_t) + 6 * sizeof(float);
+    if (length < headerBytes) { throw SceneLoadError("vol: " + path + " is shorter than the 48-byte header"); }
+    char header[3];
+    stream.read(header, 3);
+    if (header[0] != 'V' || header[1] != 'O' || header[2] != 'L') { throw SceneLoadError("vol: " + path + " does not start with \"VOL\""); }
+    char version;
+    stream.read(&version, sizeof version);
+    uint32_t encoding, channels;
+    VolFile vol;
+    stream.read(reinterpret_cast<char *>(&encoding), sizeof encoding);
+    stream.read(reinterpret_cast<char *>(vol.cells), sizeof vol.cells);
+    stream.read(reinterpret_cast<char *>(&channels), sizeof channels);
+    if (channels != 1) { throw SceneLoadError("vol: " + path + " has " + std::to_string(channels) + " channels; a density grid has 1"); }
+    stream.read(reinterpret_cast<char *>(vol.bounds), sizeof vol.bounds);
+
+    for (int k = 0; k < 3; k++) {
+        if (vol.cells[k] == 0 || vol.cells[k] >= (1u << 20)) { throw SceneLoadError("vol: " + path + " has an implausible cell count"); }
+    }
+    const unsigned long long count = (unsigned long long)vol.cells[0] * vol.cells[1] * vol.cells[2];
+    if (length != headerBytes + count * sizeof(float)) {
+        throw SceneLoadError("vol: " + path + " is " + std::to_string(length) + " bytes long; its header announces "
+                             + std::to_string(vol.cells[0]) + " x " + std::to_string(vol.cells[1]) + " x " + std::to_string(vol.cells[2])
+                             + " cells, " + std::to_string(headerBytes + count * sizeof(float)) + " bytes");
+    }
+    vol.data.resize((size_t)count);
+    stream.read(reinterpret_cast<char *>(vol.data.data()), (std::streamsize)(count * sizeof(float)));
+    if (!stream) { throw SceneLoadError("vol: error reading " + path); }
+    return vol;
+}
+
 PathedSceneDesc FlatScene::desc() const
 {
     PathedSceneDesc d;
@@ -911,12 +958,34 @@ FlatScene loadScene(
         }
     }
 
-    // media: scene_parser.cpp:202-229 (homogeneous only; voxel grids are outside the scope)
+    // media: scene_parser.cpp:202-229
     const Json &media = json["media"];
     if (media.isArray()) {
         for (const Json &mediumJson : media.elements()) {
             const std::string kind = mediumJson["type"].isString() ? mediumJson["type"].asString() : "";
-            if (kind == "heterogeneous") { throw SceneLoadError("Unsupported: heterogeneous (voxel) media are outside the hot-path scope (SURVEY.md §2)"); }
+            if (kind == "heterogeneous") {
+                // :209-220 and VolParser::parse: the medium gets the INVERSE of the parsed transform (vol_parser.cpp:76)
+                if (!mediumJson["name"].isString()) { throw SceneLoadError("media: a medium needs a string \"name\""); }
+                if (!mediumJson["filename"].isString()) { throw SceneLoadError("media: a heterogeneous medium needs a \"filename\""); }
+                FlatGrid grid;
+                std::memset(&grid.desc, 0, sizeof grid.desc);
+                if (!checkFloat(mediumJson["albedo"], &grid.desc.albedo)) { throw SceneLoadError("media: a heterogeneous medium needs a number (string) \"albedo\""); }
+                grid.desc.scale = parseFloatDefault(mediumJson["scale"], 1.f);
+                const Transform transform = parseTransform(mediumJson["transform"]);
+                transform.inverse.toArray(grid.desc.world_to_model);
+                transform.matrix.toArray(grid.desc.model_to_world);
+                VolFile vol = readVolFile(context.resolve(mediumJson["filename"].asString()));
+                grid.desc.cells_x = vol.cells[0]; grid.desc.cells_y = vol.cells[1]; grid.desc.cells_z = vol.cells[2];
+                std::memcpy(grid.desc.bounds, vol.bounds, sizeof vol.bounds);
+                grid.data = std::move(vol.data);
+                grid.medium = (int)scene.media.size();
+                PathedMedium placeholder;   // the slot the grid is set on; its sigmas are ignored from then on
+                std::memset(&placeholder, 0, sizeof placeholder);
+                context.mediumLookup[mediumJson["name"].asString()] = grid.medium;
+                scene.media.push_back(placeholder);
+                scene.grids.push_back(std::move(grid));
+                continue;
+            }
             if (kind != "homogeneous") { continue; }   // the reference ignores unknown kinds
             PathedMedium medium;
             parseColor(mediumJson["sigma_t"], kBlack, medium.sigma_t);

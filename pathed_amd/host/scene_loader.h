@@ -11,6 +11,7 @@
 //   quad         reference src/quad.cpp:7-151
 //   sphere       reference src/sphere.cpp:16-48, src/scene_parser.cpp:484-512
 //   textures     reference src/texture.cpp:12-31 (PNG / PNM here, see image_decode.h)
+//   .vol grids   reference src/vol_parser.cpp:10-80, src/scene_parser.cpp:202-220
 #pragma once
 
 #include "pathed_hip.h"
@@ -21,6 +22,25 @@
 #include <vector>
 
 namespace pathed {
+
+// A "heterogeneous" medium of the scene file: the voxel grid of its .vol file (reference GridMedium).  PathedSceneDesc does not
+// know grids: the slot `medium` of FlatScene::media is a placeholder, and whoever creates the device scene hands the grid
+// over with pathed_hip_scene_set_grid_medium(scene, medium, gridDesc(i)) (host/integrator.cpp: Scene::upload).
+struct FlatGrid {
+    int medium = -1;           // index into FlatScene::media
+    PathedGridMedium desc;     // desc.data is set by FlatScene::gridDesc
+    std::vector<float> data;   // cells_x * cells_y * cells_z, index = (z * cells_y + y) * cells_x + x
+};
+
+// The contents of a .vol file (vol_parser.cpp's layout: "VOL", a version byte, uint32 encoding, cells x / y / z, channels,
+// six float bounds, then the cells as float32).  Throws SceneLoadError on a wrong header, a channel count other than 1, or
+// a length that is not the header plus cells x 4 bytes (the reference checks none of the three).
+struct VolFile {
+    uint32_t cells[3];
+    float bounds[6];
+    std::vector<float> data;
+};
+VolFile readVolFile(const std::string &path);
 
 struct FlatScene {
     PathedCamera camera;
@@ -35,6 +55,7 @@ struct FlatScene {
     std::vector<PathedGeom> geoms;
     std::vector<PathedMaterial> materials;
     std::vector<PathedMedium> media;
+    std::vector<FlatGrid> grids;
 
     bool hasEnv = false;
     PathedEnvLight env;
@@ -47,6 +68,8 @@ struct FlatScene {
 
     // valid as long as this FlatScene is alive and unmodified
     PathedSceneDesc desc() const;
+    // grid i ready for pathed_hip_scene_set_grid_medium (same lifetime rule)
+    const PathedGridMedium *gridDesc(size_t i) const;
 };
 
 struct SceneLoadError : std::runtime_error {

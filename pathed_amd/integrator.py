@@ -70,11 +70,12 @@ class HipScene:
     wave_stragglers, wave_refill, chunks_per_pass, hybrid_batch, hybrid_ready, local_rays, shade_launches, shade_chain, intersector ("auto" | "bvh"),
     trace_blocks_per_cu, shade_kernel ("auto" | "per-slot" | "staged" | "fused" | "split" | "wave" | "hybrid"), stage_slots,
     unit_order ("auto" | "stripes" | "stripes-tiled" | "tiles"), node_format ("auto" | "wide" | "compressed" | "compressed8"), small_phase1 ("auto" | "valu" | "mfma").  `device=None` keeps the device of an earlier pathed_hip_init.
+    `grids`: (medium slot, _capi.PathedGridMedium) pairs set on the created scene (LoadedScene.grids; see set_grid_medium).
     """
 
     BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2}  # PATHED_BVH_SAH_HOST / _LBVH_DEVICE / _PLOC_DEVICE
 
-    def __init__(self, desc_pointer, device=None, bvh_builder="sah", **options):
+    def __init__(self, desc_pointer, device=None, bvh_builder="sah", grids=(), **options):
         self._lib = _capi.load_hip()
         packed = _capi.PathedSceneOptions()
         packed.struct_size = C.sizeof(_capi.PathedSceneOptions)
@@ -99,6 +100,8 @@ class HipScene:
         self.device = int(self._lib.pathed_hip_scene_device(handle))
         self.width = int(desc_pointer.contents.camera.width)
         self.height = int(desc_pointer.contents.camera.height)
+        for medium_index, grid in grids:   # LoadedScene.grids: the voxel-grid media of the scene file
+            self.set_grid_medium(medium_index, grid)
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -212,6 +215,44 @@ class HipScene:
     def set_camera(self, camera):
         """Another view of the same scene (pathed_hip_scene_set_camera): `camera` is a _capi.PathedCamera of the scene's resolution."""
         _check(self._lib, self._lib.pathed_hip_scene_set_camera(self._handle, C.byref(camera)), "pathed_hip_scene_set_camera")
+
+    def set_grid_medium(self, medium_index, grid=None, *, data=None, bounds=None, albedo=1.0, scale=1.0, world_to_model=None, model_to_world=None):
+        """Turn medium slot `medium_index` into a voxel-grid medium (pathed_hip_scene_set_grid_medium), or replace its grid.
+        Either `grid`, a _capi.PathedGridMedium (LoadedScene.grids carries those of a scene file), or `data`, a float array of
+        shape (cells_z, cells_y, cells_x), with `bounds` = (min x, y, z, max x, y, z) and the two row-major 4x4 matrices
+        (identity when absent; one given, the other is its numpy inverse)."""
+        if grid is None:
+            data = np.ascontiguousarray(data, dtype=np.float32)
+            assert data.ndim == 3 and bounds is not None and len(bounds) == 6
+            if world_to_model is None and model_to_world is None:
+                world_to_model = model_to_world = np.eye(4)
+            elif model_to_world is None:
+                model_to_world = np.linalg.inv(np.asarray(world_to_model, dtype=np.float64))
+            elif world_to_model is None:
+                world_to_model = np.linalg.inv(np.asarray(model_to_world, dtype=np.float64))
+            grid = _capi.PathedGridMedium()
+            grid.cells_z, grid.cells_y, grid.cells_x = data.shape
+            grid.bounds[:] = [float(value) for value in bounds]
+            grid.data = data.ctypes.data_as(C.POINTER(C.c_float))
+            grid.albedo, grid.scale = float(albedo), float(scale)
+            grid.world_to_model[:] = [float(value) for value in np.asarray(world_to_model, dtype=np.float32).reshape(16)]
+            grid.model_to_world[:] = [float(value) for value in np.asarray(model_to_world, dtype=np.float32).reshape(16)]
+        grid.struct_size = C.sizeof(_capi.PathedGridMedium)
+        _check(self._lib, self._lib.pathed_hip_scene_set_grid_medium(self._handle, int(medium_index), C.byref(grid)), "pathed_hip_scene_set_grid_medium")
+
+    def grid_queries(self, medium_index, a, b, target):
+        """GridMedium::transmittance(a, b) and findTransmittance(a, b, target) of the grid in slot `medium_index` for n world-space
+        segments (pathed_hip_grid_queries): (transmittance, distance), float32 (n,); distance is -1 where the result is invalid."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3)
+        target = np.ascontiguousarray(target, dtype=np.float32).reshape(-1)
+        assert a.shape == b.shape and target.shape[0] == a.shape[0]
+        transmittance = np.zeros(a.shape[0], dtype=np.float32)
+        distance = np.zeros(a.shape[0], dtype=np.float32)
+        pointer = lambda array: array.ctypes.data_as(C.POINTER(C.c_float))
+        _check(self._lib, self._lib.pathed_hip_grid_queries(self._handle, int(medium_index), a.shape[0], pointer(a), pointer(b), pointer(target),
+                                                            pointer(transmittance), pointer(distance)), "pathed_hip_grid_queries")
+        return transmittance, distance
 
     def set_integrator(self, name):
         """"PathTracer" (default), "VolumePathTracer" or "AlbedoIntegrator" (reference src/job.cpp:65-97)."""

@@ -14,6 +14,13 @@ class LoadedScene:
         if not self._handle:
             raise RuntimeError(self._host.pathed_host_last_error().decode())
         self.desc = self._host.pathed_host_scene_desc(self._handle)
+        # the scene file's "heterogeneous" media: (medium slot, _capi.PathedGridMedium) pairs for HipScene(..., grids=...); the
+        # structs point into this object
+        self.grids = []
+        for i in range(self._host.pathed_host_scene_grid_count(self._handle)):
+            slot = C.c_int(-1)
+            grid = self._host.pathed_host_scene_grid(self._handle, i, C.byref(slot))
+            self.grids.append((slot.value, grid.contents))
         self.width = width
         self.height = height
 

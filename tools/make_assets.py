@@ -15,6 +15,9 @@ here is SYNTHETIC (labelled so in DESIGN.md); file formats are the reference's o
   assets/cornell-volume-caustic/{bounds,CornellBox-Frame}.obj   for scenes/cornell-medium.json: the gas container (a box
                                                    around the glass sphere, below the light) and the Cornell room
                                                    without its two boxes (cut from scenes/CornellBox-Original.obj)
+  assets/smoke-plume.vol                           for scenes/cornell-smoke.json: a synthetic smoke plume, 32 x 32 x 32 densities in
+                                                   [0, 1] in the reference's .vol layout (src/vol_parser.cpp); the reference's own
+                                                   smoke and cloud volumes are not available
   test_scenes/1_pixel_test.exr                     1000x500, one texel (col 753,row 239)=1e4,
                                                    as decoded from the reference's file
 """
@@ -182,6 +185,42 @@ def make_cornell_medium():
             handle.write("f %d %d %d %d\n" % tuple(index + 1 for index in quad))
 
 
+def write_vol(path, density, bounds):
+    """The layout src/vol_parser.cpp reads: "VOL", a version byte, uint32 encoding (1: float32), cells x / y / z, channels,
+    six float bounds (min x, y, z, max x, y, z), then the cells, x fastest.  density: (cells_z, cells_y, cells_x)."""
+    density = np.ascontiguousarray(density, dtype="<f4")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "wb") as handle:
+        handle.write(b"VOL" + struct.pack("<B", 3))
+        handle.write(struct.pack("<5I", 1, density.shape[2], density.shape[1], density.shape[0], 1))
+        handle.write(struct.pack("<6f", *bounds))
+        handle.write(density.tobytes())
+
+
+def make_smoke_plume(cells=32):
+    """assets/smoke-plume.vol: SYNTHETIC.  A column that rises from a source near the floor of its box, widens and bends as
+    it climbs and thins out towards the top, broken up by lattice noise; zero on the box's faces, so that the medium ends
+    inside its container."""
+    axis = (np.arange(cells) + 0.5) / cells
+    z, y, x = np.meshgrid(axis, axis, axis, indexing="ij")
+    height = y
+    centre_x = 0.5 + 0.10 * np.sin(2.6 * height) * height
+    centre_z = 0.5 + 0.07 * np.sin(3.9 * height + 1.0) * height
+    radius = 0.07 + 0.22 * height
+    distance2 = (x - centre_x) ** 2 + (z - centre_z) ** 2
+    column = np.exp(-distance2 / (2.0 * radius ** 2)) * (0.07 / radius) ** 0.7
+    points = np.stack([x.ravel(), y.ravel() * 1.5, z.ravel()], axis=1) * 3.0
+    wisps = np.clip(0.55 + 1.6 * value_noise(points, 11).reshape(x.shape), 0.0, 1.5)
+    fade = np.clip(height / 0.06, 0.0, 1.0) * np.clip((1.0 - height) / 0.25, 0.0, 1.0)
+    density = np.clip(column * wisps * fade * 1.6, 0.0, 1.0)
+    for k in range(3):   # the faces of the box
+        face = [slice(None)] * 3
+        for end in (0, -1):
+            face[k] = end
+            density[tuple(face)] = 0.0
+    write_vol(os.path.join(REPO_ROOT, "assets", "smoke-plume.vol"), density, (-0.6, -0.85, -0.6, 0.6, 0.85, 0.6))
+
+
 def parallel_chunks(function, array, min_chunk=1 << 18):
     """function over chunks of `array` on a thread pool (numpy releases the GIL inside its loops), results concatenated."""
     workers = max(1, min(64, os.cpu_count() or 1))
@@ -293,12 +332,13 @@ def main():
     parser.add_argument("--force", action="store_true")
     args = parser.parse_args()
 
-    marker = os.path.join(REPO_ROOT, "assets", ".generated-v2")
+    marker = os.path.join(REPO_ROOT, "assets", ".generated-v3")
     if args.force or not os.path.exists(marker):
         make_mis()
         make_teapot()
         make_env_test()
         make_cornell_medium()
+        make_smoke_plume()
         write_exr(os.path.join(REPO_ROOT, "assets", "20060807_wells6_hd.exr"), sky(256, 128, sun_dir=(0.3, 0.2, 0.8)))
         with open(marker, "w") as handle:
             handle.write("tools/make_assets.py\n")

@@ -2,7 +2,7 @@
 """Msamples/s of a list of scenes through the C ABI, one process, interleaved repeats; variants are PathedSceneOptions
 (the product library reads no environment variable), images of the variants of a scene compared bit for bit.
 
-    tools/rates.py [--spp 256] [--repeats 3] [--scenes C2,ON,GGX,GL,GLASS,C3,C4,C5,VOL] [--variants default,generic]
+    tools/rates.py [--spp 256] [--repeats 3] [--scenes C2,ON,GGX,GL,GLASS,C3,C4,C5,VOL,SMOKE] [--variants default,generic]
                    [--lib other.so]   # the second column from another build of the library (a child process per library)
 
 Variants: name or name=opt:value+opt:value, e.g. "wave=shade_kernel:wave", "front=shade_kernel:per-slot".
@@ -29,6 +29,7 @@ SCENES = {
     "GL": ("scenes/cornell-glossy.json", 1024, 1024, "PathTracer"),
     "GLASS": ("scenes/cornell-glass.json", 1024, 1024, "PathTracer"),
     "VOL": ("scenes/cornell-medium.json", 1024, 1024, "VolumePathTracer"),
+    "SMOKE": ("scenes/cornell-smoke.json", 1024, 1024, "VolumePathTracer"),   # a voxel-grid medium (k_path_volume_grid)
 }
 PRESETS = {
     "default": {},
@@ -62,10 +63,12 @@ def run(args):
         for text in args.variants.split(","):
             name, options = parse_variant(text)
             try:
-                variants[name] = HipScene(scene.desc, device=0, bvh_builder=builder, **options)
+                variants[name] = HipScene(scene.desc, device=0, bvh_builder=builder, grids=scene.grids, **options)
                 variants[name].set_integrator(integrator)
             except Exception as error:   # a variant that does not apply to this scene
                 print("%s %s: %s" % (key, name, error), flush=True)
+        if not variants:
+            continue
         accum = {k: torch.zeros((h, w, 3), dtype=torch.float32, device="cuda") for k in variants}
         for k, gpu in variants.items():
             gpu.render_device(1, 0, min(args.spp, 16), 0, 10, accum[k].data_ptr())
