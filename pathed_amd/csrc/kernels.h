@@ -215,6 +215,7 @@ struct RenderParams {
     // sphere of radius -1 that no ray touches): phase 1 of the sphere queries (smallSphereCandidates)
     float spherePairs[8][4][2];   // [pair][component][half], kBruteForceMaxSpheres / 2 pairs
     float smallKappaT;        // ... and the absolute slack of their t bounds per det^2
+    float4 *cameraQueue;      // k_path_small: per wave of the grid kCameraQueueWords float4 of started samples (the camera queue)
     const float *mfmaTable;   // k_path_small<.., MFMA>: the A-side rows of the matrix-pipe phase 1 (mfma_candidates.h), kMfmaTableFloats
     MfmaFrame mfmaFrame;
     // k_path_hybrid (path_hybrid.h): scene.leafTris holds the DIRECT set in item order (hybridDirectTris of them), the rest of the
@@ -234,6 +235,9 @@ struct RenderParams {
     float4 localTris[3 * 8];
 };
 static const int kMaxLocalTris = 8;
+// k_path_small's camera queue: entries per wave (two refills of 64: a power of two), float4 per wave
+static const unsigned int kCameraQueueEntries = 128u;
+static const size_t kCameraQueueWords = 3 * (size_t)kCameraQueueEntries;
 
 // BounceController, reference src/bounce_controller.cpp:14-25
 __device__ inline bool checkDone(int lastBounce, int bounce)
@@ -2692,10 +2696,12 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ENV_ATTRIBUTE void k_shade_env
 // k_path_small: scenes of <= kBruteForceMaxTris triangles, whose ray queries are two straight-line passes
 // over kernarg-resident triangle records, need no ray or hit buffers at all.  One lane carries one PATH from
 // camera ray to termination with its whole state in registers -- the wavefront iteration
-// "trace, shade, trace shadow, regenerate" becomes the body of one loop -- and waves are persistent: a lane
-// whose sample ended takes the next sample of its work unit, or the next unit from the wave's reserved
-// range (one wave-level atomic per kUnitGrab units on a sharded cursor; a wave whose shard is dealt out
-// moves on to the next).  No path state touches HBM: per unit one 16-byte partial sum is written.
+// "trace, shade, trace shadow, regenerate" becomes the body of one loop -- and waves are persistent: a wave
+// starts units 64 at a time (one wave-level atomic per unitGrab units on a sharded cursor; a wave whose shard
+// is dealt out moves on to the next), keeps their camera rays' hits in its camera queue (below), and a lane
+// whose sample ended takes the next sample of its work unit, or the next entry of that queue.  No state of a
+// path in flight touches HBM: what does is the queue (48 bytes per started sample, written and read once by
+// the same wave) and per unit one 16-byte partial sum.
 // Every operation on a path's values is k_shade's, in k_shade's order, and the unit decomposition fixes
 // the summation order, so the radiance sums are the wavefront kernels' bit for bit (GPU test).
 // What the wavefront keeps and this gives up is the DENSE shadow-ray list: a shadow ray is traced by the lane
@@ -2733,14 +2739,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
 
     const DScene &scene = p.scene;
     const int lane = threadIdx.x & 63;
-    const unsigned int waveId = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const unsigned int waveId = blockIdx.x * kWavesPerBlock + (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (wave-uniform, and known to be)
     const int nTris = p.scene.nTris;
     const uint64_t seed = ((uint64_t)p.seedHi << 32) | p.seedLo;
     UnitTaker units(p, waveId);
 
     // ---- the path a lane carries
-    bool alive = false;
-    unsigned int unit = 0xFFFFFFFFu;
+    bool alive = true;               // the lane has a sample or may still get one
+    bool needEntry = true;           // ... it has none: it takes the next entry of the camera queue
+    unsigned int unit = 0xFFFFFFFFu; // the unit in flight; where a unit is one sample (singleSample), its partial sum's index
     uint32_t pixel = 0, sample = 0, endSample = 0;   // sample: absolute index of the sample in flight
     PathRegisters path = idlePath();
     float4 partial = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2750,18 +2757,27 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
 
     unsigned int closestRays = 0, shadowRays = 0, trisTested = 0;
 
-    // the camera ray: one inlined copy, reached from the initial fill and from the end of every sample
+    // ---- the wave's camera queue: a ring of kCameraQueueEntries started samples in HBM, three float4 each ([part][entry]):
+    // (direction, t), (u, v, prim, unit or partial index), (k0, k1 of the sample's random stream).  A camera ray's hit depends
+    // on (pixel, sample) alone, so the wave starts 64 units at a time at full width -- unit bookkeeping, key, camera ray, a
+    // primary-ray-only pass over the triangles -- ahead of need, and a lane whose sample ended takes a finished camera hit
+    // instead of starting a ray a sixth of a wave wide.  Only this wave touches its entries: a workgroup-scope fence after the
+    // writes and before the reads orders them.  Head, count and unitsLeft are wave-uniform.
+    float4 *const cameraQueue = p.cameraQueue + (size_t)waveId * kCameraQueueWords;
+    unsigned int queueHead = 0u, queueCount = 0u;
+    bool unitsLeft = true;           // UnitTaker::take has not yet come back short
+    const bool singleSample = p.chunk == 1;   // every unit is one sample: no lane ever needs the unit's pixel again
+
+    // a unit's later samples (set_samples_per_unit > 1) start in place, in order: one inlined copy of the camera ray
     bool startNext = false;
-    firstUnits(p, units, lane, unit, pixel, sample, endSample, alive, startNext);
 
     while (true) {
-        SHADE_REGION(0, alive);        // (profile builds, tools/fused_profile.py) iterations / live lanes
-        SHADE_REGION(1, startNext);    // camera ray
+        SHADE_REGION(0, alive && !needEntry);   // (profile builds, tools/fused_profile.py) iterations / lanes with a sample in flight
+        SHADE_REGION(1, startNext);    // camera ray started in place
         if (startNext) {
             startCameraSample(p, seed, pixel, sample, path);
             startNext = false;
         }
-        if (__ballot(alive) == 0ull) { break; }
 
         // ---- the path's ray (Scene::testIntersect's rtcIntersect1) and, from the same point, the shadow ray of the
         // vertex it leaves (Scene::testOcclusion's rtcOccluded1): an occluded light sample contributes nothing
@@ -2775,10 +2791,59 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
             stash[5 * kBlock] = make_float4(intAsFloat((int)path.random.k0), intAsFloat((int)path.random.k1), intAsFloat(path.firstEmitMaterial), intAsFloat((int)path.random.dimension));
             asm volatile("" ::: "memory");   // the values below are re-read from LDS: the registers are free for the pass
         }
+
+        // ---- refill (QUADS: inside the stash window, the path state is out of the way): fewer than a wave's worth of entries
+        // and units left: every lane starts one unit's first sample.  Phase 2 accepts by an order-independent rule, so the hit
+        // is the one the pair pass below would give this ray.
+        if (queueCount < 64u && unitsLeft) {
+            const unsigned int newUnit = units.take(p, lane, true);
+            const bool got = newUnit != 0xFFFFFFFFu;
+            const unsigned long long gotMask = __ballot(got);
+            SHADE_REGION(11, got);   // refill batches / their width
+            if (gotMask != ~0ull) { unitsLeft = false; }
+            Rng cameraRandom;
+            cameraRandom.k0 = 0u; cameraRandom.k1 = 0u; cameraRandom.dimension = 0u;
+            V3 cameraO = v3(0.f, 0.f, 0.f), cameraD = v3(0.f, 0.f, 1.f);
+            if (got) {
+                uint32_t unitPixel, unitFirst, unitEnd;
+                unitSamples(p, newUnit, &unitPixel, &unitFirst, &unitEnd);
+                cameraSampleRay(p, seed, unitPixel, unitFirst, cameraRandom, &cameraO, &cameraD);
+            }
+            LaneRay cameraHit;
+            laneRayInit(cameraHit, cameraO, cameraD, PATHED_TNEAR, PATHED_TFAR, false);
+            unsigned int candidatesLow = 0, candidatesHigh = 0;
+            if (got) {
+                if (QUADS || MFMA) {
+                    unsigned int unusedLow = 0, unusedHigh = 0;
+                    smallCandidatesItems<false, true, true>(smallTris.data, p.smallQuads, nTris, p.smallKappaT, cameraO, cameraD, cameraD,
+                                                             &candidatesLow, &candidatesHigh, &unusedLow, &unusedHigh, candidateNear(PATHED_TNEAR), 0.f);
+                } else {
+                    smallCandidates(smallTris.data, nTris, cameraO, cameraD, &candidatesLow, &candidatesHigh, candidateNear(PATHED_TNEAR));
+                }
+            }
+            if (COUNT && got) {
+                trisTested += (unsigned int)nTris;
+                closestRays++;
+            }
+            smallResolve(geometry, cameraHit, candidatesLow, candidatesHigh);
+            if (got) {
+                finishRay(geometry, cameraHit);
+                const unsigned int slot = (queueHead + queueCount + laneRank(gotMask)) & (kCameraQueueEntries - 1u);
+                // where a unit has several samples the lane needs the unit itself: its pixel and its samples
+                const unsigned int target = singleSample ? (unsigned int)partialIndex(p, newUnit) : newUnit;
+                cameraQueue[0 * kCameraQueueEntries + slot] = make_float4(cameraD.x, cameraD.y, cameraD.z, cameraHit.best);
+                cameraQueue[1 * kCameraQueueEntries + slot] = make_float4(cameraHit.bestU, cameraHit.bestV, intAsFloat(cameraHit.bestPrim), intAsFloat((int)target));
+                cameraQueue[2 * kCameraQueueEntries + slot] = make_float4(intAsFloat((int)cameraRandom.k0), intAsFloat((int)cameraRandom.k1), 0.f, 0.f);
+            }
+            queueCount += (unsigned int)__popcll(gotMask);
+            __threadfence_block();   // (release) the entries are written before any lane of the wave reads them
+        }
+
+        const bool tracing = alive && !needEntry;   // the lane has a ray in flight
         LaneRay ray;
         laneRayInit(ray, path.o, path.d, PATHED_TNEAR, PATHED_TFAR, false);
         {
-            const bool traceShadow = alive && pendingShadow;
+            const bool traceShadow = tracing && pendingShadow;
             LaneRay shadowRay;
             laneRayInit(shadowRay, path.o, shadowDirection, PATHED_TNEAR, shadowTfar, true);
             unsigned int candidatesLow = 0, candidatesHigh = 0, shadowLow = 0, shadowHigh = 0;
@@ -2787,27 +2852,27 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                 // every lane takes part (the matrix instructions are the wave's); words: even / odd triangles
                 mfmaCandidatesPair(mfmaRows, nTris, p.mfmaFrame, __ballot(traceShadow) != 0ull, path.o, path.d, shadowDirection,
                                    candidateNear(PATHED_TNEAR), candidateFar(shadowTfar), &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh);
-                if (!alive) { candidatesLow = 0u; candidatesHigh = 0u; }
+                if (!tracing) { candidatesLow = 0u; candidatesHigh = 0u; }
                 if (!traceShadow) { shadowLow = 0u; shadowHigh = 0u; }
             } else if (QUADS) {
                 // one instantiation of the pass: a wave without a single shadow ray is rare (3 % of the passes) and pays for
                 // the second ray's arithmetic rather than for a second copy of the loop's registers
-                if (alive) {
+                if (tracing) {
                     smallCandidatesItems<true, true, true>(smallTris.data, p.smallQuads, nTris, p.smallKappaT, path.o, path.d, shadowDirection,
                                                             &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh,
                                                             candidateNear(PATHED_TNEAR), candidateFar(shadowTfar));
                     if (!traceShadow) { shadowLow = 0u; shadowHigh = 0u; }
                 }
             } else if (__ballot(traceShadow) != 0ull) {
-                if (alive) {
+                if (tracing) {
                     smallCandidatesPair(smallTris.data, nTris, path.o, path.d, shadowDirection, &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh,
                                         candidateNear(PATHED_TNEAR), candidateFar(shadowTfar));
                     if (!traceShadow) { shadowLow = 0u; shadowHigh = 0u; }
                 }
-            } else if (alive) {
+            } else if (tracing) {
                 smallCandidates(smallTris.data, nTris, path.o, path.d, &candidatesLow, &candidatesHigh, candidateNear(PATHED_TNEAR));
             }
-            if (COUNT && alive) {
+            if (COUNT && tracing) {
                 trisTested += (unsigned int)nTris * (traceShadow ? 2u : 1u);
                 closestRays++;
                 if (traceShadow) { shadowRays++; }
@@ -2825,7 +2890,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                 scratch.occluded = resolveOccluded + waveBase; scratch.count = resolveCount + wave;
                 // spheres (the Veach scene's lights): a packed line-misses-sphere test for both rays, the exact tests on the shared list
                 unsigned int sphereCandidates = 0u, shadowSphereCandidates = 0u;
-                if (TRAITS::spheres && geometry.nSpheres > 0 && alive) {
+                if (TRAITS::spheres && geometry.nSpheres > 0 && tracing) {
                     smallSphereCandidates(p, geometry.nSpheres, path.o, path.d, shadowDirection, &sphereCandidates, &shadowSphereCandidates);
                     if (!traceShadow) { shadowSphereCandidates = 0u; }
                 }
@@ -2835,7 +2900,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                 smallResolve(geometry, ray, candidatesLow, candidatesHigh);
                 smallResolve(geometry, shadowRay, shadowLow, shadowHigh);
             }
-            if (alive && !spheresDone) { finishRay(geometry, ray); }
+            if (tracing && !spheresDone) { finishRay(geometry, ray); }
             if (traceShadow) {
                 if (!spheresDone) { finishRay(geometry, shadowRay); }
                 if (shadowRay.occluded) { path.pend = rgb(0.f); }
@@ -2853,14 +2918,75 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
             pixel = (uint32_t)floatAsInt(s4.x); sample = (uint32_t)floatAsInt(s4.y); endSample = (uint32_t)floatAsInt(s4.z); unit = (unsigned int)floatAsInt(s4.w);
             path.random.k0 = (uint32_t)floatAsInt(s5.x); path.random.k1 = (uint32_t)floatAsInt(s5.y); path.firstEmitMaterial = floatAsInt(s5.z); path.random.dimension = (uint32_t)floatAsInt(s5.w);
         }
-        const float4 h = make_float4(ray.best, ray.bestU, ray.bestV, intAsFloat(ray.bestPrim));
+        float4 h = make_float4(ray.best, ray.bestU, ray.bestV, intAsFloat(ray.bestPrim));
 
-        // ---- the vertex
-        bool finished = false;
+        // ---- the ray arrives: the MIS term of the BSDF sample that sent it, then termination
+        bool done = false;      // the lane's sample ended, `color` is its value
+        bool departs = false;   // the lane has a hit (h) to go on from
         Rgb color = rgb(0.f);
-        if (alive) {
+        if (tracing) {
+            const bool miss = floatAsInt(h.w) < 0;
+            Isect arrived;
+            SHADE_REGION(3, !miss);   // the hit's record, for the arrival
+            if (!miss) { arrived = makeIsect<TRAITS>(scene, path.o, path.d, h); }
+            done = pathArrive<TRAITS, true>(p, scene, materials, path, arrived, miss, &color);
+            departs = !done;
+        }
+
+        // ---- the lanes whose sample ended put it away and take the next camera hit from the queue, by ballot rank, to depart
+        // from it in this same iteration.  A camera ray that left the scene ends its sample at once: the lane comes round again.
+        while (true) {
+            SHADE_REGION(8, done);   // samples finished (every turn of this loop and below: the lanes add up to the samples)
+            {
+                const bool unitDone = putSampleAway(p, singleSample, done, color, partial, unit, sample, endSample);
+                needEntry = needEntry || unitDone;
+                startNext = startNext || (done && !unitDone);   // the unit's next sample starts in place
+            }
+            done = false;
+            const unsigned long long wanting = __ballot(needEntry);
+            if (wanting == 0ull) { break; }
+            if (queueCount == 0u) {
+                // the next refill brings more, or the pass is dealt out and the lanes retire
+                if (!unitsLeft && needEntry) { alive = false; needEntry = false; }
+                break;
+            }
+            __threadfence_block();   // (acquire) see the refill
+            const unsigned int rank = laneRank(wanting);
+            if (needEntry && rank < queueCount) {
+                const unsigned int slot = (queueHead + rank) & (kCameraQueueEntries - 1u);
+                const float4 e0 = cameraQueue[0 * kCameraQueueEntries + slot];
+                const float4 e1 = cameraQueue[1 * kCameraQueueEntries + slot];
+                const float4 e2 = cameraQueue[2 * kCameraQueueEntries + slot];
+                resetPath(path);
+                path.o = cameraOrigin(scene.camera);   // cameraRay's expression: the same for every sample
+                path.d = v3(e0.x, e0.y, e0.z);
+                path.random.k0 = (uint32_t)floatAsInt(e2.x); path.random.k1 = (uint32_t)floatAsInt(e2.y); path.random.dimension = 2u;
+                h = make_float4(e0.w, e1.x, e1.y, e1.z);
+                unit = (unsigned int)floatAsInt(e1.w);
+                if (singleSample) { sample = 0u; endSample = 1u; }
+                else { unitSamples(p, unit, &pixel, &sample, &endSample); }
+                needEntry = false;
+                if (floatAsInt(h.w) < 0) {
+                    color = cameraMissColor<TRAITS>(scene, path.d);
+                    done = true;
+                } else {
+                    departs = true;
+                }
+            }
+            const unsigned int wanted = (unsigned int)__popcll(wanting);
+            const unsigned int taken = wanted < queueCount ? wanted : queueCount;
+            queueHead = (queueHead + taken) & (kCameraQueueEntries - 1u);
+            queueCount -= taken;
+        }
+        if (__ballot(alive) == 0ull) { break; }   // no sample in flight, no entry, no unit left: nothing another wave could change
+
+        // ---- the new vertex, of the lanes that go on and of the lanes that took a camera hit alike
+        SHADE_REGION(6, departs);   // new vertex: makeIsect, BSDF sample
+        bool ended = false;
+        if (departs) {
+            Isect isect = makeIsect<TRAITS>(scene, path.o, path.d, h);
             ShadowRequest shadow;
-            finished = pathVertex<TRAITS, true>(p, scene, materials, path, h, &shadow, &color);
+            ended = pathDepart<TRAITS, true>(p, scene, materials, path, isect, &shadow, &color);
             // the vertex's shadow ray leaves isect.point like the continuation ray: both are traced in the next pass
             if (shadow.push) {
                 pendingShadow = true;
@@ -2868,9 +2994,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                 shadowTfar = shadow.tfar;
             }
         }
-
-        SHADE_REGION(8, alive && finished);   // sample finished
-        finishSample(p, units, lane, alive && finished, color, partial, unit, pixel, sample, endSample, alive, startNext);
+        // (rare: a dead end, or the last vertex the bounce window wants) such a lane takes its entry in the next iteration
+        if (__ballot(ended) != 0ull) {
+            SHADE_REGION(8, ended);
+            const bool unitDone = putSampleAway(p, singleSample, ended, color, partial, unit, sample, endSample);
+            needEntry = needEntry || unitDone;
+            startNext = startNext || (ended && !unitDone);
+        }
     }
 
     if (COUNT) {

@@ -137,41 +137,33 @@ __device__ __forceinline__ void startCameraSample(const RenderParams &p, uint64_
 // The remaining copies of this text are k_shade, k_shade_env and the kernels of kernels_experiments.h: they work on path
 // state in HBM, interleave its loads with the arithmetic and differ in what an ENV_ONLY scene lets them drop, and k_shade
 // sits one register under a budget whose loss costs 6-8 % (tests/test_kernel_resources.py).
-template <typename TRAITS, bool PROBES = false, typename MATERIALS>
-__device__ __forceinline__ bool pathVertex(const RenderParams &p, const DScene &scene, const MATERIALS &materials, PathRegisters &path,
-                                           float4 h, ShadowRequest *shadowOut, Rgb *color)
+//
+// The vertex has two halves.  pathArrive: the ray reaches its hit -- the MIS term of the BSDF sample that sent it, then
+// termination; of the hit it reads the material, the shading normal and the point, never the frame.  pathDepart: the new
+// vertex -- the camera ray's own bookkeeping, the BSDF sample, the light sample.  k_path_small hands a finished lane its next
+// sample's camera hit between the two (kernels.h: the camera queue), so that the lane departs in the same iteration; the
+// other kernels run them back to back on one Isect (pathVertex).
+
+// what a camera ray that leaves the scene is worth: SampleIntegrator::samplePixel, src/sample_integrator.cpp:18-59
+template <typename TRAITS>
+__device__ __forceinline__ Rgb cameraMissColor(const DScene &scene, V3 direction)
 {
-    ShadowRequest shadow;
-    shadow.push = false;
-    shadow.origin = v3(0.f, 0.f, 0.f);
-    shadow.direction = v3(0.f, 0.f, 1.f);
-    shadow.tfar = 0.f;
+    return rgb(0.f) + environmentL<TRAITS>(scene, direction);
+}
+
+// `isect`: makeIsect of the hit (anything where `miss`).  Returns true when the sample is finished (*color is its value).
+template <typename TRAITS, bool PROBES = false, typename MATERIALS>
+__device__ __forceinline__ bool pathArrive(const RenderParams &p, const DScene &scene, const MATERIALS &materials, PathRegisters &path, const Isect &isect,
+                                           bool miss, Rgb *color)
+{
     bool finished = false;
     *color = rgb(0.f);
-    const bool miss = floatAsInt(h.w) < 0;
     const int st = path.st;
     const int rayBounce = st & kStBounceMask;  // vertex that spawned this ray, 0 = camera
-    bool haveVertex = false;
-    Isect isect;
-    const int vertex = rayBounce + 1;
-    if (PROBES) { SHADE_REGION(3, !miss); }        // makeIsect
-    if (!miss) { isect = makeIsect<TRAITS>(scene, path.o, path.d, h); }
-
-    if (PROBES) { SHADE_REGION(4, rayBounce == 0); }   // camera-ray vertex
     if (rayBounce == 0) {
-        // SampleIntegrator::samplePixel, src/sample_integrator.cpp:18-59
         if (miss) {
-            *color = rgb(0.f) + environmentL<TRAITS>(scene, path.d);
+            *color = cameraMissColor<TRAITS>(scene, path.d);
             finished = true;
-        } else {
-            path.firstEmitMaterial = -1;
-            if (checkCounts(p.startBounce, p.lastBounce, 0)) {
-                const Rgb emit = matEmit(materials[isect.material]);
-                const bool backside = dot(isect.normal, isect.wo) < 0.f;
-                if (!isBlack(emit) && !backside) { path.firstEmitMaterial = isect.material; }
-            }
-            path.result = rgb(0.f);
-            haveVertex = true;
         }
     } else {
         // the ray left vertex `rayBounce` along its BSDF sample
@@ -211,7 +203,6 @@ __device__ __forceinline__ bool pathVertex(const RenderParams &p, const DScene &
             const float invPDF = 1.f / path.bsdfPdf;
             path.modulation = path.modulation * (path.throughput * path.cosTheta * invPDF);
             if (isBlack(path.modulation)) { finished = true; }
-            else { haveVertex = true; }
         }
         if (finished) {
             Rgb first = rgb(0.f);
@@ -219,9 +210,39 @@ __device__ __forceinline__ bool pathVertex(const RenderParams &p, const DScene &
             *color = first + path.result;
         }
     }
+    return finished;
+}
 
-    if (PROBES) { SHADE_REGION(6, haveVertex); }   // new vertex: BSDF sample
-    if (haveVertex) {
+// The vertex at `isect` (makeIsect of the hit of (path.o, path.d)) of a path that pathArrive did not finish.  Returns true
+// when the sample is finished here (*color is its value); otherwise path.o / path.d hold the next ray and *shadowOut the
+// vertex's occlusion query, if any.
+template <typename TRAITS, bool PROBES = false, typename MATERIALS>
+__device__ __forceinline__ bool pathDepart(const RenderParams &p, const DScene &scene, const MATERIALS &materials, PathRegisters &path,
+                                           Isect &isect, ShadowRequest *shadowOut, Rgb *color)
+{
+    ShadowRequest shadow;
+    shadow.push = false;
+    shadow.origin = v3(0.f, 0.f, 0.f);
+    shadow.direction = v3(0.f, 0.f, 1.f);
+    shadow.tfar = 0.f;
+    bool finished = false;
+    *color = rgb(0.f);
+    const int rayBounce = path.st & kStBounceMask;
+    const int vertex = rayBounce + 1;
+
+    if (PROBES) { SHADE_REGION(4, rayBounce == 0); }   // camera-ray vertex
+    if (rayBounce == 0) {
+        // SampleIntegrator::samplePixel, src/sample_integrator.cpp:18-59
+        path.firstEmitMaterial = -1;
+        if (checkCounts(p.startBounce, p.lastBounce, 0)) {
+            const Rgb emit = matEmit(materials[isect.material]);
+            const bool backside = dot(isect.normal, isect.wo) < 0.f;
+            if (!isBlack(emit) && !backside) { path.firstEmitMaterial = isect.material; }
+        }
+        path.result = rgb(0.f);
+    }
+
+    {
         // PathTracer::L: sample the BSDF, then direct(), src/path_tracer.cpp:30-36, 60-73
         const DMaterial &material = materials[isect.material];
         prepareLobes<TRAITS>(material, isect);
@@ -268,6 +289,22 @@ __device__ __forceinline__ bool pathVertex(const RenderParams &p, const DScene &
     return finished;
 }
 
+// Both halves on one hit: `h` is the hit of the ray (path.o, path.d).
+template <typename TRAITS, typename MATERIALS>
+__device__ __forceinline__ bool pathVertex(const RenderParams &p, const DScene &scene, const MATERIALS &materials, PathRegisters &path,
+                                           float4 h, ShadowRequest *shadowOut, Rgb *color)
+{
+    const bool miss = floatAsInt(h.w) < 0;
+    Isect isect;
+    if (!miss) { isect = makeIsect<TRAITS>(scene, path.o, path.d, h); }
+    shadowOut->push = false;
+    shadowOut->origin = v3(0.f, 0.f, 0.f);
+    shadowOut->direction = v3(0.f, 0.f, 1.f);
+    shadowOut->tfar = 0.f;
+    if (pathArrive<TRAITS>(p, scene, materials, path, isect, miss, color)) { return true; }
+    return pathDepart<TRAITS>(p, scene, materials, path, isect, shadowOut, color);
+}
+
 // The lanes of a fresh wave take their first units.
 __device__ __forceinline__ void firstUnits(const RenderParams &p, UnitTaker &units, int lane, unsigned int &unit,
                                            uint32_t &pixel, uint32_t &sample, uint32_t &endSample, bool &alive, bool &startNext)
@@ -281,12 +318,12 @@ __device__ __forceinline__ void firstUnits(const RenderParams &p, UnitTaker &uni
 }
 
 // End of a sample on the lanes where `done`: radianceLookup += color (src/sample_integrator.cpp:61-63; non-finite samples
-// dropped), then the unit's next sample (startNext), or the unit's partial sum goes out and the lane takes the next unit;
-// a lane that gets none retires (alive).
-__device__ __forceinline__ void finishSample(const RenderParams &p, UnitTaker &units, int lane, bool done, Rgb color, float4 &partial,
-                                             unsigned int &unit, uint32_t &pixel, uint32_t &sample, uint32_t &endSample, bool &alive, bool &startNext)
+// dropped); where that was the unit's last sample its partial sum goes out.  Returns true where the unit is finished.
+// unitIsIndex: every unit is one sample and `unit` already holds its partialIndex (k_path_small's camera queue).
+__device__ __forceinline__ bool putSampleAway(const RenderParams &p, bool unitIsIndex, bool done, Rgb color, float4 &partial, unsigned int unit,
+                                              uint32_t &sample, uint32_t endSample)
 {
-    bool needUnit = false;
+    bool unitDone = false;
     if (done) {
         const bool finite = isfinite(color.r) && isfinite(color.g) && isfinite(color.b);
         if (finite) {
@@ -297,14 +334,21 @@ __device__ __forceinline__ void finishSample(const RenderParams &p, UnitTaker &u
             atomicAdd(&p.stats[kStatDropped], 1ull);
         }
         sample++;
-        if (sample < endSample) {
-            startNext = true;
-        } else {
-            p.state.chunkBuf[partialIndex(p, unit)] = partial;
+        if (sample >= endSample) {
+            p.state.chunkBuf[unitIsIndex ? (size_t)unit : partialIndex(p, unit)] = partial;
             partial = make_float4(0.f, 0.f, 0.f, 0.f);
-            needUnit = true;
+            unitDone = true;
         }
     }
+    return unitDone;
+}
+
+// ... then the unit's next sample (startNext), or the lane takes the next unit; a lane that gets none retires (alive).
+__device__ __forceinline__ void finishSample(const RenderParams &p, UnitTaker &units, int lane, bool done, Rgb color, float4 &partial,
+                                             unsigned int &unit, uint32_t &pixel, uint32_t &sample, uint32_t &endSample, bool &alive, bool &startNext)
+{
+    const bool needUnit = putSampleAway(p, false, done, color, partial, unit, sample, endSample);
+    if (done && !needUnit) { startNext = true; }
     if (__ballot(needUnit) != 0ull) {
         const unsigned int newUnit = units.take(p, lane, needUnit);
         if (needUnit) {

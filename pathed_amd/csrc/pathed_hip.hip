@@ -217,6 +217,7 @@ struct PathedScene {
     std::vector<DGrid> gridsHost;
     std::vector<std::vector<float>> gridCells;   // per grid
     DeviceBuffer<int> volumeOverflow;   // the volume kernel's traversal-stack spill, per thread
+    DeviceBuffer<float4> cameraQueue;   // the fused kernel's started samples, per wave of its largest grid (kernels.h: the camera queue)
 
     // render state, allocated on first use
     int nSlots = 0;               // capacity of the per-slot state buffers
@@ -2161,7 +2162,9 @@ static int persistentPass(PathedScene *scene, const Pass &pass, int blocksPerCu,
     }
     {
         // a wave reserves up to one unit per lane at a time; passes too small for that hand out less per atomic,
-        // so that the last reservations of a queue do not leave most waves idle
+        // so that the last reservations of a queue do not leave most waves idle.  (k_path_small starts 64 units per refill of
+        // its camera queue whatever the reservation size -- several atomics where unitGrab is small -- and holds up to 127
+        // started samples: at the end of a pass a wave may still own that many while others retire)
         const unsigned int wavesPerQueue = (waves + (unsigned int)params.nQueues - 1) / (unsigned int)params.nQueues;
         unsigned int grab = (pass.nUnits / (unsigned int)params.nQueues) / (wavesPerQueue * 4u);
         params.unitGrab = (int)(grab < 1u ? 1u : grab > 64u ? 64u : grab);
@@ -2189,9 +2192,17 @@ static int persistentPass(PathedScene *scene, const Pass &pass, int blocksPerCu,
 // The fused path kernel (k_path_small: scenes of <= 64 triangles, whole paths in registers).  No tree, no stack.
 static int renderPassFused(PathedScene *scene, const Pass &pass)
 {
-    return persistentPass(scene, pass, PATHED_FUSED_WAVES, 0, 0, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
+    // the camera queues: once per scene, for every wave of the largest grid persistentPass starts; the launch below checks
+    // its grid against what is there
+    const size_t queueBlocks = (size_t)(scene->computeUnits > 0 ? scene->computeUnits : 1) * PATHED_FUSED_WAVES;
+    const size_t queueWords = queueBlocks * kWavesPerBlock * kCameraQueueWords;
+    if (scene->cameraQueue.count < queueWords) { HIP_TRY(scene->cameraQueue.allocate(queueWords)); }
+    bool queueShort = false;
+    const int code = persistentPass(scene, pass, PATHED_FUSED_WAVES, 0, 0, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
+        if ((size_t)grid.x * kWavesPerBlock * kCameraQueueWords > scene->cameraQueue.count) { queueShort = true; return; }   // nothing is launched
         const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
         const size_t lds = ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0;
+        params.cameraQueue = scene->cameraQueue.ptr;
         params.mfmaTable = scene->mfmaTable.ptr;
         params.mfmaFrame = scene->mfmaFrame;
         params.smallQuads = scene->smallLayout.nQuads;
@@ -2232,6 +2243,8 @@ static int renderPassFused(PathedScene *scene, const Pass &pass)
             withBool(ldsMaterials, [&](auto LDS_MATERIALS) { withBool(count, [&](auto COUNT) { run(k_path_small<LDS_MATERIALS, COUNT, TraitsAll>); }); });
         }
     });
+    if (queueShort) { return fail(PATHED_E_DEVICE, "the fused kernel's grid outgrew its camera queues"); }
+    return code;
 }
 
 // The volume integrator (k_path_volume).  small: <= 64 triangles, <= 16 spheres go through the all-triangles intersector
@@ -3182,12 +3195,15 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
         }
     }
     if (tuningEnv("PATHED_FUSED_PROFILE")) {   // the same counters in k_path_small (-DPATHED_SHADE_PROFILE builds)
-        static const char *regions[9] = { "iterations (live lanes)", "camera ray", "passes with shadow rays (lanes with one)", "makeIsect (hit)",
-                                          "camera-ray vertex", "BSDF sample met an emitter: lightsPDF", "new vertex: BSDF sample", "light sampling",
-                                          "sample finished" };
-        for (int r = 0; r < 9; r++) {
+        static const char *regions[9] = { "iterations (live lanes)", "camera ray started in place", "passes with shadow rays (lanes with one)",
+                                          "arrival: the hit's record", "camera-ray vertex (hit taken from the queue)", "BSDF sample met an emitter: lightsPDF",
+                                          "new vertex: makeIsect, BSDF sample", "light sampling", "sample finished" };
+        static const int shown[10] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 11 };   // (9, 10: the resolve loops, below)
+        for (int k = 0; k < 10; k++) {
+            const int r = shown[k];
+            const char *name = r == 11 ? "refill of the camera queue (units started)" : regions[r];
             const unsigned long long waves = device[kStatShadeProfile + 2 * r], lanes = device[kStatShadeProfile + 2 * r + 1];
-            fprintf(stderr, "[pathed] k_path_small %-44s waves %12llu  (%.3f of the iterations)  lanes per wave %.1f\n", regions[r], waves,
+            fprintf(stderr, "[pathed] k_path_small %-44s waves %12llu  (%.3f of the iterations)  lanes per wave %.1f\n", name, waves,
                     device[kStatShadeProfile] ? (double)waves / (double)device[kStatShadeProfile] : 0.0, waves ? (double)lanes / (double)waves : 0.0);
         }
         static const char *loops[2] = { "resolve loop of the path's ray", "resolve loop of the shadow ray" };

@@ -1144,6 +1144,16 @@ __device__ inline float envEmitPDF(const DEnv &env, V3 direction)
 
 // ------------------------------------------------------------------------- camera
 
+// where every camera ray starts: the camera's transform applied to (0, 0, 0)
+__device__ inline V3 cameraOrigin(const DCamera &camera)
+{
+    const float *m = camera.m;
+    return v3(
+        m[0] * 0.f + m[1] * 0.f + m[2] * 0.f + camera.origin[0],
+        m[3] * 0.f + m[4] * 0.f + m[5] * 0.f + camera.origin[1],
+        m[6] * 0.f + m[7] * 0.f + m[8] * 0.f + camera.origin[2]);
+}
+
 // Camera::generateRay(float,float), src/camera.cpp:32-47 (film size precomputed on the host)
 __device__ inline void cameraRay(const DCamera &camera, float row, float col, V3 *origin, V3 *direction)
 {
@@ -1157,10 +1167,7 @@ __device__ inline void cameraRay(const DCamera &camera, float row, float col, V3
         -zNear));
 
     const float *m = camera.m;
-    *origin = v3(
-        m[0] * 0.f + m[1] * 0.f + m[2] * 0.f + camera.origin[0],
-        m[3] * 0.f + m[4] * 0.f + m[5] * 0.f + camera.origin[1],
-        m[6] * 0.f + m[7] * 0.f + m[8] * 0.f + camera.origin[2]);
+    *origin = cameraOrigin(camera);
     *direction = v3(
         m[0] * local.x + m[1] * local.y + m[2] * local.z,
         m[3] * local.x + m[4] * local.y + m[5] * local.z,
