@@ -446,6 +446,36 @@ int pathed_hip_scene_set_grid_medium(PathedScene *scene, int medium_index, const
 int pathed_hip_grid_queries(PathedScene *scene, int medium_index, size_t n, const float *a, const float *b, const float *target,
                             float *transmittance, float *distance);
 
+/* Test hook onto the shading functions (BSDF evaluation and sampling, Fresnel, sphere and environment sampling), below the
+ * image: one thread per record runs ONE function as the path kernels call it, in the instantiation `traits` of the kernels'
+ * compile-time scene sets.  Records are fp32, host memory, in the layouts of tests/golden/README.md
+ * (material(20) = type, albedo type, diffuse(3), emit(3), checker on(3), off(3), res(2), sigma, alpha, ior, distribution;
+ *  isect(11) = geometric normal(3), shading normal(3), wo(3), uv(2)); the random numbers a sampling function draws are the
+ * record's own u, in drawing order:
+ *   function                          in                               out
+ *   PATHED_QUERY_MATERIAL_F           material(20) isect(11) wi(3)     f(3) pdf
+ *   PATHED_QUERY_MATERIAL_SAMPLE      material(20) isect(11) u(3)      wi(3) pdf throughput(3)
+ *   PATHED_QUERY_FRESNEL              cos etaI etaT                    F
+ *   PATHED_QUERY_SPHERE_SAMPLE        center(3) radius ref(3) u(2)     point(3) normal(3) invPDF measure (0 solid angle, 1 area)
+ *   PATHED_QUERY_SPHERE_PDF           center(3) radius ref(3)          solid-angle pdf
+ *   PATHED_QUERY_ENV_EMIT             lightWo(3)                       Le(3)
+ *   PATHED_QUERY_ENV_PDF              direction(3)                     pdf, thetaStep, phiStep, thetaPDF * phiPDF * width * height
+ *   PATHED_QUERY_ENV_SAMPLE           point(3) u(2)                    point(3) normal(3) invPDF thetaStep phiStep
+ * The environment functions run on the scene's environment; nothing else of the scene is read.
+ * PATHED_E_INVALID, and nothing is launched: a material type, distribution or albedo kind outside the set `traits` (image
+ * textures and the passthrough material in every set), a sphere function on a set without spheres, an environment function
+ * on a set without environment or a scene without one, u outside [0, 1], a zero or non-finite environment direction. */
+enum {
+    PATHED_QUERY_MATERIAL_F = 0, PATHED_QUERY_MATERIAL_SAMPLE = 1, PATHED_QUERY_FRESNEL = 2, PATHED_QUERY_SPHERE_SAMPLE = 3,
+    PATHED_QUERY_SPHERE_PDF = 4, PATHED_QUERY_ENV_EMIT = 5, PATHED_QUERY_ENV_PDF = 6, PATHED_QUERY_ENV_SAMPLE = 7
+};
+enum {
+    PATHED_TRAITS_ALL = 0, PATHED_TRAITS_LAMBERTIAN_TRIANGLES = 1, PATHED_TRAITS_LAMBERTIAN_PLASTIC_SPHERES = 2,
+    PATHED_TRAITS_LAMBERTIAN_GLASS_CONTAINER = 3, PATHED_TRAITS_TRIANGLE_LIT = 4, PATHED_TRAITS_ENVIRONMENT_ONLY = 5,
+    PATHED_TRAITS_ROUGH_BECKMANN = 6, PATHED_TRAITS_ROUGH_GGX = 7, PATHED_TRAITS_SMOOTH = 8, PATHED_TRAITS_COUNT = 9
+};
+int pathed_hip_debug_shading_queries(PathedScene *scene, int function, int traits, size_t n, const float *in, float *out);
+
 /* Test hook onto the intersector that stands in for Embree.
  * rays: n * 8 floats (ox,oy,oz,tnear, dx,dy,dz,tfar), host memory.
  * any_hit == 0: closest hit (rtcIntersect1, reference src/scene.cpp:91-117):

@@ -1070,11 +1070,12 @@ struct EnvLight {
     }
 
     /* src/environment_light.cpp:82-105 */
-    SurfaceSample sample(Vec3 point, Rng &random) const
+    SurfaceSample sample(Vec3 point, Rng &random, int *steps = nullptr) const
     {
         float thetaPDF, phiPDF;
         const int thetaStep = thetaDistribution.sample(&thetaPDF, random);
         const int phiStep = phiDistributions[(size_t)thetaStep].sample(&phiPDF, random);
+        if (steps) { steps[0] = thetaStep; steps[1] = phiStep; }   /* (function-level checks: env_sample_steps) */
 
         const float phiCanonical = (phiStep + 0.5f) / width;
         const float thetaCanonical = (thetaStep + 0.5f) / height;
@@ -1095,7 +1096,7 @@ struct EnvLight {
     }
 
     /* src/environment_light.cpp:117-138 */
-    float emitPDF(Vec3 direction) const
+    float emitPDF(Vec3 direction, float *parts = nullptr) const
     {
         float phi, theta;
         cartesianToSpherical(worldToMap.applyVector(direction), &phi, &theta);
@@ -1108,6 +1109,7 @@ struct EnvLight {
 
         const float thetaPDF = thetaDistribution.pdf(thetaStep);
         const float phiPDF = phiDistributions[(size_t)thetaStep].pdf(phiStep);
+        if (parts) { parts[0] = (float)thetaStep; parts[1] = (float)phiStep; parts[2] = thetaPDF * phiPDF * width * height; }   /* (env_pdf_parts) */
 
         return thetaPDF * phiPDF * width * height / (sinf(theta) * kTwoPi * kPi);
     }
@@ -2769,6 +2771,23 @@ int oracle_env_eval(OracleScene *scene, const char *fn, const float *in, int n_i
         out[0] = s.point.x; out[1] = s.point.y; out[2] = s.point.z;
         out[3] = s.normal.x; out[4] = s.normal.y; out[5] = s.normal.z; out[6] = s.invPDF;
         return 7;
+    }
+    if (name == "env_pdf_parts") {
+        /* direction(3) -> pdf thetaStep phiStep (thetaPDF * phiPDF * width * height): the cell and the factors in front of the sinf */
+        if (n_in < 3 || n_out < 4) { return -2; }
+        out[0] = env.emitPDF(v3(in[0], in[1], in[2]), out + 1);
+        return 4;
+    }
+    if (name == "env_sample_steps") {
+        /* env_sample, then the chosen thetaStep phiStep */
+        if (n_in < 5 || n_out < 9) { return -2; }
+        Rng random = scriptedRng(in + 3, 2);
+        int steps[2];
+        const SurfaceSample s = env.sample(v3(in[0], in[1], in[2]), random, steps);
+        out[0] = s.point.x; out[1] = s.point.y; out[2] = s.point.z;
+        out[3] = s.normal.x; out[4] = s.normal.y; out[5] = s.normal.z; out[6] = s.invPDF;
+        out[7] = (float)steps[0]; out[8] = (float)steps[1];
+        return 9;
     }
     return -1;
 }

@@ -45,7 +45,7 @@ int oracle_render_chunked(OracleScene *scene, uint64_t seed,
                           float *accum_rgb_sum, int threads, uint64_t *stats, int chunk);
 
 /* Environment-light function-level checks (need an image, hence a scene):
- * fn in {"env_emit", "env_pdf", "env_sample"}, layouts in tests/golden/README.md. */
+ * fn in {"env_emit", "env_pdf", "env_sample", "env_pdf_parts", "env_sample_steps"}, layouts in tests/golden/README.md. */
 int oracle_env_eval(OracleScene *scene, const char *fn, const float *in, int n_in, float *out, int n_out);
 
 /* Radiance of ONE camera sample (for spot checks): rgb out. */

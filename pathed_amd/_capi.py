@@ -197,6 +197,16 @@ class PathedValuClocks(C.Structure):
 
 DEVICE_CURRENT = -1
 
+# pathed_hip_debug_shading_queries: function -> (id, floats in, floats out); traits set -> id (include/pathed_hip.h)
+SHADING_QUERIES = {
+    "material_f": (0, 34, 4), "material_sample": (1, 34, 7), "fresnel": (2, 3, 1), "sphere_sample": (3, 9, 8),
+    "sphere_pdf": (4, 7, 1), "env_emit": (5, 3, 3), "env_pdf": (6, 3, 4), "env_sample": (7, 5, 9),
+}
+SHADING_TRAITS = {
+    "All": 0, "LambertianTriangles": 1, "LambertianPlasticSpheres": 2, "LambertianGlassContainer": 3, "TriangleLit": 4,
+    "EnvironmentOnly": 5, "RoughBeckmann": 6, "RoughGgx": 7, "Smooth": 8,
+}
+
 # every symbol include/pathed_hip.h declares; tests check that the library exports all
 HIP_SYMBOLS = [
     "pathed_hip_init",
@@ -206,6 +216,7 @@ HIP_SYMBOLS = [
     "pathed_hip_scene_set_camera",
     "pathed_hip_scene_set_grid_medium",
     "pathed_hip_grid_queries",
+    "pathed_hip_debug_shading_queries",
     "pathed_hip_scene_destroy",
     "pathed_hip_render",
     "pathed_hip_render_device",
@@ -325,6 +336,9 @@ def load_hip():
     lib.pathed_hip_debug_small_candidates.restype = C.c_int
     lib.pathed_hip_debug_light_records.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int)]
     lib.pathed_hip_debug_light_records.restype = C.c_int
+    if hasattr(lib, "pathed_hip_debug_shading_queries"):   # (an older build of the same ABI, as above)
+        lib.pathed_hip_debug_shading_queries.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.pathed_hip_debug_shading_queries.restype = C.c_int
     lib.pathed_hip_scene_refit.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.pathed_hip_scene_refit.restype = C.c_int
     lib.pathed_hip_has_experiments.argtypes = []

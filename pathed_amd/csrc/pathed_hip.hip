@@ -6,6 +6,7 @@
 #include "bvh_build.h"
 #include "kernels.h"
 #include "features.h"
+#include "shading_queries.h"
 #if PATHED_EXPERIMENTS
 #include "kernels_experiments.h"
 #endif
@@ -2979,6 +2980,85 @@ int pathed_hip_grid_queries(PathedScene *scene, int medium_index, size_t n, cons
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(transmittance, deviceTransmittance.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(distance, deviceDistance.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
+    return PATHED_OK;
+}
+
+// what pathed_hip_debug_shading_queries needs to know of one SceneTraits set, and its instantiation of the kernel
+struct ShadingQuerySet {
+    unsigned materials;
+    bool beckmann, ggx, env, spheres, varyingAlbedo;
+    void (*kernel)(DEnv, const DMaterial *, int, int, int, int, const float *, float *);
+};
+#define SHADING_QUERY_SET(TRAITS) { TRAITS::materials, TRAITS::beckmann, TRAITS::ggx, TRAITS::env, TRAITS::spheres, TRAITS::varyingAlbedo, k_shading_queries<TRAITS> }
+
+int pathed_hip_debug_shading_queries(PathedScene *scene, int function, int traits, size_t n, const float *in, float *out)
+{
+    // the sets of the launch ladders, in the order of PATHED_TRAITS_* (include/pathed_hip.h)
+    static const ShadingQuerySet sets[PATHED_TRAITS_COUNT] = {
+        SHADING_QUERY_SET(TraitsAll), SHADING_QUERY_SET(TraitsLambertianTriangles), SHADING_QUERY_SET(TraitsLambertianPlasticSpheres),
+        SHADING_QUERY_SET(TraitsLambertianGlassContainer), SHADING_QUERY_SET(TraitsTriangleLit), SHADING_QUERY_SET(TraitsEnvironmentOnly),
+        SHADING_QUERY_SET(TraitsRoughBeckmann), SHADING_QUERY_SET(TraitsRoughGgx), SHADING_QUERY_SET(TraitsSmooth),
+    };
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (function < 0 || function >= kQueryCount) { return fail(PATHED_E_INVALID, "shading queries: unknown function"); }
+    if (traits < 0 || traits >= PATHED_TRAITS_COUNT) { return fail(PATHED_E_INVALID, "shading queries: unknown traits set"); }
+    const ShadingQuerySet &set = sets[traits];
+    const bool material = function == kQueryMaterialF || function == kQueryMaterialSample;
+    const bool sphere = function == kQuerySphereSample || function == kQuerySpherePdf;
+    const bool env = function == kQueryEnvEmit || function == kQueryEnvPdf || function == kQueryEnvSample;
+    if (sphere && !set.spheres) { return fail(PATHED_E_INVALID, "shading queries: the traits set holds no spheres"); }
+    if (env && !set.env) { return fail(PATHED_E_INVALID, "shading queries: the traits set holds no environment"); }
+    if (env && !scene->device.hasEnv) { return fail(PATHED_E_INVALID, "shading queries: the scene has no environment"); }
+    if (n == 0) { return PATHED_OK; }
+    if (!in || !out) { return fail(PATHED_E_INVALID, "null record or result buffer"); }
+    if (n > (size_t)1 << 20) { return fail(PATHED_E_INVALID, "too many records in one call"); }
+    const int inputs = kQueryInputs[function], outputs = kQueryOutputs[function];
+    auto unit = [](float u) { return u >= 0.f && u <= 1.f; };
+    std::vector<DMaterial> materials;
+    for (size_t i = 0; i < n; i++) {
+        const float *p = in + (size_t)inputs * i;
+        if (material) {
+            PathedMaterial m;
+            std::memset(&m, 0, sizeof m);
+            if (!(p[0] >= 0.f && p[0] <= 5.f) || p[0] != (float)(int)p[0]) { return fail(PATHED_E_INVALID, "shading queries: material type"); }
+            m.type = (int)p[0];
+            if (((set.materials >> m.type) & 1u) == 0u) { return fail(PATHED_E_INVALID, "shading queries: the traits set does not hold the material type"); }
+            if (p[1] != (float)PATHED_ALBEDO_CONSTANT && p[1] != (float)PATHED_ALBEDO_CHECKERBOARD) { return fail(PATHED_E_INVALID, "shading queries: constant or checkerboard albedo"); }
+            m.albedo_type = (int)p[1];
+            if (m.albedo_type != PATHED_ALBEDO_CONSTANT && !set.varyingAlbedo) { return fail(PATHED_E_INVALID, "shading queries: the traits set holds constant albedo only"); }
+            if (p[19] != (float)PATHED_DIST_BECKMANN && p[19] != (float)PATHED_DIST_GGX) { return fail(PATHED_E_INVALID, "shading queries: distribution"); }
+            m.distribution = (int)p[19];
+            if (m.type == PATHED_MAT_MICROFACET || m.type == PATHED_MAT_PLASTIC) {
+                if (m.distribution == PATHED_DIST_GGX ? !set.ggx : !set.beckmann) { return fail(PATHED_E_INVALID, "shading queries: the traits set does not hold the distribution"); }
+            }
+            for (int k = 0; k < 3; k++) {
+                m.diffuse[k] = p[2 + k]; m.emit[k] = p[5 + k]; m.checker_on[k] = p[8 + k]; m.checker_off[k] = p[11 + k];
+            }
+            m.checker_res[0] = p[14]; m.checker_res[1] = p[15];
+            m.sigma = p[16]; m.alpha = p[17]; m.ior = p[18];
+            materials.push_back(buildMaterial(m));
+            if (function == kQueryMaterialSample && !(unit(p[31]) && unit(p[32]) && unit(p[33]))) { return fail(PATHED_E_INVALID, "shading queries: random numbers lie in [0, 1]"); }
+        }
+        if (function == kQuerySphereSample && !(unit(p[7]) && unit(p[8]))) { return fail(PATHED_E_INVALID, "shading queries: random numbers lie in [0, 1]"); }
+        if (function == kQueryEnvSample && !(unit(p[3]) && unit(p[4]))) { return fail(PATHED_E_INVALID, "shading queries: random numbers lie in [0, 1]"); }
+        if (function == kQueryEnvEmit || function == kQueryEnvPdf) {
+            // the texel index comes from the direction's angles: not-a-number angles index outside the image
+            const float length2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+            if (!std::isfinite(length2) || !(length2 > 1e-30f)) { return fail(PATHED_E_INVALID, "shading queries: a direction must be finite and not zero"); }
+        }
+    }
+    SELECT_DEVICE(scene);
+    DeviceBuffer<float> deviceIn, deviceOut;
+    DeviceBuffer<DMaterial> deviceMaterials;
+    HIP_TRY(deviceIn.upload(std::vector<float>(in, in + (size_t)inputs * n)));
+    HIP_TRY(deviceOut.allocate((size_t)outputs * n));
+    if (material) { HIP_TRY(deviceMaterials.upload(materials)); }
+    HIP_TRY(hipMemset(deviceOut.ptr, 0, (size_t)outputs * n * sizeof(float)));
+    hipLaunchKernelGGL(set.kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, scene->device.env, deviceMaterials.ptr,
+                       function, (int)n, inputs, outputs, deviceIn.ptr, deviceOut.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, deviceOut.ptr, (size_t)outputs * n * sizeof(float), hipMemcpyDeviceToHost));
     return PATHED_OK;
 }
 

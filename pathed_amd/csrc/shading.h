@@ -221,8 +221,8 @@ __device__ inline void cosSin(float angle, float *cosine, float *sine)
 }
 
 // src/monte_carlo.cpp:24-41
-template <bool PAIRED = false>
-__device__ inline V3 cosineSampleHemisphere(Rng &random)
+template <bool PAIRED = false, typename RNG>
+__device__ inline V3 cosineSampleHemisphere(RNG &random)
 {
     const float xi1 = random.next();
     const float r = sqrtf(xi1);
@@ -368,8 +368,8 @@ __device__ inline Rgb lambertianF(const DMaterial &m, const Isect &isect, V3 wiW
 }
 
 // src/lambertian.cpp:42-58
-template <bool VARYING_ALBEDO = true, bool PAIRED = false>
-__device__ inline BSDFSample lambertianSample(const DMaterial &m, const Isect &isect, Rng &random)
+template <bool VARYING_ALBEDO = true, bool PAIRED = false, typename RNG>
+__device__ inline BSDFSample lambertianSample(const DMaterial &m, const Isect &isect, RNG &random)
 {
     const V3 localSample = cosineSampleHemisphere<PAIRED>(random);
     const V3 worldSample = toWorld(isect.frame, localSample);
@@ -427,8 +427,8 @@ __device__ inline Rgb orenNayarF(const DMaterial &m, const Isect &isect, V3 wiWo
 }
 
 // src/oren_nayar.cpp:69-85
-template <bool PAIRED = false>
-__device__ inline BSDFSample orenNayarSample(const DMaterial &m, const Isect &isect, Rng &random)
+template <bool PAIRED = false, typename RNG>
+__device__ inline BSDFSample orenNayarSample(const DMaterial &m, const Isect &isect, RNG &random)
 {
     const V3 localSample = cosineSampleHemisphere<PAIRED>(random);
     const V3 worldSample = toWorld(isect.frame, localSample);
@@ -483,8 +483,8 @@ __device__ inline float beckmannG(float alpha, V3 wo, V3 wi)
 }
 
 // src/beckmann.cpp:13-43: phi is drawn first, then the tan^2 variate
-template <bool PAIRED = false>
-__device__ inline V3 beckmannSampleWh(float alpha, Rng &random)
+template <bool PAIRED = false, typename RNG>
+__device__ inline V3 beckmannSampleWh(float alpha, RNG &random)
 {
     const float phi = twoPiTimes(random.next());
 
@@ -522,8 +522,8 @@ __device__ inline float ggxG1(float alpha, V3 v)
 }
 
 // src/ggx.cpp:13-25: theta variate first, then phi (the opposite of Beckmann)
-template <bool PAIRED = false>
-__device__ inline V3 ggxSampleWh(float alpha, Rng &random)
+template <bool PAIRED = false, typename RNG>
+__device__ inline V3 ggxSampleWh(float alpha, RNG &random)
 {
     const float xi1 = random.next();
     const float xi2 = random.next();
@@ -554,8 +554,8 @@ __device__ inline float distributionG(const DMaterial &m, V3 wo, V3 wi)
 {
     return usesGgx<TRAITS>(m) ? ggxG1(m.alpha, wo) * ggxG1(m.alpha, wi) : beckmannG(m.alpha, wo, wi);
 }
-template <typename TRAITS>
-__device__ inline V3 distributionSampleWh(const DMaterial &m, Rng &random)
+template <typename TRAITS, typename RNG>
+__device__ inline V3 distributionSampleWh(const DMaterial &m, RNG &random)
 {
     return usesGgx<TRAITS>(m) ? ggxSampleWh<TRAITS::pairedTrig>(m.alpha, random) : beckmannSampleWh<TRAITS::pairedTrig>(m.alpha, random);
 }
@@ -591,8 +591,8 @@ __device__ inline Rgb microfacetF(const DMaterial &m, const Isect &isect, V3 wiW
 }
 
 // src/microfacet.cpp:59-78
-template <typename TRAITS = TraitsAll>
-__device__ inline BSDFSample microfacetSample(const DMaterial &m, const Isect &isect, Rng &random)
+template <typename TRAITS = TraitsAll, typename RNG>
+__device__ inline BSDFSample microfacetSample(const DMaterial &m, const Isect &isect, RNG &random)
 {
     const V3 wo = toLocal(isect.frame, isect.wo);
     const V3 wh = distributionSampleWh<TRAITS>(m, random);
@@ -618,8 +618,8 @@ __device__ inline Rgb plasticF(const DMaterial &m, const Isect &isect, V3 wiWorl
 }
 
 // src/plastic.cpp:35-66
-template <typename TRAITS = TraitsAll>
-__device__ inline BSDFSample plasticSample(const DMaterial &m, const Isect &isect, Rng &random)
+template <typename TRAITS = TraitsAll, typename RNG>
+__device__ inline BSDFSample plasticSample(const DMaterial &m, const Isect &isect, RNG &random)
 {
     const float xi = random.next();
     BSDFSample sample;
@@ -642,7 +642,8 @@ __device__ inline BSDFSample plasticSample(const DMaterial &m, const Isect &isec
 // src/glass.cpp:30-85.  Where the reference exit(1)s (refraction branch taken although
 // Snell::refract reported total internal reflection — a rounding corner) the direction
 // refract() produced is used.
-__device__ inline BSDFSample glassSample(const DMaterial &m, const Isect &isect, Rng &random)
+template <typename RNG>
+__device__ inline BSDFSample glassSample(const DMaterial &m, const Isect &isect, RNG &random)
 {
     const V3 localWo = toLocal(isect.frame, isect.wo);
     V3 localWi = v3(0.f, 0.f, 0.f);
@@ -766,8 +767,8 @@ __device__ inline Rgb materialF(const DMaterial &m, const Isect &isect, V3 wiWor
 #endif
 }
 
-template <typename TRAITS = TraitsAll>
-__device__ inline BSDFSample materialSample(const DMaterial &m, const Isect &isect, Rng &random)
+template <typename TRAITS = TraitsAll, typename RNG>
+__device__ inline BSDFSample materialSample(const DMaterial &m, const Isect &isect, RNG &random)
 {
 #if PATHED_MATERIAL_SWITCH
     switch (m.type) {
@@ -858,7 +859,8 @@ __device__ inline float triangleArea(V3 p0, V3 p1, V3 p2)
 __device__ inline V3 triangleSampleNormal(V3 p0, V3 p1, V3 p2) { return normalized(cross(p1 - p0, p2 - p0)); }
 
 // src/triangle.cpp:16-38, the part that depends on the random numbers; normal and area are constants of the triangle
-__device__ inline SurfaceSample triangleSamplePoint(V3 p0, V3 p1, V3 p2, V3 normal, float area, Rng &random)
+template <typename RNG>
+__device__ inline SurfaceSample triangleSamplePoint(V3 p0, V3 p1, V3 p2, V3 normal, float area, RNG &random)
 {
     const float r1 = random.next();
     const float r2 = random.next();
@@ -876,7 +878,8 @@ __device__ inline SurfaceSample triangleSamplePoint(V3 p0, V3 p1, V3 p2, V3 norm
 }
 
 // src/triangle.cpp:16-38 from the corners alone: what the light records (device_scene.h) are checked against
-__device__ inline SurfaceSample triangleSample(V3 p0, V3 p1, V3 p2, Rng &random)
+template <typename RNG>
+__device__ inline SurfaceSample triangleSample(V3 p0, V3 p1, V3 p2, RNG &random)
 {
     return triangleSamplePoint(p0, p1, p2, triangleSampleNormal(p0, p1, p2), triangleArea(p0, p1, p2), random);
 }
@@ -944,8 +947,8 @@ __device__ inline float uniformConePdf(float cosThetaMax)
 }
 
 // src/sphere.cpp:54-70
-template <bool PAIRED = false>
-__device__ inline SurfaceSample sphereSampleArea(V3 center, float radius, Rng &random)
+template <bool PAIRED = false, typename RNG>
+__device__ inline SurfaceSample sphereSampleArea(V3 center, float radius, RNG &random)
 {
     const float z = 1 - 2 * random.next();
     const float r = sqrtf(fmaxf(0, 1 - z * z));
@@ -963,8 +966,8 @@ __device__ inline SurfaceSample sphereSampleArea(V3 center, float radius, Rng &r
 }
 
 // src/sphere.cpp:77-128 (samples about the UNTRANSFORMED centre, as the reference does)
-template <bool PAIRED = false>
-__device__ inline SurfaceSample sphereSample(V3 center, float radius, V3 referencePoint, Rng &random)
+template <bool PAIRED = false, typename RNG>
+__device__ inline SurfaceSample sphereSample(V3 center, float radius, V3 referencePoint, RNG &random)
 {
     const float centerDistance = length(center - referencePoint);
     const float centerDistance2 = centerDistance * centerDistance;
@@ -1094,15 +1097,17 @@ __device__ inline Rgb envEmit(const DEnv &env, V3 lightWo)
     return rgb(texel.x, texel.y, texel.z) * env.scale;
 }
 
-// EnvironmentLight::sample, src/environment_light.cpp:82-105
-template <bool PAIRED = false>
-__device__ inline SurfaceSample envSample(const DEnv &env, V3 point, Rng &random)
+// EnvironmentLight::sample, src/environment_light.cpp:82-105.  `steps`: where the query hook (shading_queries.h) wants the
+// chosen (thetaStep, phiStep); the path kernels pass none
+template <bool PAIRED = false, typename RNG>
+__device__ inline SurfaceSample envSample(const DEnv &env, V3 point, RNG &random, int *steps = nullptr)
 {
     float thetaPDF, phiPDF;
     const int thetaStep = cdfSampleRecord(env.thetaRecords, env.thetaCdf, env.height, random.next(), &thetaPDF);
     const int phiStep = cdfSampleRecord(
         env.phiRecords + (size_t)2 * thetaStep * (env.width + 1), env.phiCdf + (size_t)thetaStep * env.width, env.width,
         random.next(), &phiPDF);
+    if (steps) { steps[0] = thetaStep; steps[1] = phiStep; }
 
     const float phiCanonical = (phiStep + 0.5f) / env.width;
     const float thetaCanonical = (thetaStep + 0.5f) / env.height;
@@ -1124,8 +1129,9 @@ __device__ inline SurfaceSample envSample(const DEnv &env, V3 point, Rng &random
     return out;
 }
 
-// EnvironmentLight::emitPDF, src/environment_light.cpp:117-138
-__device__ inline float envEmitPDF(const DEnv &env, V3 direction)
+// EnvironmentLight::emitPDF, src/environment_light.cpp:117-138.  `parts`: where the query hook wants (thetaStep, phiStep, the
+// numerator thetaPDF * phiPDF * width * height), what the result is made of before the division by sinf
+__device__ inline float envEmitPDF(const DEnv &env, V3 direction, float *parts = nullptr)
 {
     float phi, theta;
     cartesianToSpherical(apply3x3(env.worldToMap, direction), &phi, &theta);
@@ -1138,6 +1144,7 @@ __device__ inline float envEmitPDF(const DEnv &env, V3 direction)
 
     const float thetaPDF = cdfPdf(env.thetaCdf, env.thetaEmpty, thetaStep);
     const float phiPDF = cdfPdf(env.phiCdf + (size_t)thetaStep * env.width, env.phiEmpty[thetaStep], phiStep);
+    if (parts) { parts[0] = (float)thetaStep; parts[1] = (float)phiStep; parts[2] = thetaPDF * phiPDF * env.width * env.height; }
 
     return thetaPDF * phiPDF * env.width * env.height / (sinf(theta) * PATHED_TWO_PI * PATHED_PI);
 }

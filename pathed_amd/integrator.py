@@ -254,6 +254,18 @@ class HipScene:
                                                             pointer(transmittance), pointer(distance)), "pathed_hip_grid_queries")
         return transmittance, distance
 
+    def shading_queries(self, function, traits, records):
+        """One shading function per record on the device (pathed_hip_debug_shading_queries): `function` a key of
+        _capi.SHADING_QUERIES, `traits` one of _capi.SHADING_TRAITS, records (n, floats in) in the layouts of
+        tests/golden/README.md -> (n, floats out) float32."""
+        code, n_in, n_out = _capi.SHADING_QUERIES[function]
+        records = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, n_in)
+        out = np.zeros((records.shape[0], n_out), dtype=np.float32)
+        pointer = lambda array: array.ctypes.data_as(C.POINTER(C.c_float))
+        _check(self._lib, self._lib.pathed_hip_debug_shading_queries(self._handle, code, _capi.SHADING_TRAITS[traits], records.shape[0],
+                                                                     pointer(records), pointer(out)), "pathed_hip_debug_shading_queries")
+        return out
+
     def set_integrator(self, name):
         """"PathTracer" (default), "VolumePathTracer" or "AlbedoIntegrator" (reference src/job.cpp:65-97)."""
         code = {"PathTracer": _capi.INTEGRATOR_PATH_TRACER, "DataParallelIntegrator": _capi.INTEGRATOR_PATH_TRACER,
