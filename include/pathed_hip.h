@@ -221,7 +221,8 @@ typedef struct PathedStats {
                                       6 wave path kernel (BVH scenes, the last render call),
                                       7 hybrid path kernel (scenes of 65 .. 4096 triangles, the last render call),
                                       8 feature kernel (the last call was pathed_hip_render_features[_device], or a render call
-                                        of PATHED_INTEGRATOR_ALBEDO; its samples count in camera_samples and closest_rays) */
+                                        of PATHED_INTEGRATOR_ALBEDO; its samples count in camera_samples and closest_rays),
+                                      9 multiple-scattering volume kernel (PATHED_INTEGRATOR_BASIC_VOLUME) */
     uint32_t reserved0;
     uint64_t local_closest_rays;   /* closest-hit queries the shade kernel resolved itself (rays that cannot meet anything but the
                                       scene's few large triangles, PathedSceneOptions.local_rays) -- stats mode; NOT in closest_rays */
@@ -377,10 +378,21 @@ int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
  *                                         calls run the feature kernel: last_bounce is ignored, start_bounce only decides the
  *                                         emission, and a pixel's samples are summed one by one in sample order whatever
  *                                         pathed_hip_set_samples_per_unit says.
- * Scenes that contain PATHED_MAT_PASSTHROUGH materials render with the volume integrator only. */
+ *   PATHED_INTEGRATOR_BASIC_VOLUME        BasicVolumeIntegrator::L (src/basic_volume_integrator.cpp:25-197, src/job.cpp:73-74) with
+ *                                         the same DirectLightingHelper::Ld: multiple scattering.  Every segment samples a
+ *                                         scattering distance in the current medium (Medium::integrate); a path that scatters is
+ *                                         weighted by the albedo (IntegrationResult::weight), lit there (VolumeHelper::
+ *                                         directSampleLights, whatever the bounce window says) and turned through the isotropic
+ *                                         phase function (include/phase.h, UniformSampleSphere, src/monte_carlo.cpp:43-52); the
+ *                                         current medium is the top of a stack of the media the path has entered
+ *                                         (updateMediumPtrs, :145-174; a surface without an internal medium pushes "none").  The
+ *                                         stack holds four entries: a sample that would push a fifth is dropped and counted in
+ *                                         PathedStats.dropped_samples.
+ * Scenes that contain PATHED_MAT_PASSTHROUGH materials render with the two volume integrators only. */
 #define PATHED_INTEGRATOR_PATH_TRACER 0
 #define PATHED_INTEGRATOR_VOLUME_PATH_TRACER 1
 #define PATHED_INTEGRATOR_ALBEDO 2
+#define PATHED_INTEGRATOR_BASIC_VOLUME 3
 int pathed_hip_set_integrator(PathedScene *scene, int integrator);
 
 /* Summation granularity.  A pixel's samples are summed in sample order in groups of
@@ -426,8 +438,8 @@ int pathed_hip_render_features(PathedScene *scene, uint64_t seed, uint32_t spp_b
  * pathed_hip_scene_set_grid_medium turns medium slot `medium_index` into a grid medium (its sigma_t / sigma_s are ignored
  * from then on); called again on the same slot it replaces the grid.  It uploads the grid and rebuilds nothing else.
  * PATHED_E_INVALID: index out of range or a scene without media, cells < 2, bounds or data not finite, struct_size wrong.
- * A scene with a grid renders as PATHED_INTEGRATOR_VOLUME_PATH_TRACER only; every other render or feature call returns
- * PATHED_E_UNSUPPORTED. */
+ * A scene with a grid renders as PATHED_INTEGRATOR_VOLUME_PATH_TRACER or PATHED_INTEGRATOR_BASIC_VOLUME only; every other
+ * render or feature call returns PATHED_E_UNSUPPORTED. */
 typedef struct PathedGridMedium {
     uint32_t struct_size;   /* sizeof(PathedGridMedium) */
     uint32_t cells_x, cells_y, cells_z;
@@ -475,6 +487,12 @@ enum {
     PATHED_TRAITS_ROUGH_BECKMANN = 6, PATHED_TRAITS_ROUGH_GGX = 7, PATHED_TRAITS_SMOOTH = 8, PATHED_TRAITS_COUNT = 9
 };
 int pathed_hip_debug_shading_queries(PathedScene *scene, int function, int traits, size_t n, const float *in, float *out);
+
+/* Test hook onto the phase function of PATHED_INTEGRATOR_BASIC_VOLUME: the device's phaseSample (pathed_amd/csrc/volume.h =
+ * UniformSampleSphere, src/monte_carlo.cpp:43-52), one thread per record, on scripted numbers instead of the path's stream.
+ * u: n * 2 floats in [0, 1] (z's number, then phi's); out: n * 3 floats, the direction (r cos phi, z, r sin phi).  Host
+ * memory both.  PATHED_E_INVALID, and nothing is launched: a number outside [0, 1], more than 2^20 records. */
+int pathed_hip_debug_phase_samples(PathedScene *scene, size_t n, const float *u, float *out);
 
 /* Test hook onto the intersector that stands in for Embree.
  * rays: n * 8 floats (ox,oy,oz,tnear, dx,dy,dz,tfar), host memory.

@@ -14,7 +14,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 PATHED_ABI_VERSION = 4
 
 MAT_LAMBERTIAN, MAT_OREN_NAYAR, MAT_MICROFACET, MAT_PLASTIC, MAT_GLASS, MAT_MIRROR, MAT_PASSTHROUGH = range(7)
-INTEGRATOR_PATH_TRACER, INTEGRATOR_VOLUME_PATH_TRACER, INTEGRATOR_ALBEDO = 0, 1, 2
+INTEGRATOR_PATH_TRACER, INTEGRATOR_VOLUME_PATH_TRACER, INTEGRATOR_ALBEDO, INTEGRATOR_BASIC_VOLUME = 0, 1, 2, 3
 ALBEDO_CONSTANT, ALBEDO_CHECKERBOARD, ALBEDO_TEXTURE = 0, 1, 2
 GEOM_MESH, GEOM_SPHERE = 0, 1
 
@@ -217,6 +217,7 @@ HIP_SYMBOLS = [
     "pathed_hip_scene_set_grid_medium",
     "pathed_hip_grid_queries",
     "pathed_hip_debug_shading_queries",
+    "pathed_hip_debug_phase_samples",
     "pathed_hip_scene_destroy",
     "pathed_hip_render",
     "pathed_hip_render_device",
@@ -339,6 +340,9 @@ def load_hip():
     if hasattr(lib, "pathed_hip_debug_shading_queries"):   # (an older build of the same ABI, as above)
         lib.pathed_hip_debug_shading_queries.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.pathed_hip_debug_shading_queries.restype = C.c_int
+    if hasattr(lib, "pathed_hip_debug_phase_samples"):
+        lib.pathed_hip_debug_phase_samples.argtypes = [vp, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.pathed_hip_debug_phase_samples.restype = C.c_int
     lib.pathed_hip_scene_refit.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.pathed_hip_scene_refit.restype = C.c_int
     lib.pathed_hip_has_experiments.argtypes = []

@@ -3193,7 +3193,9 @@ __device__ __forceinline__ void volumeQueryPairSmall(const VolumeContext<Materia
 // are the kernels of scenes without a grid (k_path_volume), those with it are k_path_volume_grid.  A medium is read in three
 // places: the segment transmittance of the bounce loop, rayTransmission / the shadow transmittance of scatter, and scatter's
 // distance sample -- `transmit`, `transmission` and the head of `scatter` below.
-template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS, bool QUADS, bool GRID>
+// MULTI: the bounce loop is BasicVolumeIntegrator::L (multiple scattering, a stack of media) instead of VolumePathTracer::L; the
+// instantiations with it are k_path_scatter / k_path_scatter_grid, and the others contain none of its code.
+template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS, bool QUADS, bool GRID, bool MULTI = false>
 __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTris &smallTris)
 {
     extern __shared__ float4 ldsRaw[];
@@ -3403,7 +3405,10 @@ __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTri
 
     // VolumePathTracer::scatter -> HomogeneousMedium::integrate -> VolumeHelper::directSampleLights
     // (src/volume_path_tracer.cpp:114-131, src/homogeneous_medium.cpp:36-66, src/volume_helper.cpp:12-69)
-    auto scatter = [&](int medium, V3 entry, V3 exitPoint, Rng &random) -> Rgb {
+    // Returns IntegrationResult::Ld.  `event` (BasicVolumeIntegrator::L, MULTI below; VolumePathTracer passes none):
+    // IntegrationResult::shouldScatter and scatterPoint, filled in when the distance sample falls short of the segment's end.
+    struct ScatterEvent { bool scattered; V3 point; };
+    auto scatter = [&](int medium, V3 entry, V3 exitPoint, Rng &random, ScatterEvent *event = nullptr) -> Rgb {
         if (medium < 0) { return rgb(0.f); }
         V3 samplePoint;
         bool gridMedium = false;
@@ -3422,6 +3427,7 @@ __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTri
             if (sampleT >= distance) { return rgb(0.f); }
             samplePoint = entry + normalized(travel) * sampleT;
         }
+        if (event) { event->scattered = true; event->point = samplePoint; }
         if (scene.nLights == 0) { return rgb(0.f); }
         const int lightCount = scene.nLights;
         int lightIndex = (int)floorf(random.next() * lightCount);
@@ -3502,6 +3508,95 @@ __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTri
             }
         }
 
+        if constexpr (MULTI) {
+            // ---- BasicVolumeIntegrator::L, src/basic_volume_integrator.cpp:25-143.  `interaction` is (surface, last,
+            // bsdfSample) or (origin, direction) of a scatter event; after a scatter event `last` and `bsdfSample` keep the
+            // last SURFACE's values, as interaction.intersection and interaction.bsdfSample do, and are not read.
+            MediumStack media;
+            mediaClear(media);
+            random.dimension = vertexBase(1);
+            prepareLobes<TRAITS>(materials[last.material], last);
+            BSDFSample bsdfSample = volumeMaterialSample<TRAITS>(materials[last.material], last, random);
+            Rgb result = rgb(0.f);
+            {
+                const bool direct = checkCounts(p.startBounce, p.lastBounce, 1);
+                random.dimension = vertexBase(1) + 3;
+                const Rgb Ld = vertexLighting(last, mediaTop(media), materials[last.material], bsdfSample, random, direct, !checkDone(p.lastBounce, 2));
+                if (direct) { result = Ld; }
+            }
+            Rgb modulation = rgb(1.f);
+            bool surface = true, overflow = false;
+            V3 origin = last.point, direction = bsdfSample.wiWorld;   // interaction.point(), interaction.wiWorld()
+            for (int bounce = 2; !checkDone(p.lastBounce, bounce); bounce++) {
+                SHADE_REGION(2, true);   // bounce-loop iterations
+                // Scene::testIntersect along the interaction's ray (:62-65): containers are surfaces
+                if (surface) {
+                    // the previous vertex's pass has answered it (vertexLighting; every vertex whose path goes on asks)
+                    if (!segmentKnown || !segmentFound) { break; }
+                    segmentKnown = false;
+                    hit = segmentHit;
+                } else {
+                    SHADE_REGION(3, true);   // the ray that leaves a scatter event
+                    if (!query(kQueryRegular, origin, direction, PATHED_TFAR, &hit, nullptr)) { break; }
+                }
+                Isect next = makeIsect<TRAITS>(scene, origin, direction, make_float4(hit.t, hit.u, hit.v, intAsFloat(hit.prim)));
+                if (surface) {   // :68-77
+                    const float invPDF = 1.f / bsdfSample.pdf;
+                    const float cosTheta = fabsf(dot(last.shadingNormal, bsdfSample.wiWorld));
+                    modulation = modulation * (bsdfSample.throughput * cosTheta * invPDF);
+                }
+                if (isBlack(modulation)) { break; }
+                // updateMediumPtrs, :145-174: a path that changes sides at a surface enters or leaves what the surface holds
+                if (surface) {
+                    const bool woFrontside = dot(last.normal, last.wo) >= 0.f;
+                    const bool wiFrontside = dot(last.normal, bsdfSample.wiWorld) >= 0.f;
+                    if (woFrontside != wiFrontside) {
+                        const int internal = context.primMedium[last.prim];   // -1: a surface without one (pushed all the same)
+                        if (!wiFrontside) {
+                            if (!mediaPush(media, internal)) { overflow = true; break; }
+                        } else {
+                            mediaErase(media, internal);
+                        }
+                    }
+                }
+                // scatter(current medium, interaction.point(), hit point), :88-94 and :186-197
+                const int medium = mediaTop(media);
+                random.dimension = mediumBase(bounce);
+                ScatterEvent event;
+                event.scattered = false; event.point = origin;
+                const Rgb Ld = scatter(medium, origin, next.point, random, &event);
+                if (event.scattered) {
+                    SHADE_REGION(9, true);   // scatter events
+                    // IntegrationResult::weight: sigma_s / sigma_t (src/homogeneous_medium.cpp:64), the grid's albedo (src/grid_medium.cpp:212)
+                    const DMedium &record = context.media[medium];
+                    Rgb weight = rgb(record.sigmaS[0] / record.sigmaT[0], record.sigmaS[1] / record.sigmaT[1], record.sigmaS[2] / record.sigmaT[2]);   // Color / Color, src/color.cpp:116-125
+                    if constexpr (GRID) {
+                        if (record.kind == kMediumGrid) { weight = rgb(scene.grids[record.grid].albedo); }
+                    }
+                    modulation = modulation * weight;
+                    result = result + Ld * modulation;   // not gated by the bounce window (:99-101)
+                    random.dimension = phaseBase(bounce);
+                    direction = phaseSample<TRAITS::pairedTrig>(random);
+                    origin = event.point;
+                    surface = false;
+                } else {
+                    random.dimension = vertexBase(bounce);
+                    prepareLobes<TRAITS>(materials[next.material], next);
+                    bsdfSample = volumeMaterialSample<TRAITS>(materials[next.material], next, random);
+                    last = next;
+                    const bool direct = checkCounts(p.startBounce, p.lastBounce, bounce);
+                    random.dimension = vertexBase(bounce) + 3;
+                    const Rgb Ld = vertexLighting(last, medium, materials[last.material], bsdfSample, random, direct, !checkDone(p.lastBounce, bounce + 1));
+                    if (direct) { result = result + Ld * modulation; }
+                    origin = last.point;
+                    direction = bsdfSample.wiWorld;
+                    surface = true;
+                }
+            }
+            // a fifth nested medium: the sample is dropped, and counted with the non-finite ones (the caller's test)
+            if (overflow) { return rgb(__builtin_nanf("")); }
+            return color + result;
+        } else {
         // ---- VolumePathTracer::L, src/volume_path_tracer.cpp:14-99
         int medium = -1;
         random.dimension = vertexBase(1);
@@ -3554,6 +3649,7 @@ __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTri
             }
         }
         return color + result;
+        }
     };
 
     unsigned long long samplesDone = 0;
@@ -3595,6 +3691,36 @@ template <int STACK, bool SMALL>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_volume_grid(RenderParams p, SmallTris smallTris)
 {
     pathVolume<false, STACK, SMALL, TraitsAll, false, true>(p, smallTris);
+}
+
+// BasicVolumeIntegrator (multiple scattering, volume.h): generic traits, pair-of-triangles phase 1, the material table read from
+// memory, as the grid family; eight instantiations in all
+template <int STACK, bool SMALL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_scatter(RenderParams p, SmallTris smallTris)
+{
+    pathVolume<false, STACK, SMALL, TraitsAll, false, false, true>(p, smallTris);
+}
+
+template <int STACK, bool SMALL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_scatter_grid(RenderParams p, SmallTris smallTris)
+{
+    pathVolume<false, STACK, SMALL, TraitsAll, false, true, true>(p, smallTris);
+}
+
+// Test hook behind pathed_hip_debug_phase_samples: one thread per record, phaseSample on the record's two numbers
+struct ScriptedPair {
+    float u[2];
+    int taken;
+    __device__ float next() { const float value = u[taken & 1]; taken++; return value; }
+};
+__global__ __launch_bounds__(kBlock) void k_debug_phase_samples(int n, const float *u, float *out)
+{
+    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (i >= n) { return; }
+    ScriptedPair random;
+    random.u[0] = u[2 * (size_t)i]; random.u[1] = u[2 * (size_t)i + 1]; random.taken = 0;
+    const V3 direction = phaseSample<TraitsAll::pairedTrig>(random);
+    out[3 * (size_t)i] = direction.x; out[3 * (size_t)i + 1] = direction.y; out[3 * (size_t)i + 2] = direction.z;
 }
 
 // ------------------------------------------------------------------------- scene set-up

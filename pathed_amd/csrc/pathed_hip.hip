@@ -2084,10 +2084,16 @@ static bool fillUnitOrder(RenderParams &q, int order, int width, int height, int
 // src/path_tracer.cpp:79-216), every volumetric query degenerates to the regular one and no segment scatters -- the oracle's
 // two integrators and k_path_volume / the path-tracer kernels give the same floats there (tests/test_gpu_volume.py).  Such a
 // scene therefore runs the path tracer's kernels (fused or wavefront: one path per lane with no refill is 0.5-0.6x of them);
-// PathedSceneOptions.generic_kernels = 1 keeps k_path_volume, for that very comparison.
+// PathedSceneOptions.generic_kernels = 1 keeps k_path_volume, for that very comparison.  The same holds for
+// BasicVolumeIntegrator and k_path_scatter: without a medium no segment scatters and the stack never holds one.
+static bool volumeIntegrator(const PathedScene *scene)
+{
+    return scene->integrator == PATHED_INTEGRATOR_VOLUME_PATH_TRACER || scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME;
+}
+
 static bool usesVolumeKernel(const PathedScene *scene)
 {
-    if (scene->integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER) { return false; }
+    if (!volumeIntegrator(scene)) { return false; }
     return scene->hasContainers || scene->device.nMedia > 0 || scene->options.generic_kernels != 0;
 }
 
@@ -2268,7 +2274,25 @@ static int renderPassVolume(PathedScene *scene, const Pass &pass)
         const auto run = [&](void (*kernel)(RenderParams, SmallTris)) {
             hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, quads ? scene->smallItems : scene->smallTris);
         };
-        if (!scene->gridsHost.empty()) {
+        if (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME) {
+            // BasicVolumeIntegrator: k_path_scatter / k_path_scatter_grid<STACK, SMALL>, the generic set, pair-of-triangles
+            // phase 1, the material table read from memory (eight instantiations in all)
+            params.smallQuads = 0;
+            params.scene.leafTris = scene->leafTris.ptr;
+            const size_t scatterLds = (size_t)((small ? 8 : scene->stackRows) + 1) * kBlock * sizeof(int);
+            const bool grids = !scene->gridsHost.empty();
+            const auto runScatter = [&](void (*plain)(RenderParams, SmallTris), void (*withGrids)(RenderParams, SmallTris)) {
+                hipLaunchKernelGGL(grids ? withGrids : plain, grid, dim3(kBlock), scatterLds, stream, params, scene->smallTris);
+            };
+            if (small) { runScatter(k_path_scatter<8, true>, k_path_scatter_grid<8, true>); }
+            else {
+                switch (scene->stackRows) {
+                case 8: runScatter(k_path_scatter<8, false>, k_path_scatter_grid<8, false>); break;
+                case 16: runScatter(k_path_scatter<16, false>, k_path_scatter_grid<16, false>); break;
+                default: runScatter(k_path_scatter<22, false>, k_path_scatter_grid<22, false>); break;
+                }
+            }
+        } else if (!scene->gridsHost.empty()) {
             // a voxel-grid medium: the generic set, pair-of-triangles phase 1, the material table read from memory (four
             // instantiations in all; params.smallQuads is 0 where no instantiation reads the item records)
             params.smallQuads = 0;
@@ -2660,10 +2684,10 @@ int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
         FeatureBuffers none = { nullptr, nullptr, nullptr, nullptr };
         return launchFeatures(scene, seed, spp_begin, spp_count, start_bounce, -1, true, d_accum_rgb_sum, none, (hipStream_t)stream_handle);
     }
-    if (scene->hasContainers && scene->integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER) {
+    if (scene->hasContainers && !volumeIntegrator(scene)) {
         return fail(PATHED_E_UNSUPPORTED, "the scene has passthrough (medium container) surfaces: select the VolumePathTracer integrator (pathed_hip_set_integrator)");
     }
-    if (!scene->gridsHost.empty() && scene->integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER) {
+    if (!scene->gridsHost.empty() && !volumeIntegrator(scene)) {
         return fail(PATHED_E_UNSUPPORTED, "a scene with a voxel-grid medium renders with the VolumePathTracer integrator only (pathed_hip_set_integrator)");
     }
     SELECT_DEVICE(scene);
@@ -2745,7 +2769,8 @@ int pathed_hip_scene_set_camera(PathedScene *scene, const PathedCamera *camera)
 int pathed_hip_set_integrator(PathedScene *scene, int integrator)
 {
     if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
-    if (integrator != PATHED_INTEGRATOR_PATH_TRACER && integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER && integrator != PATHED_INTEGRATOR_ALBEDO) {
+    if (integrator != PATHED_INTEGRATOR_PATH_TRACER && integrator != PATHED_INTEGRATOR_VOLUME_PATH_TRACER && integrator != PATHED_INTEGRATOR_ALBEDO
+        && integrator != PATHED_INTEGRATOR_BASIC_VOLUME) {
         return fail(PATHED_E_INVALID, "unknown integrator");
     }
     scene->integrator = integrator;
@@ -2980,6 +3005,27 @@ int pathed_hip_grid_queries(PathedScene *scene, int medium_index, size_t n, cons
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(transmittance, deviceTransmittance.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(distance, deviceDistance.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
+    return PATHED_OK;
+}
+
+int pathed_hip_debug_phase_samples(PathedScene *scene, size_t n, const float *u, float *out)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (n == 0) { return PATHED_OK; }
+    if (!u || !out) { return fail(PATHED_E_INVALID, "null record or result buffer"); }
+    if (n > (size_t)1 << 20) { return fail(PATHED_E_INVALID, "too many records in one call"); }
+    for (size_t i = 0; i < 2 * n; i++) {
+        if (!(u[i] >= 0.f && u[i] <= 1.f)) { return fail(PATHED_E_INVALID, "phase samples: random numbers lie in [0, 1]"); }
+    }
+    SELECT_DEVICE(scene);
+    DeviceBuffer<float> deviceIn, deviceOut;
+    HIP_TRY(deviceIn.upload(std::vector<float>(u, u + 2 * n)));
+    HIP_TRY(deviceOut.allocate(3 * n));
+    HIP_TRY(hipMemset(deviceOut.ptr, 0, 3 * n * sizeof(float)));
+    hipLaunchKernelGGL(k_debug_phase_samples, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, (int)n, deviceIn.ptr, deviceOut.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, deviceOut.ptr, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
     return PATHED_OK;
 }
 
@@ -3263,7 +3309,7 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
     out->bvh_build_ms = scene->bvhBuildMs;
     out->bvh_builder = (uint32_t)scene->bvhBuilder;
     out->trace_launches_all = (uint32_t)scene->traceLaunchesAll;
-    out->path_kernel = scene->lastCallFeatures ? 8u : usesVolumeKernel(scene) ? 4u : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
+    out->path_kernel = scene->lastCallFeatures ? 8u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? 9u : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
     if (tuningEnv("PATHED_SHADE_PROFILE")) {   // counters exist in -DPATHED_SHADE_PROFILE builds only
         static const char *regions[11] = { "all waves", "active slots", "makeIsect (hit)", "camera-ray vertex", "finish previous MIS term",
                                            "new vertex: BSDF sample", "light sampling", "sample finished", "startSample (regeneration)", "shadow ray pushed",
@@ -3315,10 +3361,11 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
     }
 #endif
     if (tuningEnv("PATHED_VOLUME_PROFILE")) {   // the same counters in k_path_volume (-DPATHED_SHADE_PROFILE builds)
-        static const char *regions[9] = { "samples", "camera-ray query", "bounce-loop iterations", "segment query (no direct lighting before)",
-                                          "medium event: occlusion query", "direct lighting at a vertex", "light sample: occlusion query",
-                                          "BSDF sample: closest query", "seen through a container: query" };
-        for (int r = 0; r < 9; r++) {
+        // (region 3 and 9: k_path_scatter only -- the query of the ray that leaves a scatter event, and the scatter events)
+        static const char *regions[10] = { "samples", "camera-ray query", "bounce-loop iterations", "segment query (no direct lighting before)",
+                                           "medium event: occlusion query", "direct lighting at a vertex", "light sample: occlusion query",
+                                           "BSDF sample: closest query", "seen through a container: query", "scatter events" };
+        for (int r = 0; r < 10; r++) {
             const unsigned long long waves = device[kStatShadeProfile + 2 * r], lanes = device[kStatShadeProfile + 2 * r + 1];
             fprintf(stderr, "[pathed] k_path_volume %-44s waves %12llu  (%.3f per sample-wave)  lanes per wave %.1f\n", regions[r], waves,
                     device[kStatShadeProfile] ? (double)waves / (double)device[kStatShadeProfile] : 0.0, waves ? (double)lanes / (double)waves : 0.0);

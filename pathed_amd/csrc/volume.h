@@ -246,4 +246,64 @@ __device__ inline BSDFSample volumeMaterialSample(const DMaterial &m, const Isec
 // dimensions of the medium's distance sample (+0) and light sample (+1..3) on the segment that ends at `vertex`
 __device__ inline uint32_t mediumBase(int vertex) { return 0x4000u + 4u * (uint32_t)(vertex - 1); }
 
+// ---- BasicVolumeIntegrator (src/basic_volume_integrator.cpp): multiple scattering
+// dimensions of the phase sample of a scatter event at bounce `bounce`
+__device__ inline uint32_t phaseBase(int bounce) { return 0x8000u + 2u * (uint32_t)(bounce - 1); }
+
+// Phase::sample (include/phase.h) = UniformSampleSphere, src/monte_carlo.cpp:43-52: isotropic, whatever the direction of arrival
+template <bool PAIRED = false, typename RNG>
+__device__ inline V3 phaseSample(RNG &random)
+{
+    const float z = random.next() * 2.f - 1;
+    const float r = sqrtf(fmaxf(0.f, 1.f - z * z));
+    const float phi = twoPiTimes(random.next());
+    float cosPhi, sinPhi;
+    cosSin<PAIRED>(phi, &cosPhi, &sinPhi);
+    const float x = r * cosPhi;
+    const float y = r * sinPhi;
+    return v3(x, z, y);
+}
+
+// The media a path is inside of, innermost last: the reference's std::vector<std::shared_ptr<Medium>> with room for four,
+// -1 = "no medium" (the inside of a glass ball is an entry like any other).  Four named words and selects rather than an
+// indexed array: an array indexed by `depth` would live in scratch, and the kernel spills as it is.
+static const int kMediumStackDepth = 4;
+struct MediumStack {
+    int entry0, entry1, entry2, entry3;
+    int depth;
+};
+
+__device__ inline void mediaClear(MediumStack &s) { s.entry0 = -1; s.entry1 = -1; s.entry2 = -1; s.entry3 = -1; s.depth = 0; }
+
+// currentMediumPtr, :17-23
+__device__ inline int mediaTop(const MediumStack &s)
+{
+    return s.depth == 0 ? -1 : s.depth == 1 ? s.entry0 : s.depth == 2 ? s.entry1 : s.depth == 3 ? s.entry2 : s.entry3;
+}
+
+// push_back; false when the stack is full (the caller drops the sample)
+__device__ inline bool mediaPush(MediumStack &s, int medium)
+{
+    if (s.depth >= kMediumStackDepth) { return false; }
+    if (s.depth == 0) { s.entry0 = medium; }
+    else if (s.depth == 1) { s.entry1 = medium; }
+    else if (s.depth == 2) { s.entry2 = medium; }
+    else { s.entry3 = medium; }
+    s.depth++;
+    return true;
+}
+
+// std::find + erase, :166-169: the FIRST entry equal to `medium` goes, the ones above it move down
+__device__ inline void mediaErase(MediumStack &s, int medium)
+{
+    const int at = (s.depth > 0 && s.entry0 == medium) ? 0 : (s.depth > 1 && s.entry1 == medium) ? 1
+        : (s.depth > 2 && s.entry2 == medium) ? 2 : (s.depth > 3 && s.entry3 == medium) ? 3 : -1;
+    if (at < 0) { return; }
+    if (at <= 0) { s.entry0 = s.entry1; }
+    if (at <= 1) { s.entry1 = s.entry2; }
+    if (at <= 2) { s.entry2 = s.entry3; }
+    s.entry3 = -1;
+    s.depth--;
+}
+
 }  // namespace pathed

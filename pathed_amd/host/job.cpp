@@ -78,6 +78,9 @@ std::shared_ptr<Integrator> Job::integrator() const
     } else if (name == "VolumePathTracer") {
         // src/job.cpp:71-72: participating media behind passthrough containers
         return std::make_shared<HipPathTracer>(m_bounceController, PATHED_INTEGRATOR_VOLUME_PATH_TRACER);
+    } else if (name == "BasicVolumeIntegrator") {
+        // src/job.cpp:73-74: multiple scattering, a stack of media
+        return std::make_shared<HipPathTracer>(m_bounceController, PATHED_INTEGRATOR_BASIC_VOLUME);
     } else if (name == "AlbedoIntegrator") {
         // src/job.cpp:91: a SampleIntegrator whose L is material->albedo(intersection)
         return std::make_shared<HipPathTracer>(m_bounceController, PATHED_INTEGRATOR_ALBEDO);

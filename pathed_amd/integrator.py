@@ -266,10 +266,20 @@ class HipScene:
                                                                      pointer(records), pointer(out)), "pathed_hip_debug_shading_queries")
         return out
 
+    def phase_samples(self, u):
+        """The device's phase-function sample (pathed_hip_debug_phase_samples) on scripted numbers: u (n, 2) in [0, 1] ->
+        directions (n, 3) float32, (r cos phi, z, r sin phi) with z = 2 u[0] - 1 and phi = 2 pi u[1]."""
+        u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+        out = np.zeros((u.shape[0], 3), dtype=np.float32)
+        pointer = lambda array: array.ctypes.data_as(C.POINTER(C.c_float))
+        _check(self._lib, self._lib.pathed_hip_debug_phase_samples(self._handle, u.shape[0], pointer(u), pointer(out)), "pathed_hip_debug_phase_samples")
+        return out
+
     def set_integrator(self, name):
-        """"PathTracer" (default), "VolumePathTracer" or "AlbedoIntegrator" (reference src/job.cpp:65-97)."""
+        """"PathTracer" (default), "VolumePathTracer", "BasicVolumeIntegrator" or "AlbedoIntegrator" (reference src/job.cpp:65-97)."""
         code = {"PathTracer": _capi.INTEGRATOR_PATH_TRACER, "DataParallelIntegrator": _capi.INTEGRATOR_PATH_TRACER,
-                "VolumePathTracer": _capi.INTEGRATOR_VOLUME_PATH_TRACER, "AlbedoIntegrator": _capi.INTEGRATOR_ALBEDO}[name]
+                "VolumePathTracer": _capi.INTEGRATOR_VOLUME_PATH_TRACER, "AlbedoIntegrator": _capi.INTEGRATOR_ALBEDO,
+                "BasicVolumeIntegrator": _capi.INTEGRATOR_BASIC_VOLUME}[name]
         _check(self._lib, self._lib.pathed_hip_set_integrator(self._handle, code), "pathed_hip_set_integrator")
 
     def set_stats_mode(self, count=False, time_kernels=False, time_sampled=False):
@@ -366,7 +376,7 @@ class PathTracer:
         return image
 
 
-INTEGRATOR_NAMES = ("PathTracer", "DataParallelIntegrator", "VolumePathTracer", "AlbedoIntegrator")
+INTEGRATOR_NAMES = ("PathTracer", "DataParallelIntegrator", "VolumePathTracer", "AlbedoIntegrator", "BasicVolumeIntegrator")
 FEATURE_NAMES = ("albedo", "normal", "depth")
 
 

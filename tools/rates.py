@@ -2,7 +2,7 @@
 """Msamples/s of a list of scenes through the C ABI, one process, interleaved repeats; variants are PathedSceneOptions
 (the product library reads no environment variable), images of the variants of a scene compared bit for bit.
 
-    tools/rates.py [--spp 256] [--repeats 3] [--scenes C2,ON,GGX,GL,GLASS,C3,C4,C5,VOL,SMOKE] [--variants default,generic]
+    tools/rates.py [--spp 256] [--repeats 3] [--scenes C2,ON,GGX,GL,GLASS,C3,C4,C5,VOL,SMOKE,VOL-MS,SMOKE-MS] [--variants default,generic]
                    [--lib other.so]   # the second column from another build of the library (a child process per library)
 
 Variants: name or name=opt:value+opt:value, e.g. "wave=shade_kernel:wave", "front=shade_kernel:per-slot".
@@ -30,6 +30,8 @@ SCENES = {
     "GLASS": ("scenes/cornell-glass.json", 1024, 1024, "PathTracer"),
     "VOL": ("scenes/cornell-medium.json", 1024, 1024, "VolumePathTracer"),
     "SMOKE": ("scenes/cornell-smoke.json", 1024, 1024, "VolumePathTracer"),   # a voxel-grid medium (k_path_volume_grid)
+    "VOL-MS": ("scenes/cornell-medium.json", 1024, 1024, "BasicVolumeIntegrator"),   # multiple scattering (k_path_scatter)
+    "SMOKE-MS": ("scenes/cornell-smoke.json", 1024, 1024, "BasicVolumeIntegrator"),   # ... in a voxel grid (k_path_scatter_grid)
 }
 PRESETS = {
     "default": {},
