@@ -40,7 +40,8 @@ extern "C" {
 /* Additions that leave PathedSceneDesc unchanged (no version bump): PathedSceneOptions /
  * pathed_hip_scene_create_ex (per-scene device and tuning), pathed_hip_measure_valu,
  * pathed_hip_accum_add / pathed_hip_accum_copy_peer (multi-GPU fan-in of the radiance sums),
- * PathedFeatureBuffers / pathed_hip_render_features[_device] (first-hit feature images), PATHED_INTEGRATOR_ALBEDO. */
+ * PathedFeatureBuffers / pathed_hip_render_features[_device] (first-hit feature images), PATHED_INTEGRATOR_ALBEDO,
+ * pathed_hip_render_moments[_device] / PathedNoise / pathed_hip_noise_estimate_device (per-pixel second moments and the noise figure). */
 
 /* error codes */
 #define PATHED_OK            0
@@ -426,6 +427,49 @@ int pathed_hip_render_features_device(PathedScene *scene, uint64_t seed, uint32_
  * order, onto what they hold: 3 + 5 samples in two calls are the 8 of one call, bit for bit */
 int pathed_hip_render_features(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
                                float *albedo, float *normal, float *depth, float *hits);
+
+/* Per-pixel second moments: the render call that also keeps, beside the radiance sums, the per-channel sums of the SQUARED
+ * sample colours -- the third thing a denoiser or an adaptive scheme wants, and what "render until the image is this clean"
+ * is decided on.  The path kernels are the render calls' own: with one sample per unit every sample's colour has its own
+ * entry in the pass's unit buffer, and the kernel that ends a pass adds a pixel's entries x to the sum and x * x (a multiply,
+ * then an add) to the squares, in sample order.
+ *   - d_rgb_sum gets exactly the floats pathed_hip_render_device would give.
+ *   - both buffers (3*W*H floats, layout of the radiance sums) CONTINUE from their contents: any split of [0, n) into calls
+ *     and internal passes gives the same floats.  A dropped (non-finite) sample adds zero to both.
+ *   - PATHED_E_INVALID, and nothing is launched: a null buffer; a scene whose samples-per-unit is not 1 (a unit's entry is then
+ *     the sum of a group of samples, and the last group of a call is ragged).
+ *   - PATHED_E_UNSUPPORTED, and nothing is launched: PATHED_INTEGRATOR_ALBEDO, whose render calls run the feature kernel and
+ *     have no unit buffer.
+ * Precision: the squares are summed in fp32, as the radiance sums are.  The variance Q / n - m * m (below) cancels once a
+ * pixel's relative noise falls below about 1e-3 -- far below any sensible target -- and is clamped at zero there. */
+int pathed_hip_render_moments_device(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                                     int start_bounce, int last_bounce,
+                                     float *d_rgb_sum, float *d_rgb_sq_sum, void *stream);
+/* buffers in HOST memory; ADDS the call's two sums to them like pathed_hip_render (the call's own sums start at zero) */
+int pathed_hip_render_moments(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                              int start_bounce, int last_bounce, float *rgb_sum, float *rgb_sq_sum);
+
+/* The noise figure of an image from its two sum images over n_samples >= 2 samples per pixel.  Per pixel, with sums S_c,
+ * square sums Q_c, n = (float)n_samples and a floor f > 0, all in fp32 and in this order (n and n / (n - 1) computed once):
+ *     m_c = S_c / n
+ *     d_c = Q_c / n - m_c * m_c          v_c = max(d_c, 0) * (n / (n - 1))
+ *     e   = sqrt(((v_r + v_g) + v_b) / n) / (((m_r + m_g) + m_b) + f)
+ * i.e. the standard error of the pixel's mean over its brightness; f keeps black pixels from dominating.  A non-finite e
+ * counts as 0 and in invalid_pixels.  mean_error is the sum of e over the pixels in double -- per block of 256 pixels in
+ * pixel order, the blocks in order: deterministic -- over W*H; max_error the largest e; pixels_above the pixels with
+ * e > threshold.  d_error (W*H floats, device memory) receives e per pixel, or is NULL.  Device pointers live on the scene's
+ * device; the work runs on `stream` (NULL = default stream) and the call returns when it has completed.
+ * PATHED_E_INVALID: n_samples < 2, floor <= 0, out->struct_size != sizeof(PathedNoise), a null sum buffer or result. */
+typedef struct PathedNoise {
+    uint32_t struct_size;      /* sizeof(PathedNoise), set by the caller */
+    uint32_t invalid_pixels;
+    double   mean_error;
+    double   max_error;
+    uint64_t pixels_above;
+} PathedNoise;
+int pathed_hip_noise_estimate_device(PathedScene *scene, const float *d_rgb_sum, const float *d_rgb_sq_sum,
+                                     uint32_t n_samples, float floor, float threshold,
+                                     float *d_error, PathedNoise *out, void *stream);
 
 /* Heterogeneous media: the reference's GridMedium (src/grid_medium.cpp), a voxel grid of extinction densities that is
  * looked up trilinearly and walked cell by cell (pathed_amd/csrc/grid_medium.h).  PathedSceneDesc and PathedMedium do not

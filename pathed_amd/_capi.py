@@ -189,6 +189,11 @@ class PathedFeatureBuffers(C.Structure):
     _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p)]
 
 
+class PathedNoise(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("invalid_pixels", C.c_uint32), ("mean_error", C.c_double), ("max_error", C.c_double),
+                ("pixels_above", C.c_uint64)]
+
+
 class PathedValuClocks(C.Structure):
     _fields_ = [(name, C.c_double) for name in (
         "rate", "shader_clock_mhz", "wall_clock_mhz", "peak_clock_mhz", "wave_ticks_per_instruction",
@@ -223,6 +228,9 @@ HIP_SYMBOLS = [
     "pathed_hip_render_device",
     "pathed_hip_render_features",
     "pathed_hip_render_features_device",
+    "pathed_hip_render_moments",
+    "pathed_hip_render_moments_device",
+    "pathed_hip_noise_estimate_device",
     "pathed_hip_trace",
     "pathed_hip_debug_small_candidates",
     "pathed_hip_debug_light_records",
@@ -331,6 +339,13 @@ def load_hip():
     lib.pathed_hip_render_features.restype = C.c_int
     lib.pathed_hip_render_features_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(PathedFeatureBuffers), vp]
     lib.pathed_hip_render_features_device.restype = C.c_int
+    if hasattr(lib, "pathed_hip_render_moments_device"):   # (an older build of the same ABI, as above)
+        lib.pathed_hip_render_moments_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]
+        lib.pathed_hip_render_moments_device.restype = C.c_int
+        lib.pathed_hip_render_moments.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, fp, fp]
+        lib.pathed_hip_render_moments.restype = C.c_int
+        lib.pathed_hip_noise_estimate_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_float, C.c_float, vp, C.POINTER(PathedNoise), vp]
+        lib.pathed_hip_noise_estimate_device.restype = C.c_int
     lib.pathed_hip_trace.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, vp]
     lib.pathed_hip_trace.restype = C.c_int
     lib.pathed_hip_debug_small_candidates.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint64)]

@@ -1819,6 +1819,120 @@ __global__ __launch_bounds__(kBlock) void k_resolve(RenderParams p)
     out[2] = b;
 }
 
+// k_resolve with second moments (pathed_hip_render_moments[_device]): with one sample per unit a pixel's entries ARE its
+// samples' colours, so the same pass over the same bytes also continues the per-channel sum of squares,
+// q = q + (x * x) per entry in chunk order (a multiply and an add: the build has -ffp-contract=off).  The radiance sum gets
+// exactly k_resolve's additions.  A dropped sample's entry is zero and adds zero to both.
+struct MomentsParams {
+    const float4 *chunkBuf;          // RenderState::chunkBuf of the pass
+    int nPixels;
+    int chunksPerPixel;
+    float *sum;                      // 3 * nPixels, continued
+    float *squares;                  // 3 * nPixels, continued
+};
+
+__global__ __launch_bounds__(kBlock) void k_resolve_moments(MomentsParams p)
+{
+    const int pixel = blockIdx.x * kBlock + threadIdx.x;
+    if (pixel >= p.nPixels) { return; }
+    float *out = p.sum + 3 * (size_t)pixel;
+    float *outSquares = p.squares + 3 * (size_t)pixel;
+    float r = out[0], g = out[1], b = out[2];
+    float rr = outSquares[0], gg = outSquares[1], bb = outSquares[2];
+    int chunk = 0;
+    for (; chunk + 8 <= p.chunksPerPixel; chunk += 8) {
+        float4 partial[8];
+        #pragma unroll
+        for (int k = 0; k < 8; k++) { partial[k] = p.chunkBuf[(size_t)(chunk + k) * p.nPixels + pixel]; }
+        #pragma unroll
+        for (int k = 0; k < 8; k++) {
+            r += partial[k].x;
+            g += partial[k].y;
+            b += partial[k].z;
+            rr = rr + partial[k].x * partial[k].x;
+            gg = gg + partial[k].y * partial[k].y;
+            bb = bb + partial[k].z * partial[k].z;
+        }
+    }
+    for (; chunk < p.chunksPerPixel; chunk++) {
+        const float4 partial = p.chunkBuf[(size_t)chunk * p.nPixels + pixel];
+        r += partial.x;
+        g += partial.y;
+        b += partial.z;
+        rr = rr + partial.x * partial.x;
+        gg = gg + partial.y * partial.y;
+        bb = bb + partial.z * partial.z;
+    }
+    out[0] = r;
+    out[1] = g;
+    out[2] = b;
+    outSquares[0] = rr;
+    outSquares[1] = gg;
+    outSquares[2] = bb;
+}
+
+// The noise figure of an image from its two sum images (pathed_hip_noise_estimate_device; the formula and its order of
+// operations are the header's).  One lane per pixel; a block's first lane adds the block's errors in double, in lane order,
+// and writes one partial: the host adds the partials in block order, so the mean is deterministic.
+struct NoisePartial {
+    double sum;                      // of the block's errors
+    float maxError;
+    unsigned int above;              // pixels with error > threshold
+    unsigned int invalid;            // pixels whose error was not finite (counted as 0)
+    unsigned int unused;
+};
+
+struct NoiseParams {
+    const float *sum;                // 3 * nPixels
+    const float *squares;            // 3 * nPixels
+    int nPixels;
+    float n;                         // samples, as fp32
+    float bessel;                    // n / (n - 1)
+    float floor;
+    float threshold;
+    float *error;                    // nPixels, or null
+    NoisePartial *partials;          // one per block
+};
+
+__global__ __launch_bounds__(kBlock) void k_noise(NoiseParams p)
+{
+    __shared__ float errors[kBlock];
+    __shared__ unsigned int invalid[kBlock];
+    const int pixel = blockIdx.x * kBlock + threadIdx.x;
+    float e = 0.f;
+    unsigned int bad = 0u;
+    if (pixel < p.nPixels) {
+        const float *s = p.sum + 3 * (size_t)pixel;
+        const float *q = p.squares + 3 * (size_t)pixel;
+        float m[3], v[3];
+        #pragma unroll
+        for (int c = 0; c < 3; c++) {
+            m[c] = s[c] / p.n;
+            const float d = q[c] / p.n - m[c] * m[c];
+            v[c] = (d > 0.f ? d : 0.f) * p.bessel;
+        }
+        e = sqrtf(((v[0] + v[1]) + v[2]) / p.n) / (((m[0] + m[1]) + m[2]) + p.floor);
+        if (!isfinite(e)) { e = 0.f; bad = 1u; }
+        if (p.error) { p.error[pixel] = e; }
+    }
+    errors[threadIdx.x] = e;
+    invalid[threadIdx.x] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int first = blockIdx.x * kBlock;
+        const int lanes = p.nPixels - first < kBlock ? p.nPixels - first : kBlock;
+        NoisePartial partial = { 0.0, 0.f, 0u, 0u, 0u };
+        for (int lane = 0; lane < lanes; lane++) {
+            const float value = errors[lane];
+            partial.sum += (double)value;
+            if (value > partial.maxError) { partial.maxError = value; }
+            if (value > p.threshold) { partial.above++; }
+            partial.invalid += invalid[lane];
+        }
+        p.partials[blockIdx.x] = partial;
+    }
+}
+
 // Tuning builds only (-DPATHED_SHADE_PROFILE): how many waves enter a region of k_shade and with how
 // many lanes -- lane utilisation per region (tools/shade_profile.py prints the table).
 #ifdef PATHED_SHADE_PROFILE

@@ -2104,10 +2104,28 @@ struct Pass {
     uint32_t begin, count;
     int startBounce, lastBounce;
     float *accum;
+    float *squares;   // per-channel sums of squares beside `accum` (pathed_hip_render_moments_device), or null
     hipStream_t stream;
     int nPixels, chunk, chunksPerPixel;
     unsigned int nUnits;
 };
+
+// The end of every pass: the units' partial sums onto the caller's sums, and, for a pass that carries a squares buffer,
+// their squares onto that (k_resolve_moments; such a pass has one sample per unit).
+static void launchResolve(const Pass &pass, const RenderParams &params, dim3 pixelGrid, hipStream_t stream)
+{
+    if (pass.squares) {
+        MomentsParams moments;
+        moments.chunkBuf = params.state.chunkBuf;
+        moments.nPixels = params.nPixels;
+        moments.chunksPerPixel = params.chunksPerPixel;
+        moments.sum = params.accum;
+        moments.squares = pass.squares;
+        hipLaunchKernelGGL(k_resolve_moments, pixelGrid, dim3(kBlock), 0, stream, moments);
+    } else {
+        hipLaunchKernelGGL(k_resolve, pixelGrid, dim3(kBlock), 0, stream, params);
+    }
+}
 
 // The launch parameters every kernel of the pass reads, and the unit order of pool `pool` of `pools` over nQueues queues.
 // Returns false when the unit ids of the pass do not fit 32 bits.
@@ -2187,7 +2205,7 @@ static int persistentPass(PathedScene *scene, const Pass &pass, int blocksPerCu,
     if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], pass.stream); }
     scene->traceLaunchesAll++;
     const dim3 pixelGrid((unsigned)((pass.nPixels + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_resolve, pixelGrid, dim3(kBlock), 0, pass.stream, params);
+    launchResolve(pass, params, pixelGrid, pass.stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(pass.stream));
 
@@ -2588,7 +2606,7 @@ static int renderPass(PathedScene *scene, const Pass &pass)
         }
     }
     const dim3 pixelGrid((unsigned)((nPixels + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(k_resolve, pixelGrid, block, 0, stream, params[0]);
+    launchResolve(pass, params[0], pixelGrid, stream);
     for (int h = 0; h < pools; h++) { HIP_TRY(hipStreamSynchronize(streams[h])); }
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipGetLastError());
@@ -2662,14 +2680,11 @@ static int launchFeatures(PathedScene *scene, uint64_t seed, uint32_t begin, uin
     return PATHED_OK;
 }
 
-extern "C" {
-
-int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
-                             uint32_t spp_begin, uint32_t spp_count,
-                             int start_bounce, int last_bounce,
-                             float *d_accum_rgb_sum, void *stream_handle, int blocking)
+// The body of pathed_hip_render_device and pathed_hip_render_moments_device: d_squares is null for the former, and a call
+// without it launches exactly what it always did.
+static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count, int start_bounce, int last_bounce,
+                      float *d_accum_rgb_sum, float *d_squares, void *stream_handle)
 {
-    (void)blocking;  // the iteration loop polls a device counter, so the call always completes
     if (!scene || !d_accum_rgb_sum) { return fail(PATHED_E_INVALID, "null scene or accumulation buffer"); }
     if (start_bounce < 0 || (last_bounce != -1 && start_bounce > last_bounce)) {
         return fail(PATHED_E_INVALID, "bounce window: need 0 <= startBounce <= lastBounce (or lastBounce == -1)");
@@ -2727,6 +2742,7 @@ int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
     pass.startBounce = start_bounce;
     pass.lastBounce = last_bounce;
     pass.accum = d_accum_rgb_sum;
+    pass.squares = d_squares;
     pass.stream = stream;
     pass.nPixels = scene->width * scene->height;
     pass.chunk = scene->samplesPerUnit;
@@ -2750,6 +2766,97 @@ int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
         scene->traceEvents.harvestAll();
         scene->shadeEvents.harvestAll();
     }
+    return PATHED_OK;
+}
+
+extern "C" {
+
+int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
+                             uint32_t spp_begin, uint32_t spp_count,
+                             int start_bounce, int last_bounce,
+                             float *d_accum_rgb_sum, void *stream_handle, int blocking)
+{
+    (void)blocking;  // the iteration loop polls a device counter, so the call always completes
+    return renderCall(scene, seed, spp_begin, spp_count, start_bounce, last_bounce, d_accum_rgb_sum, nullptr, stream_handle);
+}
+
+int pathed_hip_render_moments_device(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                                     int start_bounce, int last_bounce, float *d_rgb_sum, float *d_rgb_sq_sum, void *stream_handle)
+{
+    if (!scene || !d_rgb_sum || !d_rgb_sq_sum) { return fail(PATHED_E_INVALID, "null scene, sum buffer or sum-of-squares buffer"); }
+    if (scene->samplesPerUnit != 1) {
+        return fail(PATHED_E_INVALID, "second moments need one sample per unit (pathed_hip_set_samples_per_unit(scene, 1)): with more, "
+                                      "a unit's entry is the sum of a group of samples and the last group of a call is ragged");
+    }
+    if (scene->integrator == PATHED_INTEGRATOR_ALBEDO) {
+        return fail(PATHED_E_UNSUPPORTED, "second moments are not rendered under the albedo integrator: its render calls run the feature kernel, which has no unit buffer");
+    }
+    return renderCall(scene, seed, spp_begin, spp_count, start_bounce, last_bounce, d_rgb_sum, d_rgb_sq_sum, stream_handle);
+}
+
+int pathed_hip_render_moments(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                              int start_bounce, int last_bounce, float *rgb_sum, float *rgb_sq_sum)
+{
+    if (!scene || !rgb_sum || !rgb_sq_sum) { return fail(PATHED_E_INVALID, "null scene, sum buffer or sum-of-squares buffer"); }
+    SELECT_DEVICE(scene);
+    // one device buffer, the two images side by side, zeroed: the call's sums are ADDED to the caller's, as pathed_hip_render does
+    const size_t count = (size_t)3 * scene->width * scene->height;
+    DeviceBuffer<float> device;
+    HIP_TRY(device.allocate(2 * count));
+    HIP_TRY(hipMemset(device.ptr, 0, 2 * count * sizeof(float)));
+    const int code = pathed_hip_render_moments_device(scene, seed, spp_begin, spp_count, start_bounce, last_bounce, device.ptr, device.ptr + count, nullptr);
+    if (code != PATHED_OK) { return code; }
+    std::vector<float> host(2 * count);
+    HIP_TRY(hipMemcpy(host.data(), device.ptr, 2 * count * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < count; i++) {
+        rgb_sum[i] += host[i];
+        rgb_sq_sum[i] += host[count + i];
+    }
+    return PATHED_OK;
+}
+
+int pathed_hip_noise_estimate_device(PathedScene *scene, const float *d_rgb_sum, const float *d_rgb_sq_sum, uint32_t n_samples,
+                                     float floor, float threshold, float *d_error, PathedNoise *out, void *stream_handle)
+{
+    if (!scene || !d_rgb_sum || !d_rgb_sq_sum || !out) { return fail(PATHED_E_INVALID, "null scene, sum buffer, sum-of-squares buffer or result"); }
+    if (out->struct_size != sizeof(PathedNoise)) { return fail(PATHED_E_INVALID, "PathedNoise.struct_size does not match this library"); }
+    if (n_samples < 2) { return fail(PATHED_E_INVALID, "a noise estimate needs at least 2 samples per pixel"); }
+    if (!(floor > 0.f) || !std::isfinite(floor)) { return fail(PATHED_E_INVALID, "the noise floor must be a finite number > 0"); }
+    SELECT_DEVICE(scene);
+    hipStream_t stream = (hipStream_t)stream_handle;
+    const int nPixels = scene->width * scene->height;
+    const unsigned int blocks = (unsigned int)((nPixels + kBlock - 1) / kBlock);
+    DeviceBuffer<NoisePartial> partials;
+    HIP_TRY(partials.allocate(blocks));
+    NoiseParams params;
+    params.sum = d_rgb_sum;
+    params.squares = d_rgb_sq_sum;
+    params.nPixels = nPixels;
+    params.n = (float)n_samples;
+    params.bessel = params.n / (params.n - 1.f);
+    params.floor = floor;
+    params.threshold = threshold;
+    params.error = d_error;
+    params.partials = partials.ptr;
+    hipLaunchKernelGGL(k_noise, dim3(blocks), dim3(kBlock), 0, stream, params);
+    HIP_TRY(hipGetLastError());
+    std::vector<NoisePartial> host(blocks);
+    HIP_TRY(hipMemcpyAsync(host.data(), partials.ptr, blocks * sizeof(NoisePartial), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    double sum = 0.0;
+    float maxError = 0.f;
+    uint64_t above = 0;
+    uint32_t invalid = 0;
+    for (const NoisePartial &partial : host) {   // in block order
+        sum += partial.sum;
+        if (partial.maxError > maxError) { maxError = partial.maxError; }
+        above += partial.above;
+        invalid += partial.invalid;
+    }
+    out->invalid_pixels = invalid;
+    out->mean_error = sum / (double)nPixels;
+    out->max_error = (double)maxError;
+    out->pixels_above = above;
     return PATHED_OK;
 }
 

@@ -173,6 +173,7 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
     try {
         Job job(jobPath);
         const std::vector<std::string> features = job.features();   // (a bad name stops the job before it touches the output directory)
+        const Job::NoiseSettings noise = job.noise();                // (... and so does a bad noise key)
         job.init();
 
         const int width = job.width();
@@ -229,6 +230,7 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
         }
         integrator->setUseRccl(reduce == "rccl");
         integrator->setFeatures(features);
+        if (noise.collect) { integrator->setNoise(noise.target, noise.minSpp, noise.floor); }
         if (earlyComm) { integrator->adoptComm(earlyComm); earlyComm = nullptr; }
         const std::string metricsLevel = job.metricsLevel();
         if (metricsLevel != "full" && metricsLevel != "basic") { throw std::runtime_error("job: \"metrics\" must be \"full\" or \"basic\""); }
@@ -305,6 +307,15 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
             out << "  \"replica_seconds\": [";
             for (size_t i = 0; i < m.replicaSeconds.size(); i++) { out << (i ? ", " : "") << m.replicaSeconds[i]; }
             out << "],\n";
+            if (m.collectedMoments) {
+                out << "  \"noise\": [";
+                for (size_t i = 0; i < m.noise.size(); i++) {
+                    out << (i ? ", " : "") << "{\"spp\": " << m.noise[i].spp << std::setprecision(17) << ", \"mean_error\": " << m.noise[i].meanError
+                        << ", \"max_error\": " << m.noise[i].maxError << std::setprecision(9) << "}";
+                }
+                out << "],\n";
+                out << "  \"stopped_on_noise\": " << (m.stoppedOnNoise ? "true" : "false") << ",\n";
+            }
             out << "  \"dropped_samples\": " << stats.dropped_samples << "\n";
             out << "}\n";
         }

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -245,6 +246,30 @@ void Integrator::run(
         }
     }
     m_metrics.reduceMethod = replicas == 1 ? "none" : comm ? "rccl" : "peer-copy";
+
+    // second moments (setNoise): one squares buffer per replica beside its sums, and their total on replica 0
+    const bool wantMoments = m_collectMoments;
+    if (wantMoments && m_resume) { throw std::runtime_error("job: \"resume\" does not go with \"target_noise\" / \"stderr_image\": the state file holds no squares"); }
+    std::vector<float *> deviceSquares(replicas, nullptr);
+    float *totalSquares = nullptr;
+    struct MomentsCleanup {
+        Scene &scene;
+        std::vector<float *> &squares;
+        float *&total;
+        ~MomentsCleanup()
+        {
+            for (size_t r = 0; r < squares.size(); r++) { if (squares[r]) { pathed_hip_accum_free(scene.handle(r), squares[r]); } }
+            if (total) { pathed_hip_accum_free(scene.handle(0), total); }
+        }
+    } momentsCleanup{ scene, deviceSquares, totalSquares };
+    if (wantMoments) {
+        for (size_t r = 0; r < replicas; r++) {
+            if (pathed_hip_accum_alloc(scene.handle(r), floats, &deviceSquares[r]) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_alloc")); }
+        }
+        if (replicas > 1 && pathed_hip_accum_alloc(scene.handle(0), floats, &totalSquares) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_alloc")); }
+    }
+    m_metrics.collectedMoments = wantMoments;
+    std::vector<float> squaresLookup;
     ReplicaWorkers workers(replicas);
 
     std::vector<float> radianceLookup(floats, 0.f);
@@ -340,7 +365,7 @@ void Integrator::run(
             strongRange((unsigned)r, (unsigned)replicas, (unsigned)done, (unsigned)count, &first, &mine);
             if (mine == 0) { return; }
             const auto replicaBegin = std::chrono::steady_clock::now();
-            sampleImage(deviceSums[r], scene, r, first, mine);
+            sampleImage(deviceSums[r], deviceSquares[r], scene, r, first, mine);
             m_metrics.replicaSeconds[r] += std::chrono::duration<double>(std::chrono::steady_clock::now() - replicaBegin).count();
         });
         const auto end = std::chrono::steady_clock::now();
@@ -355,6 +380,8 @@ void Integrator::run(
 
         const bool checkpoint = (done & (done - 1)) == 0;
         const bool stopping = quit && *quit;
+        bool reachedTarget = false;
+        std::ostringstream noiseLine;
         if (checkpoint || done == primarySamples || stopping) {
             const auto reduceBegin = std::chrono::steady_clock::now();
             const float *source = deviceSums[0];
@@ -371,7 +398,37 @@ void Integrator::run(
                 }
                 source = total;
             }
+            // the squares are reduced exactly as the sums are
+            const float *sourceSquares = deviceSquares[0];
+            if (wantMoments && replicas > 1 && comm) {
+                std::vector<const float *> send(deviceSquares.begin(), deviceSquares.end());
+                if (pathed_hip_comm_reduce(comm, send.data(), totalSquares, floats) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_comm_reduce")); }
+                sourceSquares = totalSquares;
+            } else if (wantMoments && replicas > 1) {
+                if (pathed_hip_accum_copy_peer(scene.handle(0), totalSquares, scene.handle(0), deviceSquares[0], floats) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_copy_peer")); }
+                for (size_t r = 1; r < replicas; r++) {
+                    if (pathed_hip_accum_copy_peer(scene.handle(0), staging, scene.handle(r), deviceSquares[r], floats) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_copy_peer")); }
+                    if (pathed_hip_accum_add(scene.handle(0), totalSquares, staging, floats) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_add")); }
+                }
+                sourceSquares = totalSquares;
+            }
             if (pathed_hip_accum_download(scene.handle(0), source, floats, radianceLookup.data()) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_download")); }
+            if (wantMoments && done >= 2) {
+                squaresLookup.resize(floats);
+                if (pathed_hip_accum_download(scene.handle(0), sourceSquares, floats, squaresLookup.data()) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_download")); }
+                if ((checkpoint || done == primarySamples) && done >= m_minSpp) {
+                    PathedNoise figure;
+                    std::memset(&figure, 0, sizeof figure);
+                    figure.struct_size = sizeof figure;
+                    if (pathed_hip_noise_estimate_device(scene.handle(0), source, sourceSquares, (uint32_t)done, (float)m_noiseFloor, (float)m_targetNoise,
+                                                         nullptr, &figure, nullptr) != PATHED_OK) {
+                        throw std::runtime_error(hipError("pathed_hip_noise_estimate_device"));
+                    }
+                    m_metrics.noise.push_back({ done, figure.mean_error, figure.max_error });
+                    noiseLine << " noise: " << std::setprecision(6) << figure.mean_error;
+                    if (m_targetNoise > 0.0 && figure.mean_error <= m_targetNoise && done < primarySamples) { reachedTarget = true; }
+                }
+            }
             m_metrics.reduceSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - reduceBegin).count();
             m_metrics.reduces++;
 
@@ -394,16 +451,43 @@ void Integrator::run(
             if (checkpoint) { image.saveCheckpoint("auto"); }
             else if (done == primarySamples) { image.save("auto"); }
             if (checkpoint || done == primarySamples) { publishFeatures(done, checkpoint); }
+            if (wantMoments && done >= 2 && (checkpoint || done == primarySamples)) {
+                // auto-stderr*.exr: per-channel standard error of the mean, sqrt(v_c / n), in the header's fp32 order (standard
+                // error rather than variance: the files are HALF, and variances of 1e-5 would be mostly subnormal there)
+                Image stderrImage(width, height, image.outputDirectory());
+                stderrImage.setSpp(done);
+                const float n = (float)done, bessel = n / (n - 1.f);
+                for (int row = 0; row < height; row++) {
+                    for (int col = 0; col < width; col++) {
+                        const size_t index = (size_t)3 * ((size_t)row * width + col);
+                        float error[3];
+                        for (int c = 0; c < 3; c++) {
+                            const float mean = radianceLookup[index + c] / n;
+                            const float spread = squaresLookup[index + c] / n - mean * mean;
+                            const float variance = (spread > 0.f ? spread : 0.f) * bessel;
+                            error[c] = std::sqrt(variance / n);
+                        }
+                        stderrImage.set(row, col, error[0], error[1], error[2]);
+                    }
+                }
+                if (checkpoint) { stderrImage.saveCheckpoint("auto-stderr"); }
+                else { stderrImage.save("auto-stderr"); }
+            }
             saveState(radianceLookup, width, height, done);
         }
 
         std::ostringstream line;
         line << "[" << m_logPrefix << "] sample: " << done << "/" << primarySamples
              << std::fixed << std::setprecision(1)
-             << " (" << status.elapsedSeconds << "s elapsed)";
+             << " (" << status.elapsedSeconds << "s elapsed)" << noiseLine.str();
         std::cout << line.str() << std::endl;
 
         if (stopping) { break; }
+        if (reachedTarget) {
+            m_metrics.stoppedOnNoise = true;
+            std::cout << "[" << m_logPrefix << "] noise target " << m_targetNoise << " reached at " << done << " samples: stopping" << std::endl;
+            break;
+        }
     }
     m_metrics.lastSample = done;
     m_metrics.loopSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - loopBegin).count();
@@ -461,10 +545,20 @@ int Integrator::loadState(std::vector<float> &sums, int width, int height) const
     return header.done;
 }
 
-void HipPathTracer::sampleImage(float *deviceSums, Scene &scene, size_t replica, unsigned begin, unsigned count)
+void HipPathTracer::sampleImage(float *deviceSums, float *deviceSquares, Scene &scene, size_t replica, unsigned begin, unsigned count)
 {
     if (pathed_hip_set_integrator(scene.handle(replica), m_integrator) != PATHED_OK) {
         throw std::runtime_error(std::string("pathed_hip_set_integrator: ") + pathed_hip_last_error());
+    }
+    if (deviceSquares) {
+        const int code = pathed_hip_render_moments_device(
+            scene.handle(replica), m_seed, begin, count,
+            m_bounceController.startBounce(), m_bounceController.lastBounce(),
+            deviceSums, deviceSquares, nullptr);
+        if (code != PATHED_OK) {
+            throw std::runtime_error(std::string("pathed_hip_render_moments_device: ") + pathed_hip_last_error());
+        }
+        return;
     }
     const int code = pathed_hip_render_device(
         scene.handle(replica), m_seed, begin, count,

@@ -35,6 +35,10 @@ struct RenderMetrics {
     std::string reduceMethod = "none";     // "rccl" (pathed_hip_comm_reduce), "peer-copy" (hipMemcpyPeer + add) or "none" (one replica)
     std::string reduceFallback;            // why RCCL was not used, when it was asked for and is not
     std::vector<double> replicaSeconds;    // time each replica spent inside sampleImage
+    struct Noise { int spp; double meanError, maxError; };
+    std::vector<Noise> noise;              // the noise figure at every checkpoint it was estimated at (setNoise)
+    bool collectedMoments = false;         // the run rendered through pathed_hip_render_moments_device
+    bool stoppedOnNoise = false;           // ... and ended before `spp` because the figure reached the target
 };
 
 // Host-side Scene: the parsed description plus its upload (reference include/scene.h:83-130
@@ -110,13 +114,20 @@ public:
     // fall due -- one ray per sample -- so N GPUs give one GPU's feature images bit for bit.  The sums are not in auto.state:
     // a resumed run renders [0, done) of them again first (the random stream is counter-based: the straight run's bits).
     void setFeatures(const std::vector<std::string> &names) { m_features = names; }
+    // job keys "target_noise", "min_spp", "noise_floor", "stderr_image": the run renders through pathed_hip_render_moments_device
+    // (one squares buffer per replica, reduced exactly as the sums are and only when an image is due), writes the per-channel
+    // standard error of the mean, sqrt(v_c / n), as auto-stderr*.exr wherever it writes auto*.exr (from 2 samples on), and
+    // estimates the noise figure (pathed_hip_noise_estimate_device, on replica 0's device) at the power-of-two checkpoints
+    // from minSpp on and at the end.  With targetNoise > 0 it stops at the first such estimate at or below the target; `spp`
+    // stays the cap.  The squares are not in auto.state: such a job does not resume.
+    void setNoise(double targetNoise, int minSpp, double floor) { m_collectMoments = true; m_targetNoise = targetNoise; m_minSpp = minSpp; m_noiseFloor = floor; }
     const RenderMetrics &metrics() const { return m_metrics; }
 
 protected:
     // adds `count` samples of every pixel, starting at sample index `begin`, to the radiance sums
     // `deviceSums` that live on replica `replica`'s device (reference sampleImage adds exactly one
-    // sample to radianceLookup)
-    virtual void sampleImage(float *deviceSums, Scene &scene, size_t replica, unsigned begin, unsigned count) = 0;
+    // sample to radianceLookup), and their squares to `deviceSquares` when that is not null
+    virtual void sampleImage(float *deviceSums, float *deviceSquares, Scene &scene, size_t replica, unsigned begin, unsigned count) = 0;
 
     int m_spp = 1;
     unsigned long long m_seed = 1;
@@ -128,6 +139,10 @@ protected:
     int m_sppPerLaunch = 1024;
     bool m_resume = false;
     bool m_useRccl = true;
+    bool m_collectMoments = false;
+    double m_targetNoise = 0.0;   // 0 = none
+    int m_minSpp = 16;
+    double m_noiseFloor = 0.01;
     PathedComm *m_adoptedComm = nullptr;
     unsigned long long m_stateDigest = 0;
     std::string m_statePath;
@@ -145,7 +160,7 @@ public:
     {}
 
 protected:
-    void sampleImage(float *deviceSums, Scene &scene, size_t replica, unsigned begin, unsigned count) override;
+    void sampleImage(float *deviceSums, float *deviceSquares, Scene &scene, size_t replica, unsigned begin, unsigned count) override;
     int stateStartBounce() const override { return m_bounceController.startBounce(); }
     int stateLastBounce() const override { return m_bounceController.lastBounce(); }
 

@@ -70,6 +70,39 @@ std::vector<std::string> Job::features() const
     return names;
 }
 
+Job::NoiseSettings Job::noise() const
+{
+    NoiseSettings settings;
+    const Json &target = m_json["target_noise"];
+    if (!target.isNull()) {
+        if (!target.isNumber() || !(target.asNumber() > 0.0) || !(target.asNumber() < 1e30)) { throw std::runtime_error("job: \"target_noise\" must be a number > 0"); }
+        settings.target = target.asNumber();
+    }
+    const Json &minSpp = m_json["min_spp"];
+    if (!minSpp.isNull()) {
+        if (!minSpp.isNumber() || minSpp.asNumber() != (double)(long long)minSpp.asNumber() || minSpp.asNumber() < 2.0 || minSpp.asNumber() > 1e9) {
+            throw std::runtime_error("job: \"min_spp\" must be an integer >= 2");
+        }
+        settings.minSpp = (int)minSpp.asNumber();
+    }
+    const Json &floor = m_json["noise_floor"];
+    if (!floor.isNull()) {
+        if (!floor.isNumber() || !(floor.asNumber() > 0.0) || !(floor.asNumber() < 1e30)) { throw std::runtime_error("job: \"noise_floor\" must be a number > 0"); }
+        settings.floor = floor.asNumber();
+    }
+    const Json &image = m_json["stderr_image"];
+    if (!image.isNull() && !image.isBool()) { throw std::runtime_error("job: \"stderr_image\" must be true or false"); }
+    settings.collect = settings.target > 0.0 || (image.isBool() && image.asBool());
+    if (settings.collect && resume()) {
+        throw std::runtime_error(std::string("job: \"resume\" does not go with \"") + (settings.target > 0.0 ? "target_noise" : "stderr_image")
+                                 + "\": the state file holds no squares");
+    }
+    if (settings.collect && integratorName() == "AlbedoIntegrator") {
+        throw std::runtime_error(std::string("job: \"") + (settings.target > 0.0 ? "target_noise" : "stderr_image") + "\" does not go with the AlbedoIntegrator, which keeps no second moments");
+    }
+    return settings;
+}
+
 std::shared_ptr<Integrator> Job::integrator() const
 {
     const std::string name = integratorName();

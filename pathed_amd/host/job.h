@@ -14,6 +14,15 @@
 //   "features" (absent): a list out of "albedo", "normal", "depth" -- first-hit feature images of the same camera samples
 //               (include/pathed_hip.h: pathed_hip_render_features), written beside every auto*.exr as auto-albedo*.exr,
 //               auto-normal*.exr, auto-depth*.exr.  An unknown name is an error.
+//   "target_noise" (absent): a number > 0.  The run keeps per-pixel second moments (include/pathed_hip.h:
+//               pathed_hip_render_moments_device), estimates the image's noise figure -- the mean over the pixels of the standard
+//               error of the pixel's mean over its brightness, pathed_hip_noise_estimate_device -- at the power-of-two checkpoints
+//               from "min_spp" on, and stops at the first one at or below the target; "spp" stays the cap,
+//   "min_spp" (16): an integer >= 2, the first sample count the figure is looked at,
+//   "noise_floor" (0.01): a number > 0 added to a pixel's brightness in that ratio, so that black pixels do not dominate,
+//   "stderr_image" (false; implied by "target_noise"): write the per-channel standard error of the mean as auto-stderr*.exr
+//               beside every auto*.exr and record the figure in the log and in metrics.json ("noise", "stopped_on_noise").
+//               Neither key goes with "resume": the state file holds no squares.  Bad values are refused by name.
 #pragma once
 
 #include "bounce_controller.h"
@@ -68,6 +77,14 @@ public:
     bool resume() const { return m_json["resume"].isBool() && m_json["resume"].asBool(); }
     std::vector<int> devices() const;
     std::vector<std::string> features() const;   // in the order albedo, normal, depth
+    // "target_noise" / "min_spp" / "noise_floor" / "stderr_image", validated (a bad value throws an error that names its key)
+    struct NoiseSettings {
+        double target = 0.0;   // 0 = none
+        int minSpp = 16;
+        double floor = 0.01;
+        bool collect = false;  // a target or "stderr_image": the run keeps second moments
+    };
+    NoiseSettings noise() const;
     int gpu() const { return m_json["gpu"].isNumber() ? m_json["gpu"].asInt() : 0; }
     std::string assetRoot() const { return m_json["asset_root"].isString() ? m_json["asset_root"].asString() : ""; }
     std::string bvhBuilder() const { return m_json["bvh_builder"].isString() ? m_json["bvh_builder"].asString() : "auto"; }

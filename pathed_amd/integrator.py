@@ -160,6 +160,92 @@ class HipScene:
             self._handle, C.c_uint64(seed), spp_begin, spp_count, C.byref(buffers), C.c_void_p(stream))
         _check(self._lib, code, "pathed_hip_render_features_device")
 
+    def render_moments(self, seed, spp_begin, spp_count, start_bounce, last_bounce, accum=None, squares=None):
+        """The radiance sums of samples [spp_begin, spp_begin + spp_count) and, beside them, the per-channel sums of the squared
+        sample colours (pathed_hip_render_moments): two float32 host arrays (H, W, 3) the call ADDS to, as `render` does."""
+        if accum is None:
+            accum = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        if squares is None:
+            squares = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        for array in (accum, squares):
+            assert array.dtype == np.float32 and array.flags["C_CONTIGUOUS"] and array.size == 3 * self.width * self.height
+        code = self._lib.pathed_hip_render_moments(
+            self._handle, C.c_uint64(seed), spp_begin, spp_count, start_bounce, last_bounce,
+            accum.ctypes.data_as(C.POINTER(C.c_float)), squares.ctypes.data_as(C.POINTER(C.c_float)))
+        _check(self._lib, code, "pathed_hip_render_moments")
+        return accum, squares
+
+    def render_moments_device(self, seed, spp_begin, spp_count, start_bounce, last_bounce, sum_pointer, squares_pointer, stream=0):
+        """Same, onto caller-owned device memory (e.g. tensor.data_ptr()) on `stream`: both sums CONTINUE from the buffers'
+        contents in sample order, so any split of [0, n) into calls gives the same floats."""
+        code = self._lib.pathed_hip_render_moments_device(
+            self._handle, C.c_uint64(seed), spp_begin, spp_count, start_bounce, last_bounce,
+            C.c_void_p(sum_pointer or None), C.c_void_p(squares_pointer or None), C.c_void_p(stream))
+        _check(self._lib, code, "pathed_hip_render_moments_device")
+
+    def device_buffer(self, count, host=None):
+        """`count` floats on the scene's device (pathed_hip_accum_alloc), zeroed or filled from `host`; free with free_device_buffer."""
+        pointer = C.c_void_p()
+        _check(self._lib, self._lib.pathed_hip_accum_alloc(self._handle, int(count), C.byref(pointer)), "pathed_hip_accum_alloc")
+        if host is not None:
+            host = np.ascontiguousarray(host, dtype=np.float32)
+            assert host.size == count
+            code = self._lib.pathed_hip_accum_upload(self._handle, pointer, int(count), host.ctypes.data_as(C.POINTER(C.c_float)))
+            if code != 0:
+                self._lib.pathed_hip_accum_free(self._handle, pointer)
+            _check(self._lib, code, "pathed_hip_accum_upload")
+        return pointer.value
+
+    def download_device_buffer(self, pointer, out):
+        """Copies out.size floats from device memory at `pointer` into the float32 array `out`."""
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]
+        _check(self._lib, self._lib.pathed_hip_accum_download(self._handle, C.c_void_p(pointer), out.size, out.ctypes.data_as(C.POINTER(C.c_float))),
+               "pathed_hip_accum_download")
+        return out
+
+    def free_device_buffer(self, pointer):
+        if pointer:
+            self._lib.pathed_hip_accum_free(self._handle, C.c_void_p(pointer))
+
+    def noise_estimate(self, sum, sq, n, floor=0.01, threshold=0.0, error=None):
+        """The noise figure of the image with radiance sums `sum` and square sums `sq` over `n` samples per pixel
+        (pathed_hip_noise_estimate_device; the formula is in include/pathed_hip.h): a dict with mean_error, max_error,
+        pixels_above (pixels whose error exceeds `threshold`) and invalid_pixels.  `sum` and `sq` are float32 host arrays
+        (H, W, 3), uploaded for the call, or device pointers (ints); `error`, if given, receives the per-pixel error: a float32
+        host array (H, W) with host sums, a device pointer with device sums."""
+        noise = _capi.PathedNoise()
+        noise.struct_size = C.sizeof(_capi.PathedNoise)
+        if isinstance(sum, np.ndarray) != isinstance(sq, np.ndarray):
+            raise TypeError("noise_estimate: `sum` and `sq` must both be host arrays or both be device pointers")
+        if not isinstance(sum, np.ndarray):
+            code = self._lib.pathed_hip_noise_estimate_device(
+                self._handle, C.c_void_p(sum or None), C.c_void_p(sq or None), int(n), float(floor), float(threshold),
+                C.c_void_p(error or None), C.byref(noise), None)
+            _check(self._lib, code, "pathed_hip_noise_estimate_device")
+        else:
+            pixels = self.width * self.height
+            for array in (sum, sq):
+                assert array.dtype == np.float32 and array.size == 3 * pixels
+            if error is not None:
+                assert error.dtype == np.float32 and error.flags["C_CONTIGUOUS"] and error.size == pixels
+            buffers = []
+            try:
+                buffers.append(self.device_buffer(3 * pixels, sum))
+                buffers.append(self.device_buffer(3 * pixels, sq))
+                if error is not None:
+                    buffers.append(self.device_buffer(pixels))
+                code = self._lib.pathed_hip_noise_estimate_device(
+                    self._handle, C.c_void_p(buffers[0]), C.c_void_p(buffers[1]), int(n), float(floor), float(threshold),
+                    C.c_void_p(buffers[2]) if error is not None else None, C.byref(noise), None)
+                _check(self._lib, code, "pathed_hip_noise_estimate_device")
+                if error is not None:
+                    self.download_device_buffer(buffers[2], error)
+            finally:
+                for pointer in buffers:
+                    self.free_device_buffer(pointer)
+        return {"mean_error": noise.mean_error, "max_error": noise.max_error, "pixels_above": int(noise.pixels_above),
+                "invalid_pixels": int(noise.invalid_pixels)}
+
     def trace(self, rays, any_hit=False):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         n = rays.shape[0]
@@ -347,16 +433,70 @@ class PathTracer:
     reference's PDFIntegrator also overrides run()).
     """
 
-    def __init__(self, bounce_controller, spp=1, seed=1, spp_per_launch=1024):
+    def __init__(self, bounce_controller, spp=1, seed=1, spp_per_launch=1024, target_noise=None, min_spp=16, noise_floor=0.01):
         self.bounce_controller = bounce_controller
         self.spp = spp
         self.seed = seed
         if int(spp_per_launch) < 1:
             raise PathedError("spp_per_launch must be >= 1")
         self.spp_per_launch = int(spp_per_launch)
+        # noise-targeted stopping: the twin of the C++ host's job keys (pathed_amd/host/job.h)
+        if target_noise is not None and not float(target_noise) > 0.0:
+            raise PathedError("target_noise must be a number > 0")
+        if int(min_spp) != min_spp or int(min_spp) < 2:
+            raise PathedError("min_spp must be an integer >= 2")
+        if not float(noise_floor) > 0.0:
+            raise PathedError("noise_floor must be a number > 0")
+        self.target_noise = None if target_noise is None else float(target_noise)
+        self.min_spp = int(min_spp)
+        self.noise_floor = float(noise_floor)
+        self.noise_history = []      # (spp, mean_error) at every checkpoint the figure was estimated at
+        self.stopped_on_noise = False
+
+    def _run_to_noise_target(self, image, scene, callback, quit_flag):
+        """run() with a target: the sums and their squares stay on the device and continue there (render_moments_device), the
+        figure is estimated at the power-of-two checkpoints from min_spp on and at the end, and the run stops at the first one
+        at or below the target -- batch for batch what the C++ host does (pathed_amd/host/integrator.cpp)."""
+        floats = 3 * scene.width * scene.height
+        sums = np.zeros((scene.height, scene.width, 3), dtype=np.float32)
+        self.noise_history = []
+        self.stopped_on_noise = False
+        buffers = []
+        try:
+            buffers.append(scene.device_buffer(floats))
+            buffers.append(scene.device_buffer(floats))
+            done = 0
+            while done < self.spp:
+                next_power = 1
+                while next_power <= done:
+                    next_power *= 2
+                count = min(self.spp_per_launch, self.spp - done, next_power - done)
+                scene.render_moments_device(self.seed, done, count, self.bounce_controller.start_bounce,
+                                            self.bounce_controller.last_bounce, buffers[0], buffers[1])
+                done += count
+                scene.download_device_buffer(buffers[0], sums)
+                np.divide(sums, np.float32(done), out=image)
+                checkpoint = (done & (done - 1)) == 0
+                if callback is not None:
+                    callback(done, checkpoint)
+                if (checkpoint or done == self.spp) and done >= self.min_spp:
+                    figure = scene.noise_estimate(buffers[0], buffers[1], done, floor=self.noise_floor, threshold=self.target_noise)
+                    self.noise_history.append((done, figure["mean_error"]))
+                    if figure["mean_error"] <= self.target_noise and done < self.spp:
+                        self.stopped_on_noise = True
+                        break
+                if quit_flag is not None and quit_flag():
+                    return
+        finally:
+            for pointer in buffers:
+                scene.free_device_buffer(pointer)
+        return image
 
     def run(self, image, scene, callback=None, quit_flag=None):
-        """image: float32 (H, W, 3) array that receives the running mean; scene: HipScene."""
+        """image: float32 (H, W, 3) array that receives the running mean; scene: HipScene.  With target_noise the run may end
+        before `spp` (stopped_on_noise, noise_history)."""
+        if self.target_noise is not None:
+            return self._run_to_noise_target(image, scene, callback, quit_flag)
         radiance_lookup = np.zeros((scene.height, scene.width, 3), dtype=np.float32)
         done = 0
         while done < self.spp:
@@ -389,6 +529,32 @@ def features_from_job(job):
         if name not in FEATURE_NAMES:
             raise PathedError("job: unknown feature \"%s\" (known: %s)" % (name, ", ".join(FEATURE_NAMES)))
     return [name for name in FEATURE_NAMES if name in wanted]
+
+
+def noise_from_job(job):
+    """The job keys "target_noise" (a number > 0, absent = none), "min_spp" (an integer >= 2, default 16), "noise_floor"
+    (a number > 0, default 0.01) and "stderr_image" (a bool, implied by a target): (target_noise or None, min_spp, floor,
+    write_stderr).  A bad value is an error that names its key, and so is "resume" beside either key: the state file
+    holds no squares."""
+    def number(value):
+        return isinstance(value, (int, float)) and not isinstance(value, bool)
+    target = job.get("target_noise")
+    if target is not None and not (number(target) and 0.0 < target < 1e30):
+        raise PathedError("job: \"target_noise\" must be a number > 0")
+    min_spp = job.get("min_spp", 16)
+    if not (number(min_spp) and int(min_spp) == min_spp and 2 <= min_spp <= 1e9):
+        raise PathedError("job: \"min_spp\" must be an integer >= 2")
+    floor = job.get("noise_floor", 0.01)
+    if not (number(floor) and 0.0 < floor < 1e30):
+        raise PathedError("job: \"noise_floor\" must be a number > 0")
+    write_stderr = job.get("stderr_image", False)
+    if not isinstance(write_stderr, bool):
+        raise PathedError("job: \"stderr_image\" must be true or false")
+    write_stderr = write_stderr or target is not None
+    if write_stderr and job.get("resume", False):
+        raise PathedError("job: \"resume\" does not go with \"%s\": the state file holds no squares"
+                          % ("target_noise" if target is not None else "stderr_image"))
+    return (None if target is None else float(target)), int(min_spp), float(floor), write_stderr
 
 
 def integrator_from_job(job, **kwargs):

@@ -61,6 +61,8 @@ def main(argv=None):
     # differently between the two runners (here the GPUs are the ranks of torch.distributed.run, and there is no auto.state)
     if job.get("resume", False):
         raise SystemExit("pathed_amd.run_job: \"resume\" is a key of the C++ host (pathed <job.json>); this runner keeps no auto.state")
+    if "target_noise" in job or job.get("stderr_image", False):
+        raise SystemExit("pathed_amd.run_job: \"target_noise\" and \"stderr_image\" are keys of the C++ host (pathed <job.json>); this runner keeps no second moments")
     if "gpus" in job:
         raise SystemExit("pathed_amd.run_job: \"gpus\" is a key of the C++ host; start this runner under torch.distributed.run, one rank per GPU")
 
