@@ -41,7 +41,8 @@ extern "C" {
  * pathed_hip_scene_create_ex (per-scene device and tuning), pathed_hip_measure_valu,
  * pathed_hip_accum_add / pathed_hip_accum_copy_peer (multi-GPU fan-in of the radiance sums),
  * PathedFeatureBuffers / pathed_hip_render_features[_device] (first-hit feature images), PATHED_INTEGRATOR_ALBEDO,
- * pathed_hip_render_moments[_device] / PathedNoise / pathed_hip_noise_estimate_device (per-pixel second moments and the noise figure). */
+ * pathed_hip_render_moments[_device] / PathedNoise / pathed_hip_noise_estimate_device (per-pixel second moments and the noise figure),
+ * pathed_hip_select_pixels_device / pathed_hip_render_pixels_device (adaptive sampling over pixel lists). */
 
 /* error codes */
 #define PATHED_OK            0
@@ -470,6 +471,38 @@ typedef struct PathedNoise {
 int pathed_hip_noise_estimate_device(PathedScene *scene, const float *d_rgb_sum, const float *d_rgb_sq_sum,
                                      uint32_t n_samples, float floor, float threshold,
                                      float *d_error, PathedNoise *out, void *stream);
+
+/* Adaptive sampling: render only the pixels that are still noisy.  Beside the two sum images goes a COUNT image, W*H uint32
+ * in device memory: the samples each pixel's sums hold.
+ *
+ * pathed_hip_select_pixels_device is pathed_hip_noise_estimate_device with n read per pixel from d_count: n = (float)count and
+ * n / (n - 1) are computed per pixel, in fp32, and the formula above is applied operation for operation -- where every count
+ * is the same n >= 2, e per pixel and every field of `out` are that call's bits.  A pixel with count < 2 has no spread yet:
+ * its e counts as 0 and it counts in invalid_pixels.  The call also makes the list of the pixels still to render: those with
+ * e > threshold and those with count < 2, as pixel indices (row * W + col) in ASCENDING order, written to d_list (room for W*H
+ * uint32), their number to *n_list.  The list is built without atomics and is the same on every run.  d_error as above.
+ * Returns when the work on `stream` has completed.  PATHED_E_INVALID: floor <= 0, struct_size, a null buffer, list or result.
+ *
+ * pathed_hip_render_pixels_device renders samples [spp_begin, spp_begin + spp_count) of the n_list pixels of d_list and
+ * nothing else: the work units of its passes walk the list instead of the image (whatever PathedSceneOptions.unit_order
+ * says), and the call splits into internal passes like every render call.  A list call runs on the path tracer's WAVEFRONT
+ * kernels (PathedStats.path_kernel 1) whatever kernel the scene's other calls run on -- the fused, hybrid and wave kernels
+ * do not know the list order (pathed_amd/csrc/kernels.h says why) -- which gives the same floats: all of them do.  A scene
+ * whose calls run the volume integrators' kernels has a list form of those (k_list_volume; path_kernel 4 / 9 as ever).
+ *   - a listed pixel's sums and square sums CONTINUE exactly as pathed_hip_render_moments_device would continue them over
+ *     the same sample range -- the same floats, on every kernel organisation -- and its count grows by spp_count: a pixel
+ *     that stops at n samples holds exactly the n-sample render's value.
+ *   - no other pixel's entry of the three buffers is written or read.
+ *   - n_list == 0 (or spp_count == 0): nothing is launched, PATHED_OK.
+ *   - PATHED_E_INVALID, and nothing is rendered: a null buffer; a scene whose samples-per-unit is not 1; a list that is not
+ *     strictly ascending (so: no pixel twice) or holds an index >= W*H -- a kernel checks the list before anything else runs.
+ *   - PATHED_E_UNSUPPORTED, and nothing is launched: PATHED_INTEGRATOR_ALBEDO. */
+int pathed_hip_select_pixels_device(PathedScene *scene, const float *d_rgb_sum, const float *d_rgb_sq_sum, const uint32_t *d_count,
+                                    float floor, float threshold, float *d_error, uint32_t *d_list, uint32_t *n_list,
+                                    PathedNoise *out, void *stream);
+int pathed_hip_render_pixels_device(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count,
+                                    int start_bounce, int last_bounce, const uint32_t *d_list, uint32_t n_list,
+                                    float *d_rgb_sum, float *d_rgb_sq_sum, uint32_t *d_count, void *stream);
 
 /* Heterogeneous media: the reference's GridMedium (src/grid_medium.cpp), a voxel grid of extinction densities that is
  * looked up trilinearly and walked cell by cell (pathed_amd/csrc/grid_medium.h).  PathedSceneDesc and PathedMedium do not

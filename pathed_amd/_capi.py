@@ -231,6 +231,8 @@ HIP_SYMBOLS = [
     "pathed_hip_render_moments",
     "pathed_hip_render_moments_device",
     "pathed_hip_noise_estimate_device",
+    "pathed_hip_select_pixels_device",
+    "pathed_hip_render_pixels_device",
     "pathed_hip_trace",
     "pathed_hip_debug_small_candidates",
     "pathed_hip_debug_light_records",
@@ -346,6 +348,11 @@ def load_hip():
         lib.pathed_hip_render_moments.restype = C.c_int
         lib.pathed_hip_noise_estimate_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_float, C.c_float, vp, C.POINTER(PathedNoise), vp]
         lib.pathed_hip_noise_estimate_device.restype = C.c_int
+    if hasattr(lib, "pathed_hip_render_pixels_device"):
+        lib.pathed_hip_select_pixels_device.argtypes = [vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, C.POINTER(C.c_uint32), C.POINTER(PathedNoise), vp]
+        lib.pathed_hip_select_pixels_device.restype = C.c_int
+        lib.pathed_hip_render_pixels_device.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint32, vp, vp, vp, vp]
+        lib.pathed_hip_render_pixels_device.restype = C.c_int
     lib.pathed_hip_trace.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_int, vp]
     lib.pathed_hip_trace.restype = C.c_int
     lib.pathed_hip_debug_small_candidates.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint64)]

@@ -195,11 +195,11 @@ struct RenderParams {
     int nPixels;
     unsigned int nUnits;   // units of THIS pool
     // unit order (unitPlace): which pixel groups this pool's queues walk
-    int unitOrder;                     // kOrderStripes | kOrderStripesTiled | kOrderTiles
+    int unitOrder;                     // kOrderStripes | kOrderStripesTiled | kOrderTiles | kOrderList (wavefront kernels only)
     unsigned int pool, pools;          // queue q of pool h owns the chunks / pixel groups (q * pools + h) + j * (nQueues * pools), j = 0, 1, ..
     unsigned int nGroups;              // what the queues share out: chunks per pixel (stripes) or ceil(nPixels / kUnitGroup) (tiles)
     unsigned int lastGroupPixels;      // tiles: pixels of group nGroups - 1 (1 .. kUnitGroup)
-    unsigned int groupUnits;           // units of one owned item: nPixels (stripes) or kUnitGroup * chunksPerPixel (tiles)
+    unsigned int groupUnits;           // units of one owned item: nPixels (stripes), the list's length (list) or kUnitGroup * chunksPerPixel (tiles)
     FastDiv divStride, divGroupUnits, divBand, divWidth;   // by unitsPerQueue, by groupUnits, by 8 * image width, by the image width
     unsigned int queueUnits[kUnitQueues];        // units each queue of this pool holds
     int nQueues;           // min(kUnitQueues, shade blocks): every queue has a consumer
@@ -215,7 +215,8 @@ struct RenderParams {
     // sphere of radius -1 that no ray touches): phase 1 of the sphere queries (smallSphereCandidates)
     float spherePairs[8][4][2];   // [pair][component][half], kBruteForceMaxSpheres / 2 pairs
     float smallKappaT;        // ... and the absolute slack of their t bounds per det^2
-    float4 *cameraQueue;      // k_path_small: per wave of the grid kCameraQueueWords float4 of started samples (the camera queue)
+    float4 *cameraQueue;      // k_path_small: per wave of the grid kCameraQueueWords float4 of started samples (the camera queue);
+                              // a list pass (kOrderList, wavefront kernels): the pixel list, uint32 (pixelList())
     const float *mfmaTable;   // k_path_small<.., MFMA>: the A-side rows of the matrix-pipe phase 1 (mfma_candidates.h), kMfmaTableFloats
     MfmaFrame mfmaFrame;
     // k_path_hybrid (path_hybrid.h): scene.leafTris holds the DIRECT set in item order (hybridDirectTris of them), the rest of the
@@ -1699,8 +1700,17 @@ __device__ inline unsigned int grabUnits(const RenderParams &p, bool want, unsig
 //   kOrderTiles: pixel GROUPS of 256 (tiles) dealt round-robin to the queues, a queue hands out all chunks of a group
 //     before it moves on: the slots of a block all work on one patch of the image.  Measured 6-8 % SLOWER on the mesh
 //     scenes than the stripes (tools/chunk_sweep2.py): kept selectable (PATHED_UNIT_ORDER).
+//   kOrderList: the stripes over a LIST of pixels (pathed_hip_render_pixels_device): an item is a chunk of the pass and holds one
+//     unit per list entry, position w of it is pixel pixelList(p)[w].  The unit buffer keeps the image's layout (partialIndex:
+//     chunk * nPixels + pixel), so the entries of pixels outside the list are neither written nor read.  Not selectable: a list
+//     pass has this order and no other pass has it.  Only the WAVEFRONT kernels (k_init, k_shade, k_shade_env) and k_list_volume
+//     know it -- they call unitPlace<true> -- and every list pass runs on them: the persistent path kernels live at their register budget with a
+//     few dozen bytes of spills each, and ANY further arm in unitPlace, wherever the list pointer sat in RenderParams and however
+//     the arm was written (four shapes tried), moved the scratch of 33 to 35 of them by 4 to 64 bytes either way, past the
+//     figures tests/test_*kernel_resources.py pin.  With LIST = false they compile exactly as before.  The list pointer travels
+//     in RenderParams::cameraQueue, which only k_path_small reads: RenderParams keeps its size and layout.
 // Tile walk: bands of 8 rows, blocks of 32 columns inside a band, row-major inside a block; ragged last band / block.
-static const int kOrderStripes = 0, kOrderStripesTiled = 1, kOrderTiles = 2;
+static const int kOrderStripes = 0, kOrderStripesTiled = 1, kOrderTiles = 2, kOrderList = 3;
 
 __device__ inline unsigned int tileWalkPixel(const RenderParams &p, unsigned int index)
 {
@@ -1718,6 +1728,9 @@ __device__ inline unsigned int tileWalkPixel(const RenderParams &p, unsigned int
     return (8u * band + y) * width + 32u * block + x;
 }
 
+__device__ inline const uint32_t *pixelList(const RenderParams &p) { return reinterpret_cast<const uint32_t *>(p.cameraQueue); }
+
+template <bool LIST = false>
 __device__ inline void unitPlace(const RenderParams &p, unsigned int unit, uint32_t *pixel, uint32_t *chunkIndex)
 {
     const unsigned int queue = fastDivide(unit, p.divStride);
@@ -1726,8 +1739,14 @@ __device__ inline void unitPlace(const RenderParams &p, unsigned int unit, uint3
     const unsigned int w = k - j * p.groupUnits;
     const unsigned int owned = queue * p.pools + p.pool + j * (unsigned int)p.nQueues * p.pools;   // j-th chunk / group of the queue
     if (p.unitOrder != kOrderTiles) {
-        *chunkIndex = owned;                                   // groupUnits = pixels of the image
-        *pixel = p.unitOrder == kOrderStripes ? w : tileWalkPixel(p, w);
+        *chunkIndex = owned;                                   // groupUnits = pixels of the image (of the list)
+        if constexpr (LIST) {
+            if (p.unitOrder == kOrderStripes) { *pixel = w; }
+            else if (p.unitOrder == kOrderList) { *pixel = pixelList(p)[w]; }
+            else { *pixel = tileWalkPixel(p, w); }
+        } else {
+            *pixel = p.unitOrder == kOrderStripes ? w : tileWalkPixel(p, w);
+        }
         return;
     }
     unsigned int chunk, within;
@@ -1743,20 +1762,22 @@ __device__ inline void unitPlace(const RenderParams &p, unsigned int unit, uint3
 }
 
 // first sample index of a unit and one-past-last
+template <bool LIST = false>
 __device__ inline void unitSamples(const RenderParams &p, unsigned int unit, uint32_t *pixel, uint32_t *first, uint32_t *end)
 {
     uint32_t chunkIndex;
-    unitPlace(p, unit, pixel, &chunkIndex);
+    unitPlace<LIST>(p, unit, pixel, &chunkIndex);
     *first = p.sppBegin + chunkIndex * (unsigned int)p.chunk;
     const uint32_t last = *first + (unsigned int)p.chunk;
     *end = last < p.sppEnd ? last : p.sppEnd;
 }
 
 // where a unit's partial sum goes: chunk-major, so that k_resolve reads a chunk's pixels coalesced
+template <bool LIST = false>
 __device__ inline size_t partialIndex(const RenderParams &p, unsigned int unit)
 {
     uint32_t pixel, chunkIndex;
-    unitPlace(p, unit, &pixel, &chunkIndex);
+    unitPlace<LIST>(p, unit, &pixel, &chunkIndex);
     return (size_t)chunkIndex * (size_t)p.nPixels + pixel;
 }
 
@@ -1771,7 +1792,7 @@ __global__ __launch_bounds__(kBlock) void k_init(RenderParams p)
     const bool started = unit != 0xFFFFFFFFu;
     if (started) {
         uint32_t pixel, first, end;
-        unitSamples(p, unit, &pixel, &first, &end);
+        unitSamples<true>(p, unit, &pixel, &first, &end);
         startSample(p, pixel, first, 0, &rayO, &rayD);
     }
     p.state.rayO[slot] = rayO;
@@ -1933,6 +1954,163 @@ __global__ __launch_bounds__(kBlock) void k_noise(NoiseParams p)
     }
 }
 
+// k_resolve_moments over a LIST of pixels (pathed_hip_render_pixels_device): one lane per list entry.  A listed pixel gets
+// exactly k_resolve_moments' additions from its own entries of the unit buffer (which keeps the image's layout), and the
+// pass's sample count onto its entry of the count image; no other pixel is read or written.
+struct ListMomentsParams {
+    const float4 *chunkBuf;          // RenderState::chunkBuf of the pass
+    const uint32_t *pixelList;       // nList pixels, strictly ascending, each < nPixels
+    int nList;
+    int nPixels;
+    int chunksPerPixel;
+    uint32_t samples;                // of the pass, per listed pixel
+    float *sum;                      // 3 * nPixels, continued
+    float *squares;                  // 3 * nPixels, continued
+    uint32_t *count;                 // nPixels, continued
+};
+
+__global__ __launch_bounds__(kBlock) void k_resolve_list(ListMomentsParams p)
+{
+    const int entry = blockIdx.x * kBlock + threadIdx.x;
+    if (entry >= p.nList) { return; }
+    const uint32_t pixel = p.pixelList[entry];
+    float *out = p.sum + 3 * (size_t)pixel;
+    float *outSquares = p.squares + 3 * (size_t)pixel;
+    float r = out[0], g = out[1], b = out[2];
+    float rr = outSquares[0], gg = outSquares[1], bb = outSquares[2];
+    int chunk = 0;
+    for (; chunk + 8 <= p.chunksPerPixel; chunk += 8) {
+        float4 partial[8];
+        #pragma unroll
+        for (int k = 0; k < 8; k++) { partial[k] = p.chunkBuf[(size_t)(chunk + k) * p.nPixels + pixel]; }
+        #pragma unroll
+        for (int k = 0; k < 8; k++) {
+            r += partial[k].x;
+            g += partial[k].y;
+            b += partial[k].z;
+            rr = rr + partial[k].x * partial[k].x;
+            gg = gg + partial[k].y * partial[k].y;
+            bb = bb + partial[k].z * partial[k].z;
+        }
+    }
+    for (; chunk < p.chunksPerPixel; chunk++) {
+        const float4 partial = p.chunkBuf[(size_t)chunk * p.nPixels + pixel];
+        r += partial.x;
+        g += partial.y;
+        b += partial.z;
+        rr = rr + partial.x * partial.x;
+        gg = gg + partial.y * partial.y;
+        bb = bb + partial.z * partial.z;
+    }
+    out[0] = r;
+    out[1] = g;
+    out[2] = b;
+    outSquares[0] = rr;
+    outSquares[1] = gg;
+    outSquares[2] = bb;
+    p.count[pixel] += p.samples;
+}
+
+// Is a pixel list fit to render?  Strictly ascending and every entry below nPixels: then no pixel is listed twice (two units
+// would share an entry of the unit buffer) and no index leaves the image.  One lane per entry; *bad is zeroed by the caller
+// and every offending lane stores the same 1, so no atomic is needed.
+__global__ __launch_bounds__(kBlock) void k_check_list(const uint32_t *list, int nList, int nPixels, unsigned int *bad)
+{
+    const int entry = blockIdx.x * kBlock + threadIdx.x;
+    if (entry >= nList) { return; }
+    const uint32_t pixel = list[entry];
+    if (pixel >= (uint32_t)nPixels || (entry > 0 && list[entry - 1] >= pixel)) { *bad = 1u; }
+}
+
+// k_noise with a sample count PER PIXEL and a list of the pixels that are still too noisy (pathed_hip_select_pixels_device).
+// n = (float)count[pixel] and n / (n - 1) are computed per pixel, in fp32, and the formula is k_noise's operation for operation:
+// with one count everywhere the errors and the partials are k_noise's bits.  A pixel with fewer than 2 samples has no spread
+// yet: it is selected, its error counts as 0 and it counts as invalid.  Otherwise a pixel is selected when e > threshold.
+// The block's selected pixels go to selected[block * kBlock ..] in pixel order -- ranks from the wave's ballot (the set
+// lanes below mine) plus the totals of the waves before mine, through LDS -- and their number into the partial's `selected`;
+// k_place_list moves them to their final places once the host has added up the blocks before each.  No atomics: the list
+// is the same on every run.
+struct NoiseSelectParams {
+    const float *sum;                // 3 * nPixels
+    const float *squares;            // 3 * nPixels
+    const uint32_t *count;           // nPixels
+    int nPixels;
+    float floor;
+    float threshold;
+    float *error;                    // nPixels, or null
+    NoisePartial *partials;          // one per block; `unused` holds the block's number of selected pixels
+    uint32_t *selected;              // nPixels: block b's selected pixels from b * kBlock on
+};
+
+__global__ __launch_bounds__(kBlock) void k_noise_select(NoiseSelectParams p)
+{
+    __shared__ float errors[kBlock];
+    __shared__ unsigned int invalid[kBlock];
+    __shared__ unsigned int waveTotals[kWavesPerBlock];
+    const int pixel = blockIdx.x * kBlock + threadIdx.x;
+    float e = 0.f;
+    unsigned int bad = 0u;
+    bool chosen = false;
+    if (pixel < p.nPixels) {
+        const uint32_t samples = p.count[pixel];
+        if (samples < 2u) {
+            bad = 1u;
+            chosen = true;
+        } else {
+            const float *s = p.sum + 3 * (size_t)pixel;
+            const float *q = p.squares + 3 * (size_t)pixel;
+            const float n = (float)samples;
+            const float bessel = n / (n - 1.f);
+            float m[3], v[3];
+            #pragma unroll
+            for (int c = 0; c < 3; c++) {
+                m[c] = s[c] / n;
+                const float d = q[c] / n - m[c] * m[c];
+                v[c] = (d > 0.f ? d : 0.f) * bessel;
+            }
+            e = sqrtf(((v[0] + v[1]) + v[2]) / n) / (((m[0] + m[1]) + m[2]) + p.floor);
+            if (!isfinite(e)) { e = 0.f; bad = 1u; }
+            chosen = e > p.threshold;
+        }
+        if (p.error) { p.error[pixel] = e; }
+    }
+    errors[threadIdx.x] = e;
+    invalid[threadIdx.x] = bad;
+    const unsigned long long mask = __ballot(chosen);
+    const unsigned int lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned int before = (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0u) { waveTotals[wave] = (unsigned int)__popcll(mask); }
+    __syncthreads();
+    unsigned int base = 0u, total = 0u;
+    #pragma unroll
+    for (unsigned int k = 0; k < (unsigned int)kWavesPerBlock; k++) {
+        if (k < wave) { base += waveTotals[k]; }
+        total += waveTotals[k];
+    }
+    if (chosen) { p.selected[(size_t)blockIdx.x * kBlock + base + before] = (uint32_t)pixel; }
+    if (threadIdx.x == 0) {
+        const int first = blockIdx.x * kBlock;
+        const int lanes = p.nPixels - first < kBlock ? p.nPixels - first : kBlock;
+        NoisePartial partial = { 0.0, 0.f, 0u, 0u, 0u };
+        for (int k = 0; k < lanes; k++) {
+            const float value = errors[k];
+            partial.sum += (double)value;
+            if (value > partial.maxError) { partial.maxError = value; }
+            if (value > p.threshold) { partial.above++; }
+            partial.invalid += invalid[k];
+        }
+        partial.unused = total;
+        p.partials[blockIdx.x] = partial;
+    }
+}
+
+// the second step of the selection: block b's offsets[b + 1] - offsets[b] pixels move from selected[b * kBlock ..] to list[offsets[b] ..]
+__global__ __launch_bounds__(kBlock) void k_place_list(const uint32_t *selected, const uint32_t *offsets, uint32_t *list)
+{
+    const uint32_t first = offsets[blockIdx.x], end = offsets[blockIdx.x + 1];
+    if (threadIdx.x < end - first) { list[first + threadIdx.x] = selected[(size_t)blockIdx.x * kBlock + threadIdx.x]; }
+}
+
 // Tuning builds only (-DPATHED_SHADE_PROFILE): how many waves enter a region of k_shade and with how
 // many lanes -- lane utilisation per region (tools/shade_profile.py prints the table).
 #ifdef PATHED_SHADE_PROFILE
@@ -2085,7 +2263,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ATTRIBUTE void k_shade(RenderP
         int firstEmitMaterial = floatAsInt(ro.w);
 
         uint32_t pixel, firstSample, endSample;
-        unitSamples(p, unit, &pixel, &firstSample, &endSample);
+        unitSamples<true>(p, unit, &pixel, &firstSample, &endSample);
         const uint32_t sample = firstSample + (uint32_t)sampleInUnit;
 
         result = rgb(resIn.x, resIn.y, resIn.z);
@@ -2244,7 +2422,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ATTRIBUTE void k_shade(RenderP
             atomicAdd(&p.stats[kStatDropped], 1ull);
         }
         uint32_t pixel, firstSample, endSample;
-        unitSamples(p, unit, &pixel, &firstSample, &endSample);
+        unitSamples<true>(p, unit, &pixel, &firstSample, &endSample);
         sampleInUnit++;
         result = rgb(0.f);
         outMod = make_float4(1.f, 1.f, 1.f, 1.f);
@@ -2256,7 +2434,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ATTRIBUTE void k_shade(RenderP
             nextSample = firstSample + (uint32_t)sampleInUnit;
             p.state.acc[slot] = partial;
         } else {
-            p.state.chunkBuf[partialIndex(p, unit)] = partial;
+            p.state.chunkBuf[partialIndex<true>(p, unit)] = partial;
             if (!singleSample) { p.state.acc[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }
             needUnit = true;
         }
@@ -2269,7 +2447,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ATTRIBUTE void k_shade(RenderP
         unit = newUnit;
         if (newUnit != 0xFFFFFFFFu) {
             uint32_t endSample;
-            unitSamples(p, newUnit, &nextPixel, &nextSample, &endSample);
+            unitSamples<true>(p, newUnit, &nextPixel, &nextSample, &endSample);
             sampleInUnit = 0;
             startNext = true;
         } else {
@@ -2530,7 +2708,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ENV_ATTRIBUTE void k_shade_env
         unit = (unsigned int)floatAsInt(resIn.w);
         firstEmitMaterial = floatAsInt(ro.w);
         uint32_t firstSample, endSample;
-        unitSamples(p, unit, &pixel, &firstSample, &endSample);
+        unitSamples<true>(p, unit, &pixel, &firstSample, &endSample);
         sample = firstSample + (uint32_t)sampleInUnit;
         result = rgb(resIn.x, resIn.y, resIn.z);
         Rgb modulation = rgb(1.f);
@@ -2612,7 +2790,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ENV_ATTRIBUTE void k_shade_env
                 atomicAdd(&p.stats[kStatDropped], 1ull);                                                                     \
             }                                                                                                                \
             uint32_t unitPixel_, firstSample_, endSample_;                                                                   \
-            unitSamples(p, unit, &unitPixel_, &firstSample_, &endSample_);                                                   \
+            unitSamples<true>(p, unit, &unitPixel_, &firstSample_, &endSample_);                                             \
             sampleInUnit++;                                                                                                  \
             result = rgb(0.f);                                                                                               \
             outMod = make_float4(1.f, 1.f, 1.f, 1.f);                                                                        \
@@ -2624,7 +2802,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ENV_ATTRIBUTE void k_shade_env
                 nextSample = firstSample_ + (uint32_t)sampleInUnit;                                                          \
                 p.state.acc[slot] = partial_;                                                                                \
             } else {                                                                                                         \
-                p.state.chunkBuf[partialIndex(p, unit)] = partial_;                                                          \
+                p.state.chunkBuf[partialIndex<true>(p, unit)] = partial_;                                                    \
                 if (!singleSample_) { p.state.acc[slot] = make_float4(0.f, 0.f, 0.f, 0.f); }                                 \
                 needUnit_ = true;                                                                                            \
             }                                                                                                                \
@@ -2634,7 +2812,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ENV_ATTRIBUTE void k_shade_env
             unit = newUnit_;                                                                                                 \
             if (newUnit_ != 0xFFFFFFFFu) {                                                                                   \
                 uint32_t endSample_;                                                                                         \
-                unitSamples(p, newUnit_, &nextPixel, &nextSample, &endSample_);                                              \
+                unitSamples<true>(p, newUnit_, &nextPixel, &nextSample, &endSample_);                                        \
                 sampleInUnit = 0;                                                                                            \
                 startedNext = true;                                                                                          \
             } else {                                                                                                         \
@@ -3309,7 +3487,8 @@ __device__ __forceinline__ void volumeQueryPairSmall(const VolumeContext<Materia
 // distance sample -- `transmit`, `transmission` and the head of `scatter` below.
 // MULTI: the bounce loop is BasicVolumeIntegrator::L (multiple scattering, a stack of media) instead of VolumePathTracer::L; the
 // instantiations with it are k_path_scatter / k_path_scatter_grid, and the others contain none of its code.
-template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS, bool QUADS, bool GRID, bool MULTI = false>
+// LIST: the units walk a pixel list (unitPlace<true>): k_list_volume alone.
+template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS, bool QUADS, bool GRID, bool MULTI = false, bool LIST = false>
 __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTris &smallTris)
 {
     extern __shared__ float4 ldsRaw[];
@@ -3772,7 +3951,7 @@ __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTri
         if (__ballot(unit != 0xFFFFFFFFu) == 0ull) { break; }
         if (unit != 0xFFFFFFFFu) {
             uint32_t pixel, first, end;
-            unitSamples(p, unit, &pixel, &first, &end);
+            unitSamples<LIST>(p, unit, &pixel, &first, &end);
             float4 partial = make_float4(0.f, 0.f, 0.f, 0.f);
             for (uint32_t sample = first; sample < end; sample++) {
                 SHADE_REGION(0, true);   // samples
@@ -3787,7 +3966,7 @@ __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTri
                 }
                 samplesDone++;
             }
-            p.state.chunkBuf[partialIndex(p, unit)] = partial;
+            p.state.chunkBuf[partialIndex<LIST>(p, unit)] = partial;
         }
     }
     (void)samplesDone;
@@ -3819,6 +3998,18 @@ template <int STACK, bool SMALL>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_scatter_grid(RenderParams p, SmallTris smallTris)
 {
     pathVolume<false, STACK, SMALL, TraitsAll, false, true, true>(p, smallTris);
+}
+
+// The volume integrators over a pixel list (pathed_hip_render_pixels_device; THE UNIT ORDER: kOrderList): the one form of
+// pathVolume that knows the list order, in the generic shape of the grid and scatter families -- every material, pair-of-
+// triangles phase 1, the material table read from memory -- for SMALL scenes (8 stack rows) or the tree walk with 22 rows in
+// LDS, with or without grid media, VolumePathTracer or BasicVolumeIntegrator: eight instantiations.  The narrowed and
+// LDS-table instantiations of k_path_volume give the same floats (they differ in what code they leave out, not in what
+// they compute), so a listed pixel holds what the scene's own kernel gives it.
+template <bool SMALL, bool GRID, bool MULTI>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_list_volume(RenderParams p, SmallTris smallTris)
+{
+    pathVolume<false, SMALL ? 8 : 22, SMALL, TraitsAll, false, GRID, MULTI, true>(p, smallTris);
 }
 
 // Test hook behind pathed_hip_debug_phase_samples: one thread per record, phaseSample on the record's two numbers

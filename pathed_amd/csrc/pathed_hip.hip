@@ -250,6 +250,7 @@ struct PathedScene {
     bool waveAvailable = false;   // ... and the scene is one it serves
     bool lastCallWave = false;    // what the last render call ran (PathedStats.path_kernel)
     bool lastCallHybrid = false;
+    bool lastCallList = false;    // ... a pixel list: the wavefront kernels, whatever the scene's own path kernel is
     bool lastCallFeatures = false;   // ... k_features (features.h): a feature call, or a render call of the albedo integrator
     unsigned long long featureRays = 0;   // closest-hit queries of k_features since reset_stats (one per camera sample)
     unsigned long long waveMaxSamples = 48ull << 20;   // calls of fewer camera samples than this take it (waveMode 0)
@@ -2035,10 +2036,11 @@ void pathed_hip_scene_destroy(PathedScene *scene)
 // The unit order of one pool's launch parameters (kernels.h: THE UNIT ORDER).  The (nQueues x pools) queues share out
 // ITEMS round-robin -- the chunks of the pass (stripes: an item is one whole image of units) or groups of kUnitGroup pixels
 // (tiles: an item is all chunks of the group) -- queue q of pool `pool` owns the items (q * pools + pool) + j * queues.
+// itemPixels: the pixels the pass renders -- the image's, or the length of its pixel list (kOrderList).
 // Returns false when the unit ids of the pass do not fit 32 bits.
-static bool fillUnitOrder(RenderParams &q, int order, int width, int height, int chunksPerPixel, int pool, int pools, int nQueues)
+static bool fillUnitOrder(RenderParams &q, int order, int width, unsigned long long itemPixels, int chunksPerPixel, int pool, int pools, int nQueues)
 {
-    const unsigned long long nPixels = (unsigned long long)width * (unsigned long long)height;
+    const unsigned long long nPixels = itemPixels;
     const unsigned long long allQueues = (unsigned long long)nQueues * (unsigned long long)pools;
     unsigned long long items, itemUnits, lastItemShortfall = 0;
     if (order == kOrderTiles) {
@@ -2108,13 +2110,34 @@ struct Pass {
     hipStream_t stream;
     int nPixels, chunk, chunksPerPixel;
     unsigned int nUnits;
+    // a pass over a list of pixels (pathed_hip_render_pixels_device): nList > 0, the list in device memory, the count image
+    // beside the two sums.  nUnits = nList * chunksPerPixel then; the unit buffer keeps the image's layout (bufferUnits).
+    const uint32_t *pixelList;
+    int nList;
+    uint32_t *counts;
+
+    int unitPixels() const { return nList > 0 ? nList : nPixels; }   // pixels the pass renders
+    size_t bufferUnits() const { return (size_t)nPixels * (size_t)chunksPerPixel; }   // entries of the unit buffer: chunk * nPixels + pixel
 };
 
 // The end of every pass: the units' partial sums onto the caller's sums, and, for a pass that carries a squares buffer,
 // their squares onto that (k_resolve_moments; such a pass has one sample per unit).
-static void launchResolve(const Pass &pass, const RenderParams &params, dim3 pixelGrid, hipStream_t stream)
+static void launchResolve(const Pass &pass, const RenderParams &params, hipStream_t stream)
 {
-    if (pass.squares) {
+    const dim3 pixelGrid((unsigned)((pass.unitPixels() + kBlock - 1) / kBlock));
+    if (pass.nList > 0) {
+        ListMomentsParams moments;
+        moments.chunkBuf = params.state.chunkBuf;
+        moments.pixelList = pass.pixelList;
+        moments.nList = pass.nList;
+        moments.nPixels = params.nPixels;
+        moments.chunksPerPixel = params.chunksPerPixel;
+        moments.samples = pass.count;
+        moments.sum = params.accum;
+        moments.squares = pass.squares;
+        moments.count = pass.counts;
+        hipLaunchKernelGGL(k_resolve_list, pixelGrid, dim3(kBlock), 0, stream, moments);
+    } else if (pass.squares) {
         MomentsParams moments;
         moments.chunkBuf = params.state.chunkBuf;
         moments.nPixels = params.nPixels;
@@ -2145,7 +2168,8 @@ static bool fillPassParams(RenderParams &q, const PathedScene *scene, const Pass
     q.sppEnd = pass.begin + pass.count;
     q.startBounce = pass.startBounce;
     q.lastBounce = pass.lastBounce;
-    return fillUnitOrder(q, scene->unitOrder, scene->width, scene->height, pass.chunksPerPixel, pool, pools, nQueues);
+    if (pass.nList > 0) { q.cameraQueue = reinterpret_cast<float4 *>(const_cast<uint32_t *>(pass.pixelList)); }   // kernels.h: pixelList()
+    return fillUnitOrder(q, pass.nList > 0 ? kOrderList : scene->unitOrder, scene->width, (unsigned long long)pass.unitPixels(), pass.chunksPerPixel, pool, pools, nQueues);
 }
 
 // A pass as ONE persistent launch that renders every unit: no slot pool, no iteration loop, no polling.  This is all that the
@@ -2156,9 +2180,9 @@ static bool fillPassParams(RenderParams &q, const PathedScene *scene, const Pass
 template <typename Launch>
 static int persistentPass(PathedScene *scene, const Pass &pass, int blocksPerCu, int maxStack, int ldsRows, Launch launch)
 {
-    if (scene->chunkCapacity < (size_t)pass.nUnits) {
-        HIP_TRY(scene->chunkBuf.allocate((size_t)pass.nUnits));
-        scene->chunkCapacity = (size_t)pass.nUnits;
+    if (scene->chunkCapacity < pass.bufferUnits()) {
+        HIP_TRY(scene->chunkBuf.allocate(pass.bufferUnits()));
+        scene->chunkCapacity = pass.bufferUnits();
     }
     if (!scene->counters.ptr) { HIP_TRY(scene->counters.allocate(kMaxPools * kCtrCount)); }
     if (!scene->stats.ptr) {
@@ -2204,13 +2228,12 @@ static int persistentPass(PathedScene *scene, const Pass &pass, int blocksPerCu,
     launch(params, dim3((unsigned)blocks), pass.stream);
     if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], pass.stream); }
     scene->traceLaunchesAll++;
-    const dim3 pixelGrid((unsigned)((pass.nPixels + kBlock - 1) / kBlock));
-    launchResolve(pass, params, pixelGrid, pass.stream);
+    launchResolve(pass, params, pass.stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(pass.stream));
 
     scene->iterations += 1;
-    scene->cameraSamples += (unsigned long long)pass.count * (unsigned long long)pass.nPixels;
+    scene->cameraSamples += (unsigned long long)pass.count * (unsigned long long)pass.unitPixels();
     return PATHED_OK;
 }
 
@@ -2276,6 +2299,22 @@ static int renderPassFused(PathedScene *scene, const Pass &pass)
 // (kernarg pair records), no tree walk.
 static int renderPassVolume(PathedScene *scene, const Pass &pass)
 {
+    if (pass.nList > 0) {
+        // a pixel list: k_list_volume<SMALL, GRID, MULTI> (kernels.h), the generic shape with 8 (small) or 22 stack rows in LDS
+        const bool small = scene->bruteForce;
+        const int rows = small ? 8 : 22;
+        return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, rows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
+            const size_t lds = (size_t)(rows + 1) * kBlock * sizeof(int);
+            params.smallQuads = 0;
+            params.smallKappaT = scene->smallLayout.kappaT;
+            params.scene.leafTris = scene->leafTris.ptr;
+            const bool grids = !scene->gridsHost.empty();
+            const bool multi = scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME;
+            withBool(small, [&](auto SMALL) { withBool(grids, [&](auto GRID) { withBool(multi, [&](auto MULTI) {
+                hipLaunchKernelGGL((k_list_volume<SMALL, GRID, MULTI>), grid, dim3(kBlock), lds, stream, params, scene->smallTris);
+            }); }); });
+        });
+    }
     return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, scene->stackRows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
         const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
         const bool small = scene->bruteForce;
@@ -2410,7 +2449,6 @@ static int renderPassHybrid(PathedScene *scene, const Pass &pass)
 static int renderPass(PathedScene *scene, const Pass &pass)
 {
     const hipStream_t stream = pass.stream;
-    const int nPixels = pass.nPixels;
     const unsigned long long nUnits64 = pass.nUnits;
 
     // small jobs use one pool; otherwise split slots and units evenly
@@ -2430,7 +2468,7 @@ static int renderPass(PathedScene *scene, const Pass &pass)
     const unsigned long long slotQuantum = (unsigned long long)kBlock * (scene->stagedShade ? scene->stageRounds : 1);
     const int slotsPerPool = (int)((wanted / pools + slotQuantum - 1) / slotQuantum * slotQuantum);
     const int nSlots = slotsPerPool * pools;
-    int code = ensureRenderState(scene, nSlots, (size_t)pass.nUnits);
+    int code = ensureRenderState(scene, nSlots, pass.bufferUnits());
     if (code != PATHED_OK) { return code; }
     if (pools > 1 && !scene->poolStreams[0]) {
         for (int h = 0; h < kMaxPools; h++) {
@@ -2605,14 +2643,13 @@ static int renderPass(PathedScene *scene, const Pass &pass)
             HIP_TRY(hipStreamWaitEvent(stream, scene->poolDone[h], 0));
         }
     }
-    const dim3 pixelGrid((unsigned)((nPixels + kBlock - 1) / kBlock));
-    launchResolve(pass, params[0], pixelGrid, stream);
+    launchResolve(pass, params[0], stream);
     for (int h = 0; h < pools; h++) { HIP_TRY(hipStreamSynchronize(streams[h])); }
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipGetLastError());
 
     scene->iterations += iteration;
-    scene->cameraSamples += (unsigned long long)pass.count * (unsigned long long)nPixels;
+    scene->cameraSamples += (unsigned long long)pass.count * (unsigned long long)pass.unitPixels();
     return PATHED_OK;
 }
 
@@ -2680,10 +2717,36 @@ static int launchFeatures(PathedScene *scene, uint64_t seed, uint32_t begin, uin
     return PATHED_OK;
 }
 
-// The body of pathed_hip_render_device and pathed_hip_render_moments_device: d_squares is null for the former, and a call
-// without it launches exactly what it always did.
+// k_check_list over a list in device memory: PATHED_OK, or PATHED_E_INVALID for a list that is not strictly ascending or
+// leaves the image.  Returns when the check has completed.
+static int checkPixelList(PathedScene *scene, const uint32_t *d_list, uint32_t count, hipStream_t stream)
+{
+    const int nPixels = scene->width * scene->height;
+    if (count > (uint32_t)nPixels) { return fail(PATHED_E_INVALID, "the pixel list is longer than the image has pixels"); }
+    DeviceBuffer<unsigned int> flag;
+    HIP_TRY(flag.allocate(1));
+    HIP_TRY(hipMemsetAsync(flag.ptr, 0, sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_check_list, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, d_list, (int)count, nPixels, flag.ptr);
+    HIP_TRY(hipGetLastError());
+    unsigned int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, flag.ptr, sizeof bad, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (bad) { return fail(PATHED_E_INVALID, "the pixel list must be strictly ascending with every index below width * height"); }
+    return PATHED_OK;
+}
+
+// The pixels of a render call: every pixel of the image (list null), or a list of them in device memory with the count image
+// that goes with it (pathed_hip_render_pixels_device).
+struct PixelList {
+    const uint32_t *list;
+    uint32_t count;
+    uint32_t *sampleCounts;
+};
+
+// The body of pathed_hip_render_device, pathed_hip_render_moments_device and pathed_hip_render_pixels_device: d_squares is null
+// for the first and `pixels` for the first two, and a call without them launches exactly what it always did.
 static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count, int start_bounce, int last_bounce,
-                      float *d_accum_rgb_sum, float *d_squares, void *stream_handle)
+                      float *d_accum_rgb_sum, float *d_squares, void *stream_handle, const PixelList *pixels = nullptr)
 {
     if (!scene || !d_accum_rgb_sum) { return fail(PATHED_E_INVALID, "null scene or accumulation buffer"); }
     if (start_bounce < 0 || (last_bounce != -1 && start_bounce > last_bounce)) {
@@ -2706,13 +2769,20 @@ static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uin
         return fail(PATHED_E_UNSUPPORTED, "a scene with a voxel-grid medium renders with the VolumePathTracer integrator only (pathed_hip_set_integrator)");
     }
     SELECT_DEVICE(scene);
+    hipStream_t stream = (hipStream_t)stream_handle;
+    if (pixels) {
+        // list passes run on the wavefront kernels or k_list_volume, the only ones that know the list order (kernels.h: THE UNIT ORDER)
+        if (scene->stagedShade || scene->splitShade) { return fail(PATHED_E_UNSUPPORTED, "pixel lists are not rendered by the staged or split shade stages"); }
+        // before anything else of a list render: a bad list renders nothing
+        const int code = checkPixelList(scene, pixels->list, pixels->count, stream);
+        if (code != PATHED_OK) { return code; }
+    }
     scene->lastCallFeatures = false;
 
     if (scene->timeKernels) {
         HIP_TRY(scene->traceEvents.create());
         HIP_TRY(scene->shadeEvents.create());
     }
-    hipStream_t stream = (hipStream_t)stream_handle;
 
     // passes of at most chunk * kMaxChunksPerPass samples keep the partial-sum buffer bounded
     int chunksPerPass = kMaxChunksPerPass;
@@ -2728,15 +2798,19 @@ static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uin
     }
     const uint32_t perPass = (uint32_t)scene->samplesPerUnit * (uint32_t)chunksPerPass;
     // BVH scenes: short calls on the wave path kernel, long ones on the wavefront (the counting instantiations are the wavefront's)
-    const unsigned long long callSamples = (unsigned long long)scene->width * (unsigned long long)scene->height * (unsigned long long)spp_count;
+    // (a call over a pixel list counts the samples it renders: those of the listed pixels)
+    const unsigned long long callPixels = pixels ? (unsigned long long)pixels->count : (unsigned long long)scene->width * (unsigned long long)scene->height;
+    const unsigned long long callSamples = callPixels * (unsigned long long)spp_count;
     const bool wavePath = scene->waveAvailable && !usesVolumeKernel(scene) && !scene->countMode
         && (scene->waveMode == 2 || (scene->waveMode == 0 && (callSamples < scene->waveMaxSamples || scene->sceneInLds)));
     // (trees small enough for the trace kernel's LDS copy -- the Cornell box with its two meshes: k_path_wave, whose node reads
     // hit L1 / L2, is level with the wavefront or 11 % ahead at every length, profiles/r4_ab_wave.log)
     // [r5] ... and scenes of 65 .. 4096 triangles on the hybrid kernel at every length (counting is the wavefront's)
     const bool hybridPath = scene->hybridPath && !usesVolumeKernel(scene) && !scene->countMode;
-    scene->lastCallWave = wavePath && !hybridPath;
-    scene->lastCallHybrid = hybridPath;
+    const bool listPass = pixels != nullptr;   // ... and a call over a pixel list on the wavefront (k_list_volume with media), whatever the scene
+    scene->lastCallWave = wavePath && !hybridPath && !listPass;
+    scene->lastCallHybrid = hybridPath && !listPass;
+    scene->lastCallList = listPass;
     Pass pass;
     pass.seed = seed;
     pass.startBounce = start_bounce;
@@ -2746,15 +2820,19 @@ static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uin
     pass.stream = stream;
     pass.nPixels = scene->width * scene->height;
     pass.chunk = scene->samplesPerUnit;
+    pass.pixelList = pixels ? pixels->list : nullptr;
+    pass.nList = pixels ? (int)pixels->count : 0;
+    pass.counts = pixels ? pixels->sampleCounts : nullptr;
     uint32_t done = 0;
     while (done < spp_count) {
         pass.begin = spp_begin + done;
         pass.count = (spp_count - done < perPass) ? (spp_count - done) : perPass;
         pass.chunksPerPixel = (int)((pass.count + (uint32_t)pass.chunk - 1) / (uint32_t)pass.chunk);
-        const unsigned long long nUnits = (unsigned long long)pass.nPixels * (unsigned long long)pass.chunksPerPixel;
+        const unsigned long long nUnits = (unsigned long long)pass.unitPixels() * (unsigned long long)pass.chunksPerPixel;
         if (nUnits >= 0xFFFFFFF0ull) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
         pass.nUnits = (unsigned int)nUnits;
         const int code = usesVolumeKernel(scene) ? renderPassVolume(scene, pass)
+            : listPass ? renderPass(scene, pass)
             : scene->fusedPath ? renderPassFused(scene, pass)
             : hybridPath ? renderPassHybrid(scene, pass)
             : wavePath ? renderPassWave(scene, pass)
@@ -2858,6 +2936,84 @@ int pathed_hip_noise_estimate_device(PathedScene *scene, const float *d_rgb_sum,
     out->max_error = (double)maxError;
     out->pixels_above = above;
     return PATHED_OK;
+}
+
+int pathed_hip_select_pixels_device(PathedScene *scene, const float *d_rgb_sum, const float *d_rgb_sq_sum, const uint32_t *d_count,
+                                    float floor, float threshold, float *d_error, uint32_t *d_list, uint32_t *n_list,
+                                    PathedNoise *out, void *stream_handle)
+{
+    if (!scene || !d_rgb_sum || !d_rgb_sq_sum || !d_count || !d_list || !n_list || !out) {
+        return fail(PATHED_E_INVALID, "null scene, sum buffer, sum-of-squares buffer, count image, list, list length or result");
+    }
+    if (out->struct_size != sizeof(PathedNoise)) { return fail(PATHED_E_INVALID, "PathedNoise.struct_size does not match this library"); }
+    if (!(floor > 0.f) || !std::isfinite(floor)) { return fail(PATHED_E_INVALID, "the noise floor must be a finite number > 0"); }
+    SELECT_DEVICE(scene);
+    hipStream_t stream = (hipStream_t)stream_handle;
+    const int nPixels = scene->width * scene->height;
+    const unsigned int blocks = (unsigned int)((nPixels + kBlock - 1) / kBlock);
+    DeviceBuffer<NoisePartial> partials;
+    DeviceBuffer<uint32_t> selected, offsets;
+    HIP_TRY(partials.allocate(blocks));
+    HIP_TRY(selected.allocate((size_t)blocks * kBlock));
+    HIP_TRY(offsets.allocate((size_t)blocks + 1));
+    NoiseSelectParams params;
+    params.sum = d_rgb_sum;
+    params.squares = d_rgb_sq_sum;
+    params.count = d_count;
+    params.nPixels = nPixels;
+    params.floor = floor;
+    params.threshold = threshold;
+    params.error = d_error;
+    params.partials = partials.ptr;
+    params.selected = selected.ptr;
+    hipLaunchKernelGGL(k_noise_select, dim3(blocks), dim3(kBlock), 0, stream, params);
+    HIP_TRY(hipGetLastError());
+    std::vector<NoisePartial> host(blocks);
+    HIP_TRY(hipMemcpyAsync(host.data(), partials.ptr, blocks * sizeof(NoisePartial), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    double sum = 0.0;
+    float maxError = 0.f;
+    uint64_t above = 0;
+    uint32_t invalid = 0;
+    std::vector<uint32_t> hostOffsets((size_t)blocks + 1, 0u);
+    for (unsigned int b = 0; b < blocks; b++) {   // in block order
+        const NoisePartial &partial = host[b];
+        sum += partial.sum;
+        if (partial.maxError > maxError) { maxError = partial.maxError; }
+        above += partial.above;
+        invalid += partial.invalid;
+        hostOffsets[b + 1] = hostOffsets[b] + partial.unused;   // the block's selected pixels
+    }
+    const uint32_t total = hostOffsets[blocks];
+    if (total > 0u) {
+        HIP_TRY(hipMemcpyAsync(offsets.ptr, hostOffsets.data(), hostOffsets.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_place_list, dim3(blocks), dim3(kBlock), 0, stream, selected.ptr, offsets.ptr, d_list);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    *n_list = total;
+    out->invalid_pixels = invalid;
+    out->mean_error = sum / (double)nPixels;
+    out->max_error = (double)maxError;
+    out->pixels_above = above;
+    return PATHED_OK;
+}
+
+int pathed_hip_render_pixels_device(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uint32_t spp_count, int start_bounce, int last_bounce,
+                                    const uint32_t *d_list, uint32_t n_list, float *d_rgb_sum, float *d_rgb_sq_sum, uint32_t *d_count,
+                                    void *stream_handle)
+{
+    if (!scene || !d_rgb_sum || !d_rgb_sq_sum || !d_count) { return fail(PATHED_E_INVALID, "null scene, sum buffer, sum-of-squares buffer or count image"); }
+    if (scene->samplesPerUnit != 1) {
+        return fail(PATHED_E_INVALID, "a render over a pixel list keeps second moments and needs one sample per unit (pathed_hip_set_samples_per_unit(scene, 1))");
+    }
+    if (scene->integrator == PATHED_INTEGRATOR_ALBEDO) {
+        return fail(PATHED_E_UNSUPPORTED, "pixel lists are not rendered under the albedo integrator: its render calls run the feature kernel, which has no unit buffer");
+    }
+    if (n_list == 0) { return PATHED_OK; }
+    if (!d_list) { return fail(PATHED_E_INVALID, "null pixel list"); }
+    const PixelList pixels = { d_list, n_list, d_count };
+    return renderCall(scene, seed, spp_begin, spp_count, start_bounce, last_bounce, d_rgb_sum, d_rgb_sq_sum, stream_handle, &pixels);
 }
 
 int pathed_hip_scene_set_camera(PathedScene *scene, const PathedCamera *camera)
@@ -3416,7 +3572,7 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
     out->bvh_build_ms = scene->bvhBuildMs;
     out->bvh_builder = (uint32_t)scene->bvhBuilder;
     out->trace_launches_all = (uint32_t)scene->traceLaunchesAll;
-    out->path_kernel = scene->lastCallFeatures ? 8u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? 9u : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
+    out->path_kernel = scene->lastCallFeatures ? 8u : (scene->lastCallList && !usesVolumeKernel(scene)) ? 1u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? 9u : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
     if (tuningEnv("PATHED_SHADE_PROFILE")) {   // counters exist in -DPATHED_SHADE_PROFILE builds only
         static const char *regions[11] = { "all waves", "active slots", "makeIsect (hit)", "camera-ray vertex", "finish previous MIS term",
                                            "new vertex: BSDF sample", "light sampling", "sample finished", "startSample (regeneration)", "shadow ray pushed",

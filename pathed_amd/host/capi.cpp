@@ -231,6 +231,7 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
         integrator->setUseRccl(reduce == "rccl");
         integrator->setFeatures(features);
         if (noise.collect) { integrator->setNoise(noise.target, noise.minSpp, noise.floor); }
+        integrator->setAdaptive(noise.adaptive);
         if (earlyComm) { integrator->adoptComm(earlyComm); earlyComm = nullptr; }
         const std::string metricsLevel = job.metricsLevel();
         if (metricsLevel != "full" && metricsLevel != "basic") { throw std::runtime_error("job: \"metrics\" must be \"full\" or \"basic\""); }
@@ -256,7 +257,8 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
             PathedStats stats;
             std::memset(&stats, 0, sizeof stats);
             pathed_hip_get_stats(scene.handle(), &stats);
-            const double samples = (double)m.width * m.height * (double)(m.lastSample - m.firstSample);
+            // (an adaptive run: the samples it rendered, not pixels x the largest count)
+            const double samples = m.adaptive ? (double)m.samplesRendered : (double)m.width * m.height * (double)(m.lastSample - m.firstSample);
             // what the reference prints per render (RTCManager::printStats, src/rtc_manager.cpp:94-115) and per wave
             // (src/integrator.cpp:97-102), as rates: a one-sample counting pass over sample index `spp` into a scratch
             // buffer (the COUNT kernel variants never run inside the timed loop)
@@ -315,6 +317,12 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
                 }
                 out << "],\n";
                 out << "  \"stopped_on_noise\": " << (m.stoppedOnNoise ? "true" : "false") << ",\n";
+            }
+            if (m.adaptive) {
+                out << "  \"samples_rendered\": " << m.samplesRendered << ", \"adaptive_rounds\": " << m.adaptiveRounds
+                    << ", \"pixels_at_cap\": " << m.pixelsAtCap << ",\n";
+                out << "  \"uniform_spp\": " << m.uniformSpp << ", \"uniform_samples\": "
+                    << (unsigned long long)m.uniformSpp * (unsigned long long)m.width * (unsigned long long)m.height << ",\n";
             }
             out << "  \"dropped_samples\": " << stats.dropped_samples << "\n";
             out << "}\n";

@@ -189,6 +189,7 @@ void Integrator::run(
     std::function<void(RenderStatus)> callback,
     bool *quit
 ) {
+    if (m_adaptive) { runAdaptive(image, scene, callback, quit); return; }
     const int width = scene.width();
     const int height = scene.height();
     const int primarySamples = m_spp;
@@ -495,6 +496,149 @@ void Integrator::run(
     m_metrics.height = height;
 }
 
+// job key "adaptive": the schedule of job.h.  Everything stays on replica 0's device between the rounds; the host sees the
+// three images when files are due -- after the first step and after every round.
+void Integrator::runAdaptive(Image &image, Scene &scene, std::function<void(RenderStatus)> callback, bool *quit)
+{
+    const int width = scene.width();
+    const int height = scene.height();
+    const size_t pixels = (size_t)width * height;
+    const size_t floats = 3 * pixels;
+    if (scene.replicas() != 1) { throw std::runtime_error("job: \"adaptive\" renders on one GPU: \"gpus\" must be 1 (a pixel list is not sharded)"); }
+    if (!(m_targetNoise > 0.0)) { throw std::runtime_error("job: \"adaptive\" needs \"target_noise\""); }
+    if (m_resume) { throw std::runtime_error("job: \"adaptive\" does not go with \"resume\": the state file holds neither squares nor counts"); }
+
+    printf("Beginning pre-process...\n");
+    preprocess(scene);
+    printf("Pre-process complete (0.0s elapsed)\n");
+
+    // sums, squares, counts and the list: four buffers on the device (a uint32 is held as the float of the same bits)
+    float *buffers[4] = { nullptr, nullptr, nullptr, nullptr };
+    struct Cleanup {
+        Scene &scene;
+        float *(&buffers)[4];
+        ~Cleanup() { for (float *buffer : buffers) { if (buffer) { pathed_hip_accum_free(scene.handle(0), buffer); } } }
+    } cleanup{ scene, buffers };
+    const size_t sizes[4] = { floats, floats, pixels, pixels };
+    for (int k = 0; k < 4; k++) {
+        if (pathed_hip_accum_alloc(scene.handle(0), sizes[k], &buffers[k]) != PATHED_OK) { throw std::runtime_error(hipError("pathed_hip_accum_alloc")); }
+    }
+    float *deviceSums = buffers[0], *deviceSquares = buffers[1];
+    uint32_t *deviceCounts = reinterpret_cast<uint32_t *>(buffers[2]), *deviceList = reinterpret_cast<uint32_t *>(buffers[3]);
+
+    m_metrics = RenderMetrics();
+    m_metrics.replicas = 1;
+    m_metrics.replicaSeconds.assign(1, 0.0);
+    m_metrics.collectedMoments = true;
+    m_metrics.adaptive = true;
+    m_metrics.width = width;
+    m_metrics.height = height;
+    const auto loopBegin = std::chrono::steady_clock::now();
+
+    std::vector<float> radianceLookup(floats), squaresLookup(floats);
+    std::vector<uint32_t> counts(pixels);
+    // the files of one state: auto (sum / count), auto-stderr, auto-spp; numbered by the active pixels' count n
+    auto publish = [&](int n, bool last) {
+        const auto reduceBegin = std::chrono::steady_clock::now();
+        if (pathed_hip_accum_download(scene.handle(0), deviceSums, floats, radianceLookup.data()) != PATHED_OK
+            || pathed_hip_accum_download(scene.handle(0), deviceSquares, floats, squaresLookup.data()) != PATHED_OK
+            || pathed_hip_accum_download(scene.handle(0), buffers[2], pixels, reinterpret_cast<float *>(counts.data())) != PATHED_OK) {
+            throw std::runtime_error(hipError("pathed_hip_accum_download"));
+        }
+        m_metrics.reduceSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - reduceBegin).count();
+        m_metrics.reduces++;
+        const bool checkpoint = (n & (n - 1)) == 0 && !last;
+        Image stderrImage(width, height, image.outputDirectory()), countImage(width, height, image.outputDirectory());
+        stderrImage.setSpp(n);
+        countImage.setSpp(n);
+        {
+            std::lock_guard<std::mutex> guard(image.getLock());
+            image.setSpp(n);
+            for (int row = 0; row < height; row++) {
+                for (int col = 0; col < width; col++) {
+                    const size_t pixel = (size_t)row * width + col, index = 3 * pixel;
+                    const float samples = (float)counts[pixel], bessel = samples / (samples - 1.f);
+                    float error[3];
+                    for (int c = 0; c < 3; c++) {
+                        const float mean = radianceLookup[index + c] / samples;
+                        const float spread = squaresLookup[index + c] / samples - mean * mean;
+                        const float variance = (spread > 0.f ? spread : 0.f) * bessel;
+                        error[c] = counts[pixel] >= 2u ? std::sqrt(variance / samples) : 0.f;
+                    }
+                    image.set(row, col, radianceLookup[index + 0] / samples, radianceLookup[index + 1] / samples, radianceLookup[index + 2] / samples);
+                    stderrImage.set(row, col, error[0], error[1], error[2]);
+                    countImage.set(row, col, samples, samples, samples);
+                }
+            }
+            if (checkpoint) { image.saveCheckpoint("auto"); } else { image.save("auto"); }
+        }
+        if (checkpoint) { stderrImage.saveCheckpoint("auto-stderr"); countImage.saveCheckpoint("auto-spp"); }
+        else { stderrImage.save("auto-stderr"); countImage.save("auto-spp"); }
+    };
+
+    // 1. min(minSpp, spp) samples of every pixel
+    int n = std::min(m_minSpp, m_spp);
+    {
+        const auto begin = std::chrono::steady_clock::now();
+        for (int done = 0; done < n;) {
+            const int count = std::min(m_sppPerLaunch, n - done);
+            sampleImage(deviceSums, deviceSquares, scene, 0, (unsigned)done, (unsigned)count);
+            done += count;
+        }
+        std::fill(counts.begin(), counts.end(), (uint32_t)n);
+        if (pathed_hip_accum_upload(scene.handle(0), buffers[2], pixels, reinterpret_cast<const float *>(counts.data())) != PATHED_OK) {
+            throw std::runtime_error(hipError("pathed_hip_accum_upload"));
+        }
+        m_metrics.replicaSeconds[0] += std::chrono::duration<double>(std::chrono::steady_clock::now() - begin).count();
+        m_metrics.samplesRendered = (unsigned long long)n * pixels;
+    }
+
+    // 2., 3. the rounds
+    for (;;) {
+        PathedNoise figure;
+        std::memset(&figure, 0, sizeof figure);
+        figure.struct_size = sizeof figure;
+        uint32_t listCount = 0;
+        if (pathed_hip_select_pixels_device(scene.handle(0), deviceSums, deviceSquares, deviceCounts, (float)m_noiseFloor, (float)m_targetNoise,
+                                            nullptr, deviceList, &listCount, &figure, nullptr) != PATHED_OK) {
+            throw std::runtime_error(hipError("pathed_hip_select_pixels_device"));
+        }
+        m_metrics.noise.push_back({ n, figure.mean_error, figure.max_error });
+        const bool stopping = quit && *quit;
+        const bool last = listCount == 0 || n >= m_spp || stopping;
+        publish(n, last);
+        RenderStatus status;
+        status.sample = n;
+        status.elapsedSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - loopBegin).count();
+        if (callback) { callback(status); }
+        std::ostringstream line;
+        line << "[" << m_logPrefix << "] sample: " << n << "/" << m_spp << std::fixed << std::setprecision(1) << " (" << status.elapsedSeconds
+             << "s elapsed) noise: " << std::setprecision(6) << figure.mean_error << " active pixels: " << listCount << "/" << pixels;
+        std::cout << line.str() << std::endl;
+        if (last) {
+            m_metrics.stoppedOnNoise = listCount == 0;
+            break;
+        }
+        const int following = (int)std::min<long long>(2ll * n, (long long)m_spp);
+        const auto begin = std::chrono::steady_clock::now();
+        for (int done = n; done < following;) {
+            const int count = std::min(m_sppPerLaunch, following - done);
+            samplePixels(deviceSums, deviceSquares, deviceCounts, deviceList, listCount, scene, (unsigned)done, (unsigned)count);
+            done += count;
+        }
+        m_metrics.replicaSeconds[0] += std::chrono::duration<double>(std::chrono::steady_clock::now() - begin).count();
+        m_metrics.samplesRendered += (unsigned long long)(following - n) * listCount;
+        m_metrics.adaptiveRounds++;
+        n = following;
+        postwave(scene, n);
+    }
+    m_metrics.uniformSpp = n;   // a uniform render that holds every pixel to the same criterion takes all of them to the largest count
+    for (uint32_t count : counts) { if (count == (uint32_t)m_spp) { m_metrics.pixelsAtCap++; } }
+    m_metrics.firstSample = 0;
+    m_metrics.lastSample = n;
+    m_metrics.loopSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - loopBegin).count();
+}
+
 void Integrator::setStateIdentity(const std::string &identity)
 {
     unsigned long long hash = 1469598103934665603ull;   // FNV-1a
@@ -566,6 +710,21 @@ void HipPathTracer::sampleImage(float *deviceSums, float *deviceSquares, Scene &
         deviceSums, nullptr, 1);
     if (code != PATHED_OK) {
         throw std::runtime_error(std::string("pathed_hip_render_device: ") + pathed_hip_last_error());
+    }
+}
+
+void HipPathTracer::samplePixels(float *deviceSums, float *deviceSquares, uint32_t *deviceCounts, const uint32_t *deviceList, uint32_t listCount,
+                                 Scene &scene, unsigned begin, unsigned count)
+{
+    if (pathed_hip_set_integrator(scene.handle(0), m_integrator) != PATHED_OK) {
+        throw std::runtime_error(std::string("pathed_hip_set_integrator: ") + pathed_hip_last_error());
+    }
+    const int code = pathed_hip_render_pixels_device(
+        scene.handle(0), m_seed, begin, count,
+        m_bounceController.startBounce(), m_bounceController.lastBounce(),
+        deviceList, listCount, deviceSums, deviceSquares, deviceCounts, nullptr);
+    if (code != PATHED_OK) {
+        throw std::runtime_error(std::string("pathed_hip_render_pixels_device: ") + pathed_hip_last_error());
     }
 }
 

@@ -39,6 +39,12 @@ struct RenderMetrics {
     std::vector<Noise> noise;              // the noise figure at every checkpoint it was estimated at (setNoise)
     bool collectedMoments = false;         // the run rendered through pathed_hip_render_moments_device
     bool stoppedOnNoise = false;           // ... and ended before `spp` because the figure reached the target
+    // setAdaptive: the run rendered pixel lists
+    bool adaptive = false;
+    unsigned long long samplesRendered = 0;   // camera samples, all pixels and rounds
+    int adaptiveRounds = 0;
+    unsigned long long pixelsAtCap = 0;       // pixels that hold `spp` samples
+    int uniformSpp = 0;                       // the largest count: what a uniform render to the same per-pixel criterion gives every pixel
 };
 
 // Host-side Scene: the parsed description plus its upload (reference include/scene.h:83-130
@@ -121,6 +127,11 @@ public:
     // from minSpp on and at the end.  With targetNoise > 0 it stops at the first such estimate at or below the target; `spp`
     // stays the cap.  The squares are not in auto.state: such a job does not resume.
     void setNoise(double targetNoise, int minSpp, double floor) { m_collectMoments = true; m_targetNoise = targetNoise; m_minSpp = minSpp; m_noiseFloor = floor; }
+    // job key "adaptive" (job.h has the schedule): beside setNoise with a target.  One replica; run() then renders min(minSpp, spp)
+    // samples of every pixel and goes on in rounds over the pixels whose own error is above the target
+    // (pathed_hip_select_pixels_device, samplePixels), writes auto*.exr (sum / count per pixel), auto-stderr*.exr and
+    // auto-spp*.exr (the counts) after the first step and after every round, and fills the adaptive fields of the metrics.
+    void setAdaptive(bool adaptive) { m_adaptive = adaptive; }
     const RenderMetrics &metrics() const { return m_metrics; }
 
 protected:
@@ -128,6 +139,11 @@ protected:
     // `deviceSums` that live on replica `replica`'s device (reference sampleImage adds exactly one
     // sample to radianceLookup), and their squares to `deviceSquares` when that is not null
     virtual void sampleImage(float *deviceSums, float *deviceSquares, Scene &scene, size_t replica, unsigned begin, unsigned count) = 0;
+    // the same for the `listCount` pixels of `deviceList` alone, whose entries of `deviceCounts` grow by `count`
+    // (pathed_hip_render_pixels_device)
+    virtual void samplePixels(float *deviceSums, float *deviceSquares, uint32_t *deviceCounts, const uint32_t *deviceList, uint32_t listCount,
+                              Scene &scene, unsigned begin, unsigned count) = 0;
+    void runAdaptive(Image &image, Scene &scene, std::function<void(RenderStatus)> callback, bool *quit);
 
     int m_spp = 1;
     unsigned long long m_seed = 1;
@@ -143,6 +159,7 @@ protected:
     double m_targetNoise = 0.0;   // 0 = none
     int m_minSpp = 16;
     double m_noiseFloor = 0.01;
+    bool m_adaptive = false;
     PathedComm *m_adoptedComm = nullptr;
     unsigned long long m_stateDigest = 0;
     std::string m_statePath;
@@ -161,6 +178,8 @@ public:
 
 protected:
     void sampleImage(float *deviceSums, float *deviceSquares, Scene &scene, size_t replica, unsigned begin, unsigned count) override;
+    void samplePixels(float *deviceSums, float *deviceSquares, uint32_t *deviceCounts, const uint32_t *deviceList, uint32_t listCount,
+                      Scene &scene, unsigned begin, unsigned count) override;
     int stateStartBounce() const override { return m_bounceController.startBounce(); }
     int stateLastBounce() const override { return m_bounceController.lastBounce(); }
 

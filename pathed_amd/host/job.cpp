@@ -93,6 +93,15 @@ Job::NoiseSettings Job::noise() const
     const Json &image = m_json["stderr_image"];
     if (!image.isNull() && !image.isBool()) { throw std::runtime_error("job: \"stderr_image\" must be true or false"); }
     settings.collect = settings.target > 0.0 || (image.isBool() && image.asBool());
+    const Json &adaptive = m_json["adaptive"];
+    if (!adaptive.isNull() && !adaptive.isBool()) { throw std::runtime_error("job: \"adaptive\" must be true or false"); }
+    settings.adaptive = adaptive.isBool() && adaptive.asBool();
+    if (settings.adaptive) {
+        if (!(settings.target > 0.0)) { throw std::runtime_error("job: \"adaptive\" needs \"target_noise\": the pixels above it are the ones rendered on"); }
+        if (resume()) { throw std::runtime_error("job: \"adaptive\" does not go with \"resume\": the state file holds neither squares nor counts"); }
+        if (devices().size() != 1) { throw std::runtime_error("job: \"adaptive\" renders on one GPU: \"gpus\" must be 1 (a pixel list is not sharded)"); }
+        if (integratorName() == "AlbedoIntegrator") { throw std::runtime_error("job: \"adaptive\" does not go with the AlbedoIntegrator, which keeps no second moments"); }
+    }
     if (settings.collect && resume()) {
         throw std::runtime_error(std::string("job: \"resume\" does not go with \"") + (settings.target > 0.0 ? "target_noise" : "stderr_image")
                                  + "\": the state file holds no squares");

@@ -23,6 +23,21 @@
 //   "stderr_image" (false; implied by "target_noise"): write the per-channel standard error of the mean as auto-stderr*.exr
 //               beside every auto*.exr and record the figure in the log and in metrics.json ("noise", "stopped_on_noise").
 //               Neither key goes with "resume": the state file holds no squares.  Bad values are refused by name.
+//   "adaptive" (false; needs "target_noise"): render on only the pixels that are still noisy.  The schedule is fixed:
+//                 1. min("min_spp", "spp") samples of every pixel (pathed_hip_render_moments_device);
+//                 2. rounds: each selects, among the pixels still active, those whose OWN error e exceeds "target_noise"
+//                    (pathed_hip_select_pixels_device) and takes them from n to min(2 n, "spp") samples
+//                    (pathed_hip_render_pixels_device).  A pixel that was not selected has retired and stays retired: its sums,
+//                    and so its e, no longer change.  All active pixels therefore share one count n;
+//                 3. the run ends when no pixel is selected or n has reached "spp".
+//               The criterion is PER PIXEL -- stricter than the image-mean criterion of a "target_noise" run without
+//               "adaptive", which stops once the MEAN of e is at or below the target and leaves its noisiest pixels above it.
+//               The image is sum / count per pixel.  Written beside auto*.exr and auto-stderr*.exr after the first step
+//               and after every round: auto-spp*.exr, the count image (HALF: whole numbers are exact up to 2048, even ones up
+//               to 4096, ..).  metrics.json gains "samples_rendered", "adaptive_rounds", "pixels_at_cap" (pixels that hold
+//               "spp" samples), "uniform_spp" and "uniform_samples" (for comparison: the largest count, which a uniform render
+//               held to the same per-pixel criterion would give EVERY pixel, and that times the pixels).  "adaptive" is refused by name beside "resume", more than one GPU and the
+//               AlbedoIntegrator; sharding a pixel list over GPUs is not done.
 #pragma once
 
 #include "bounce_controller.h"
@@ -83,6 +98,7 @@ public:
         int minSpp = 16;
         double floor = 0.01;
         bool collect = false;  // a target or "stderr_image": the run keeps second moments
+        bool adaptive = false; // "adaptive": pixel lists (needs a target)
     };
     NoiseSettings noise() const;
     int gpu() const { return m_json["gpu"].isNumber() ? m_json["gpu"].asInt() : 0; }

@@ -246,6 +246,107 @@ class HipScene:
         return {"mean_error": noise.mean_error, "max_error": noise.max_error, "pixels_above": int(noise.pixels_above),
                 "invalid_pixels": int(noise.invalid_pixels)}
 
+    def device_words(self, count, host=None):
+        """`count` uint32 on the scene's device -- a count image or a pixel list -- zeroed or filled from `host`; free with
+        free_device_buffer.  (A word is moved as the float of the same bits: the copies are plain memory copies.)"""
+        if host is not None:
+            host = np.ascontiguousarray(host, dtype=np.uint32).reshape(-1).view(np.float32)
+        return self.device_buffer(count, host)
+
+    def download_device_words(self, pointer, out):
+        """Copies out.size uint32 from device memory at `pointer` into the uint32 array `out`."""
+        assert out.dtype == np.uint32 and out.flags["C_CONTIGUOUS"]
+        self.download_device_buffer(pointer, out.view(np.float32))
+        return out
+
+    def select_pixels(self, sum_pointer, squares_pointer, count_pointer, list_pointer, floor=0.01, threshold=0.0, error_pointer=0, stream=0):
+        """The noise figure with a sample count per pixel, and the pixels still to render (pathed_hip_select_pixels_device):
+        device pointers to the two sum images (3 W H floats), the count image (W H uint32), room for W H uint32 at
+        `list_pointer` and, optionally, W H floats for the per-pixel error.  The list receives, in ascending order, the pixels
+        with error > threshold or fewer than 2 samples.  Returns (n_list, figure) with noise_estimate's figure."""
+        noise = _capi.PathedNoise()
+        noise.struct_size = C.sizeof(_capi.PathedNoise)
+        n_list = C.c_uint32(0)
+        code = self._lib.pathed_hip_select_pixels_device(
+            self._handle, C.c_void_p(sum_pointer or None), C.c_void_p(squares_pointer or None), C.c_void_p(count_pointer or None),
+            float(floor), float(threshold), C.c_void_p(error_pointer or None), C.c_void_p(list_pointer or None), C.byref(n_list),
+            C.byref(noise), C.c_void_p(stream))
+        _check(self._lib, code, "pathed_hip_select_pixels_device")
+        return int(n_list.value), {"mean_error": noise.mean_error, "max_error": noise.max_error, "pixels_above": int(noise.pixels_above),
+                                   "invalid_pixels": int(noise.invalid_pixels)}
+
+    def render_pixels(self, seed, spp_begin, spp_count, start_bounce, last_bounce, list_pointer, n_list,
+                      sum_pointer, squares_pointer, count_pointer, stream=0):
+        """Samples [spp_begin, spp_begin + spp_count) of the `n_list` pixels listed (ascending uint32 pixel indices, device
+        memory) and of no other pixel (pathed_hip_render_pixels_device): their sums and square sums continue exactly as
+        render_moments_device would continue them, their counts grow by spp_count."""
+        code = self._lib.pathed_hip_render_pixels_device(
+            self._handle, C.c_uint64(seed), spp_begin, spp_count, start_bounce, last_bounce,
+            C.c_void_p(list_pointer or None), int(n_list), C.c_void_p(sum_pointer or None), C.c_void_p(squares_pointer or None),
+            C.c_void_p(count_pointer or None), C.c_void_p(stream))
+        _check(self._lib, code, "pathed_hip_render_pixels_device")
+
+    def render_adaptive(self, seed, spp, start_bounce, last_bounce, target_noise, min_spp=16, floor=0.01, spp_per_launch=1024,
+                        on_round=None):
+        """Renders until every pixel's own error is at or below `target_noise`, `spp` being the cap -- the schedule of the C++
+        host's job key "adaptive" (pathed_amd/host/job.h): min(min_spp, spp) samples of every pixel; then rounds, each of which
+        selects the pixels with error > target_noise (select_pixels) and takes them from n to min(2 n, spp) samples
+        (render_pixels); the run ends when no pixel is selected or n == spp.  A pixel that is not selected never is again (its
+        sums, and so its error, no longer change), so all listed pixels share one count.  Everything stays on the device
+        between rounds.  on_round(n, n_list, figure), if given, is called after every selection.
+        Returns a dict: sums, squares (H, W, 3) float32, counts (H, W) uint32, rounds, samples_rendered, pixels_at_cap
+        (pixels that hold `spp` samples), noise (the figure of the final state) and history [(n, n_list, mean_error)]."""
+        if not float(target_noise) > 0.0:
+            raise PathedError("target_noise must be a number > 0")
+        if int(min_spp) != min_spp or int(min_spp) < 2:
+            raise PathedError("min_spp must be an integer >= 2")
+        spp, min_spp, spp_per_launch = int(spp), int(min_spp), max(1, int(spp_per_launch))
+        pixels = self.width * self.height
+        buffers = []
+        try:
+            sums, squares = self.device_buffer(3 * pixels), None
+            buffers.append(sums)
+            squares = self.device_buffer(3 * pixels)
+            buffers.append(squares)
+            n = min(min_spp, spp)
+            counts = self.device_words(pixels, np.full(pixels, n, dtype=np.uint32))
+            buffers.append(counts)
+            pixel_list = self.device_words(pixels)
+            buffers.append(pixel_list)
+            done = 0
+            while done < n:
+                count = min(spp_per_launch, n - done)
+                self.render_moments_device(seed, done, count, start_bounce, last_bounce, sums, squares)
+                done += count
+            rounds, rendered, history = 0, n * pixels, []
+            while True:
+                n_list, figure = self.select_pixels(sums, squares, counts, pixel_list, floor=floor, threshold=target_noise)
+                history.append((n, n_list, figure["mean_error"]))
+                if on_round is not None:
+                    on_round(n, n_list, figure)
+                if n_list == 0 or n >= spp:
+                    break
+                following = min(2 * n, spp)
+                done = n
+                while done < following:
+                    count = min(spp_per_launch, following - done)
+                    self.render_pixels(seed, done, count, start_bounce, last_bounce, pixel_list, n_list, sums, squares, counts)
+                    done += count
+                rendered += (following - n) * n_list
+                rounds += 1
+                n = following
+            out = {"sums": np.zeros((self.height, self.width, 3), dtype=np.float32),
+                   "squares": np.zeros((self.height, self.width, 3), dtype=np.float32),
+                   "counts": np.zeros((self.height, self.width), dtype=np.uint32)}
+            self.download_device_buffer(sums, out["sums"])
+            self.download_device_buffer(squares, out["squares"])
+            self.download_device_words(counts, out["counts"])
+        finally:
+            for pointer in buffers:
+                self.free_device_buffer(pointer)
+        out.update(rounds=rounds, samples_rendered=rendered, pixels_at_cap=int((out["counts"] == spp).sum()), noise=figure, history=history)
+        return out
+
     def trace(self, rays, any_hit=False):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         n = rays.shape[0]
@@ -433,7 +534,7 @@ class PathTracer:
     reference's PDFIntegrator also overrides run()).
     """
 
-    def __init__(self, bounce_controller, spp=1, seed=1, spp_per_launch=1024, target_noise=None, min_spp=16, noise_floor=0.01):
+    def __init__(self, bounce_controller, spp=1, seed=1, spp_per_launch=1024, target_noise=None, min_spp=16, noise_floor=0.01, adaptive=False):
         self.bounce_controller = bounce_controller
         self.spp = spp
         self.seed = seed
@@ -452,6 +553,31 @@ class PathTracer:
         self.noise_floor = float(noise_floor)
         self.noise_history = []      # (spp, mean_error) at every checkpoint the figure was estimated at
         self.stopped_on_noise = False
+        # adaptive sampling (job key "adaptive"): the target holds per pixel, and only the pixels above it are rendered on
+        if adaptive and target_noise is None:
+            raise PathedError("adaptive needs target_noise")
+        self.adaptive = bool(adaptive)
+        self.sample_counts = None    # (H, W) uint32 after an adaptive run
+        self.adaptive_result = None  # ... and HipScene.render_adaptive's dict
+
+    def _run_adaptive(self, image, scene, callback):
+        """run() with adaptive=True: HipScene.render_adaptive; the image is sum / count per pixel.  The callback is called after
+        every selection with the sample count of the pixels still active (noise_history gets the image's mean error there)."""
+        self.noise_history = []
+
+        def on_round(n, n_list, figure):
+            self.noise_history.append((n, figure["mean_error"]))
+            if callback is not None:
+                callback(n, (n & (n - 1)) == 0)
+
+        result = scene.render_adaptive(self.seed, self.spp, self.bounce_controller.start_bounce, self.bounce_controller.last_bounce,
+                                       self.target_noise, min_spp=self.min_spp, floor=self.noise_floor,
+                                       spp_per_launch=self.spp_per_launch, on_round=on_round)
+        self.adaptive_result = result
+        self.sample_counts = result["counts"]
+        self.stopped_on_noise = result["history"][-1][1] == 0
+        np.divide(result["sums"], result["counts"][..., None].astype(np.float32), out=image)
+        return image
 
     def _run_to_noise_target(self, image, scene, callback, quit_flag):
         """run() with a target: the sums and their squares stay on the device and continue there (render_moments_device), the
@@ -495,6 +621,8 @@ class PathTracer:
     def run(self, image, scene, callback=None, quit_flag=None):
         """image: float32 (H, W, 3) array that receives the running mean; scene: HipScene.  With target_noise the run may end
         before `spp` (stopped_on_noise, noise_history)."""
+        if self.adaptive:
+            return self._run_adaptive(image, scene, callback)
         if self.target_noise is not None:
             return self._run_to_noise_target(image, scene, callback, quit_flag)
         radiance_lookup = np.zeros((scene.height, scene.width, 3), dtype=np.float32)
@@ -555,6 +683,27 @@ def noise_from_job(job):
         raise PathedError("job: \"resume\" does not go with \"%s\": the state file holds no squares"
                           % ("target_noise" if target is not None else "stderr_image"))
     return (None if target is None else float(target)), int(min_spp), float(floor), write_stderr
+
+
+def adaptive_from_job(job):
+    """The job key "adaptive" (a bool, default false): render on only the pixels whose own error is above "target_noise"
+    (pathed_amd/host/job.h has the schedule).  It needs "target_noise" and one GPU, and goes neither with "resume" nor with the
+    AlbedoIntegrator; every refusal names the key."""
+    adaptive = job.get("adaptive", False)
+    if not isinstance(adaptive, bool):
+        raise PathedError("job: \"adaptive\" must be true or false")
+    if not adaptive:
+        return False
+    if job.get("target_noise") is None:
+        raise PathedError("job: \"adaptive\" needs \"target_noise\": the pixels above it are the ones rendered on")
+    if job.get("resume", False):
+        raise PathedError("job: \"adaptive\" does not go with \"resume\": the state file holds neither squares nor counts")
+    gpus = job.get("gpus", 1)
+    if (len(gpus) if isinstance(gpus, (list, tuple)) else gpus) != 1:
+        raise PathedError("job: \"adaptive\" renders on one GPU: \"gpus\" must be 1 (a pixel list is not sharded)")
+    if job.get("integrator") == "AlbedoIntegrator":
+        raise PathedError("job: \"adaptive\" does not go with the AlbedoIntegrator, which keeps no second moments")
+    return True
 
 
 def integrator_from_job(job, **kwargs):

@@ -61,6 +61,8 @@ def main(argv=None):
     # differently between the two runners (here the GPUs are the ranks of torch.distributed.run, and there is no auto.state)
     if job.get("resume", False):
         raise SystemExit("pathed_amd.run_job: \"resume\" is a key of the C++ host (pathed <job.json>); this runner keeps no auto.state")
+    if job.get("adaptive", False):
+        raise SystemExit("pathed_amd.run_job: \"adaptive\" is a key of the C++ host (pathed <job.json>); this runner keeps no second moments and no pixel lists")
     if "target_noise" in job or job.get("stderr_image", False):
         raise SystemExit("pathed_amd.run_job: \"target_noise\" and \"stderr_image\" are keys of the C++ host (pathed <job.json>); this runner keeps no second moments")
     if "gpus" in job:
