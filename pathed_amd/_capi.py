@@ -422,6 +422,11 @@ def load_host():
     if hasattr(lib, "pathed_host_run_job"):
         lib.pathed_host_run_job.argtypes = [C.c_char_p, C.c_char_p]
         lib.pathed_host_run_job.restype = C.c_int
+    if hasattr(lib, "pathed_host_job_seed"):
+        lib.pathed_host_job_seed.argtypes = [C.c_char_p, C.POINTER(C.c_uint64)]
+        lib.pathed_host_job_seed.restype = C.c_int
+        lib.pathed_host_json_round_trip.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
+        lib.pathed_host_json_round_trip.restype = C.c_int
     if hasattr(lib, "pathed_host_write_exr_float_rgba"):
         lib.pathed_host_write_exr_float_rgba.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         lib.pathed_host_write_exr_float_rgba.restype = C.c_int

@@ -174,6 +174,7 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
         Job job(jobPath);
         const std::vector<std::string> features = job.features();   // (a bad name stops the job before it touches the output directory)
         const Job::NoiseSettings noise = job.noise();                // (... and so does a bad noise key)
+        (void)job.seed();                                            // (... and a seed that cannot be read exactly)
         job.init();
 
         const int width = job.width();
@@ -340,6 +341,34 @@ extern "C" {
 int pathed_host_run_job(const char *jobPath, const char *assetRoot)
 {
     return runJob(jobPath ? jobPath : "job.json", assetRoot ? assetRoot : "");
+}
+
+// the seed a job file asks for, exactly as Job::seed() reads it (1 = refused or unreadable: pathed_host_last_error)
+int pathed_host_job_seed(const char *jobPath, unsigned long long *seed)
+{
+    try {
+        const pathed::Job job(jobPath ? jobPath : "job.json");
+        const unsigned long long value = job.seed();
+        if (seed) { *seed = value; }
+        return 0;
+    } catch (const std::exception &error) {
+        g_hostError = error.what();
+        return 1;
+    }
+}
+
+// Json::parse then Json::dump(0) of `text` into `out` (capacity bytes, NUL included): what report.json would hold
+int pathed_host_json_round_trip(const char *text, char *out, size_t capacity)
+{
+    try {
+        const std::string dumped = pathed::Json::parse(text ? text : "").dump(0);
+        if (!out || capacity < dumped.size() + 1) { g_hostError = "buffer too small"; return 2; }
+        std::memcpy(out, dumped.c_str(), dumped.size() + 1);
+        return 0;
+    } catch (const std::exception &error) {
+        g_hostError = error.what();
+        return 1;
+    }
 }
 
 int pathed_host_write_exr_float_rgba(const char *path, int width, int height, const float *rgba)

@@ -36,6 +36,14 @@ void Job::init()
     report << m_json.dump(4) << std::endl;
 }
 
+unsigned long long Job::seed() const
+{
+    const Json &seed = m_json["seed"];
+    if (!m_json.has("seed")) { return 1ull; }
+    if (!seed.isUnsigned()) { throw std::runtime_error("job: \"seed\" must be an integer in [0, 2^64), written in plain digits"); }
+    return (unsigned long long)seed.asUnsigned();
+}
+
 std::vector<int> Job::devices() const
 {
     const Json &gpus = m_json["gpus"];

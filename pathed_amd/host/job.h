@@ -2,7 +2,9 @@
 // Same keys as the reference (spp, integrator, scene, startBounce, lastBounce,
 // output_directory, output_name, showUI, force, width, height); job-file numbers are real
 // JSON numbers.  Optional extra keys with defaults, so reference job files run unchanged:
-//   "seed" (1), "gpu" (0), "asset_root" (directory paths resolve in),
+//   "seed" (1): any integer in [0, 2^64), read exactly as written -- digits only: a negative, fractional or over-range value,
+//               one written with an exponent and anything that is not a number are refused by name,
+//   "gpu" (0), "asset_root" (directory paths resolve in),
 //   "spp_per_launch" (1024): samples per render call.  A call drains its last paths before it returns (a few ms on a
 //               BVH scene: 64 spp per call cost 4 %, 256 and more < 1 %); checkpoints still bound a call,
 //   "bvh_builder" ("auto" | "sah" | "lbvh" | "ploc": include/pathed_hip.h PATHED_BVH_*; "auto" = the host SAH build on one
@@ -81,7 +83,8 @@ public:
     int lastBounce() const { return m_bounceController.lastBounce(); }
     BounceController bounceController() const { return m_bounceController; }
 
-    unsigned long long seed() const { return m_json["seed"].isNumber() ? (unsigned long long)m_json["seed"].asNumber() : 1ull; }
+    // "seed": any integer in [0, 2^64), read exactly as written (Json::asUnsigned); anything else throws an error that names the key
+    unsigned long long seed() const;
     int sppPerLaunch() const
     {
         if (!m_json["spp_per_launch"].isNumber()) { return 1024; }

@@ -117,6 +117,18 @@ private:
         j.m_type = Json::Type::Number;
         j.m_number = std::strtod(m_text.substr(start, m_pos - start).c_str(), nullptr);
         j.m_isInteger = isInteger;
+        if (isInteger && std::isdigit((unsigned char)m_text[start])) {
+            // digits only: the exact value, unless it passes 2^64 - 1
+            uint64_t value = 0;
+            bool fits = true;
+            for (size_t i = start; i < m_pos && fits; i++) {
+                const uint64_t digit = (uint64_t)(m_text[i] - '0');
+                if (value > (UINT64_MAX - digit) / 10u) { fits = false; }
+                else { value = value * 10u + digit; }
+            }
+            j.m_isUnsigned = fits;
+            j.m_unsigned = fits ? value : 0;
+        }
         return j;
     }
 
@@ -274,6 +286,12 @@ int Json::asInt() const
     return (int)asNumber();
 }
 
+uint64_t Json::asUnsigned() const
+{
+    if (!isUnsigned()) { throw JsonError("json: value is not a non-negative integer below 2^64"); }
+    return m_unsigned;
+}
+
 const std::string &Json::asString() const
 {
     if (m_type != Type::String) { throw JsonError("json: value is not a string"); }
@@ -346,7 +364,8 @@ void Json::dumpTo(std::string &out, int indent, int depth) const
     case Type::Bool: out += m_bool ? "true" : "false"; break;
     case Type::Number: {
         char buffer[64];
-        if (m_isInteger) { snprintf(buffer, sizeof buffer, "%lld", (long long)m_number); }
+        if (m_isUnsigned) { snprintf(buffer, sizeof buffer, "%llu", (unsigned long long)m_unsigned); }
+        else if (m_isInteger && std::fabs(m_number) < 9.2e18) { snprintf(buffer, sizeof buffer, "%lld", (long long)m_number); }
         else { snprintf(buffer, sizeof buffer, "%.17g", m_number); }
         out += buffer;
         break;

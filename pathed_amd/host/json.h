@@ -42,6 +42,10 @@ public:
     bool asBool() const;
     double asNumber() const;
     int asInt() const;
+    // a number written as a plain non-negative decimal integer <= 2^64 - 1 (digits only: no sign, point or exponent) also
+    // keeps its exact value; a double holds integers exactly up to 2^53 only
+    bool isUnsigned() const { return m_type == Type::Number && m_isUnsigned; }
+    uint64_t asUnsigned() const;
     const std::string &asString() const;
 
     std::string dump(int indent = 4) const;
@@ -58,6 +62,8 @@ private:
     bool m_bool = false;
     double m_number = 0.0;
     bool m_isInteger = false;
+    bool m_isUnsigned = false;
+    uint64_t m_unsigned = 0;
     std::string m_string;
     std::vector<Json> m_array;
     std::vector<std::pair<std::string, Json>> m_object;

@@ -24,6 +24,16 @@ def _check(lib, code, what):
         raise PathedError("%s failed (%d): %s" % (what, code, lib.pathed_hip_last_error().decode()))
 
 
+SEED_RANGE = "an integer in [0, 2^64)"
+
+
+def _seed(seed):
+    """The seed of a render call: an integer in [0, 2^64).  ctypes would wrap -1 to 2^64 - 1 and 2^64 to 0 without a word."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise PathedError("seed must be %s, not %r" % (SEED_RANGE, seed))
+    return int(seed)
+
+
 def measure_bandwidth(gib=2.0, repeats=10):
     """(read GB/s, copy GB/s) of a plain streaming kernel on the current device (pathed_hip_measure_bandwidth)."""
     lib = _capi.load_hip()
@@ -120,7 +130,7 @@ class HipScene:
             accum = np.zeros((self.height, self.width, 3), dtype=np.float32)
         assert accum.dtype == np.float32 and accum.flags["C_CONTIGUOUS"] and accum.size == 3 * self.width * self.height
         code = self._lib.pathed_hip_render(
-            self._handle, C.c_uint64(seed), spp_begin, spp_count, start_bounce, last_bounce,
+            self._handle, C.c_uint64(_seed(seed)), spp_begin, spp_count, start_bounce, last_bounce,
             accum.ctypes.data_as(C.POINTER(C.c_float)))
         _check(self._lib, code, "pathed_hip_render")
         return accum
@@ -128,7 +138,7 @@ class HipScene:
     def render_device(self, seed, spp_begin, spp_count, start_bounce, last_bounce, device_pointer, stream=0):
         """Same, into caller-owned device memory (e.g. tensor.data_ptr()) on `stream`."""
         code = self._lib.pathed_hip_render_device(
-            self._handle, C.c_uint64(seed), spp_begin, spp_count, start_bounce, last_bounce,
+            self._handle, C.c_uint64(_seed(seed)), spp_begin, spp_count, start_bounce, last_bounce,
             C.c_void_p(device_pointer), C.c_void_p(stream), 1)
         _check(self._lib, code, "pathed_hip_render_device")
 
@@ -148,7 +158,7 @@ class HipScene:
                 continue
             assert array.dtype == np.float32 and array.flags["C_CONTIGUOUS"] and array.size == channels * self.width * self.height
             pointers.append(array.ctypes.data_as(C.POINTER(C.c_float)))
-        code = self._lib.pathed_hip_render_features(self._handle, C.c_uint64(seed), spp_begin, spp_count, *pointers)
+        code = self._lib.pathed_hip_render_features(self._handle, C.c_uint64(_seed(seed)), spp_begin, spp_count, *pointers)
         _check(self._lib, code, "pathed_hip_render_features")
         return albedo, normal, depth, hits
 
@@ -157,7 +167,7 @@ class HipScene:
         the buffers' contents, in sample order."""
         buffers = _capi.PathedFeatureBuffers(albedo or None, normal or None, depth or None, hits or None)
         code = self._lib.pathed_hip_render_features_device(
-            self._handle, C.c_uint64(seed), spp_begin, spp_count, C.byref(buffers), C.c_void_p(stream))
+            self._handle, C.c_uint64(_seed(seed)), spp_begin, spp_count, C.byref(buffers), C.c_void_p(stream))
         _check(self._lib, code, "pathed_hip_render_features_device")
 
     def render_moments(self, seed, spp_begin, spp_count, start_bounce, last_bounce, accum=None, squares=None):
@@ -170,7 +180,7 @@ class HipScene:
         for array in (accum, squares):
             assert array.dtype == np.float32 and array.flags["C_CONTIGUOUS"] and array.size == 3 * self.width * self.height
         code = self._lib.pathed_hip_render_moments(
-            self._handle, C.c_uint64(seed), spp_begin, spp_count, start_bounce, last_bounce,
+            self._handle, C.c_uint64(_seed(seed)), spp_begin, spp_count, start_bounce, last_bounce,
             accum.ctypes.data_as(C.POINTER(C.c_float)), squares.ctypes.data_as(C.POINTER(C.c_float)))
         _check(self._lib, code, "pathed_hip_render_moments")
         return accum, squares
@@ -179,7 +189,7 @@ class HipScene:
         """Same, onto caller-owned device memory (e.g. tensor.data_ptr()) on `stream`: both sums CONTINUE from the buffers'
         contents in sample order, so any split of [0, n) into calls gives the same floats."""
         code = self._lib.pathed_hip_render_moments_device(
-            self._handle, C.c_uint64(seed), spp_begin, spp_count, start_bounce, last_bounce,
+            self._handle, C.c_uint64(_seed(seed)), spp_begin, spp_count, start_bounce, last_bounce,
             C.c_void_p(sum_pointer or None), C.c_void_p(squares_pointer or None), C.c_void_p(stream))
         _check(self._lib, code, "pathed_hip_render_moments_device")
 
@@ -281,7 +291,7 @@ class HipScene:
         memory) and of no other pixel (pathed_hip_render_pixels_device): their sums and square sums continue exactly as
         render_moments_device would continue them, their counts grow by spp_count."""
         code = self._lib.pathed_hip_render_pixels_device(
-            self._handle, C.c_uint64(seed), spp_begin, spp_count, start_bounce, last_bounce,
+            self._handle, C.c_uint64(_seed(seed)), spp_begin, spp_count, start_bounce, last_bounce,
             C.c_void_p(list_pointer or None), int(n_list), C.c_void_p(sum_pointer or None), C.c_void_p(squares_pointer or None),
             C.c_void_p(count_pointer or None), C.c_void_p(stream))
         _check(self._lib, code, "pathed_hip_render_pixels_device")
@@ -296,6 +306,7 @@ class HipScene:
         between rounds.  on_round(n, n_list, figure), if given, is called after every selection.
         Returns a dict: sums, squares (H, W, 3) float32, counts (H, W) uint32, rounds, samples_rendered, pixels_at_cap
         (pixels that hold `spp` samples), noise (the figure of the final state) and history [(n, n_list, mean_error)]."""
+        seed = _seed(seed)
         if not float(target_noise) > 0.0:
             raise PathedError("target_noise must be a number > 0")
         if int(min_spp) != min_spp or int(min_spp) < 2:
@@ -537,7 +548,7 @@ class PathTracer:
     def __init__(self, bounce_controller, spp=1, seed=1, spp_per_launch=1024, target_noise=None, min_spp=16, noise_floor=0.01, adaptive=False):
         self.bounce_controller = bounce_controller
         self.spp = spp
-        self.seed = seed
+        self.seed = _seed(seed)
         if int(spp_per_launch) < 1:
             raise PathedError("spp_per_launch must be >= 1")
         self.spp_per_launch = int(spp_per_launch)
@@ -657,6 +668,16 @@ def features_from_job(job):
         if name not in FEATURE_NAMES:
             raise PathedError("job: unknown feature \"%s\" (known: %s)" % (name, ", ".join(FEATURE_NAMES)))
     return [name for name in FEATURE_NAMES if name in wanted]
+
+
+def seed_from_job(job):
+    """The job key "seed" (default 1): any integer in [0, 2^64), read exactly as written.  A negative, fractional or over-range
+    value, one written with an exponent (json reads it as a float) and anything that is not a number are refused by name, in
+    the C++ host's words (pathed_amd/host/job.cpp)."""
+    value = job.get("seed", 1)
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 1 << 64:
+        raise PathedError("job: \"seed\" must be %s, written in plain digits" % SEED_RANGE)
+    return value
 
 
 def noise_from_job(job):

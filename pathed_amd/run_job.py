@@ -31,7 +31,7 @@ def main(argv=None):
     import torch.distributed as dist
 
     from . import _capi, parallel
-    from .integrator import INTEGRATOR_NAMES, BounceController, HipScene, PathedError, features_from_job
+    from .integrator import INTEGRATOR_NAMES, BounceController, HipScene, PathedError, features_from_job, seed_from_job
     from .scene import LoadedScene
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -48,12 +48,12 @@ def main(argv=None):
         job = json.load(handle)
     width, height = job["width"], job["height"]
     spp = job["spp"] if job["spp"] > 0 else 9999999
-    seed = int(job.get("seed", 1))
     bounces = BounceController(job["startBounce"], job["lastBounce"])
     if job["integrator"] not in INTEGRATOR_NAMES:
         raise SystemExit("Unimplemented")  # the reference throws "Unimplemented" (src/job.cpp:96)
     try:
         features = features_from_job(job)   # "features": first-hit feature images beside every auto*.exr
+        seed = seed_from_job(job)           # "seed": exactly as written, or refused by name
     except PathedError as error:
         raise SystemExit("pathed_amd.run_job: %s" % error)
     out_dir = job["output_directory"] + "/"

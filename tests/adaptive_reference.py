@@ -35,15 +35,19 @@ def select(rgb_sum, rgb_sq_sum, counts, floor, threshold):
 
 def mean_error(e):
     """the device's mean: per block of 256 pixels the errors added in double in pixel order, the blocks' sums added in
-    block order, over the number of pixels (Python floats are IEEE doubles: the same additions)"""
-    e = np.asarray(e, dtype=F).reshape(-1)
-    total = 0.0
-    for first in range(0, e.size, BLOCK):
-        partial = 0.0
-        for value in e[first:first + BLOCK]:
-            partial += float(value)
-        total += partial
-    return total / e.size
+    block order, over the number of pixels.  np.cumsum adds one element after the other, each partial sum rounded to a
+    double: the same additions in the same order as a loop over Python floats, for all full blocks at once (row by row of
+    a (blocks, 256) array), then for the ragged last block, then over the blocks' sums."""
+    e = np.asarray(e, dtype=F).reshape(-1).astype(np.float64)
+    full = e.size // BLOCK
+    partials = []
+    if full:
+        partials.append(np.cumsum(e[:full * BLOCK].reshape(full, BLOCK), axis=1)[:, -1])
+    if e.size > full * BLOCK:
+        partials.append(np.cumsum(e[full * BLOCK:])[-1:])
+    partials = np.concatenate(partials)
+    # (0.0 + x is x: starting the chain at the first element is starting it at zero)
+    return float(np.cumsum(partials)[-1]) / e.size
 
 
 def replay(uniform, min_spp, cap, target, floor):

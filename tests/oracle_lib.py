@@ -113,6 +113,9 @@ class OracleScene:
         return accum, dict(zip(names, list(stats)))
 
     def sample_pixel(self, seed, row, col, sample, start_bounce, last_bounce):
+        """One PathTracer sample of one pixel, for spot checks of images too large to render here: `row` is the image row
+        index of `render`'s array (and of the product's buffers: pixel index = row * width + col), so the result is
+        render(..., sample, 1, ...)[0][row, col] bit for bit.  (The path tracer only: set_integrator does not reach it.)"""
         rgb = np.zeros(3, dtype=np.float32)
         self.lib.oracle_sample_pixel(self.handle, seed, row, col, sample, start_bounce, last_bounce, _fptr(rgb))
         return rgb

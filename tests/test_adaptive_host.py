@@ -108,6 +108,17 @@ def test_mean_by_hand():
     e[256] = 1.0
     assert adaptive_reference.mean_error(e) == (1.0 + 2.0 ** -22) / 257.0
     assert adaptive_reference.mean_error(np.array([0.5], dtype=F)) == 0.5
+    # the same additions in the same order as the loop it restates, where the order matters: values over 12 decades
+    rng = np.random.default_rng(3)
+    for pixels in (1, 255, 256, 257, 1000, 8100 * 256 // 100 + 7):
+        e = (rng.uniform(0.0, 1.0, pixels) * 10.0 ** rng.integers(-9, 3, pixels)).astype(F)
+        total = 0.0
+        for first in range(0, pixels, 256):
+            partial = 0.0
+            for value in e[first:first + 256]:
+                partial += float(value)
+            total += partial
+        assert adaptive_reference.mean_error(e) == total / pixels, pixels
 
 
 def test_replay_by_hand():

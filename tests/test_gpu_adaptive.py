@@ -239,9 +239,10 @@ def _synthetic(pixels, rng, counts):
     return (n * m).astype(F), (n * m * m * (1.0 + r * r)).astype(F)
 
 
-@pytest.mark.parametrize("width, height", [(1, 1), (17, 15), (16, 16), (257, 1), (40, 25)])
+@pytest.mark.parametrize("width, height", [(1, 1), (17, 15), (16, 16), (257, 1), (40, 25), (1920, 1080)])
 def test_selection_against_the_numpy_restatement(width, height):
-    """1, 255, 256, 257 and 1 000 pixels: both sides of the 256-pixel block.  Mixed counts (0, 1, 2, 7, 4 096); thresholds that
+    """1, 255, 256, 257 and 1 000 pixels: both sides of the 256-pixel block; 1920 x 1080 = 2 073 600 pixels, 8 100 blocks: the
+    size jobs run it at (the list is built from the host's block offsets; the other sizes have at most 4).  Mixed counts (0, 1, 2, 7, 4 096); thresholds that
     select none but the pixels without a spread, all, and a scattered half.  Errors, list and length exact; the mean to the
     last digit of the double.  With one count everywhere: pathed_hip_noise_estimate_device's results bit for bit."""
     from pathed_amd.integrator import HipScene

@@ -254,25 +254,36 @@ def _equal(a, b):
 
 # -------------------------------------------------------------------------------------------------------------- tests
 
-@pytest.mark.parametrize("name", sorted(SCENES))
-def test_feature_sums_match_the_oracle_derived_expectation(name):
+# beside the values every other test here uses: a seed whose high word matters and eight samples across 2^24, the first
+# sample index a float no longer holds (ids of the first rows stay the scene names)
+LATE_SEED, LATE_BEGIN = (1 << 63) + 5, (1 << 24) - 3
+FEATURE_CASES = [(name, SEED, 0) for name in sorted(SCENES)] + [(name, LATE_SEED, LATE_BEGIN) for name in sorted(SCENES)]
+
+
+@pytest.mark.parametrize("name, seed, begin", FEATURE_CASES, ids=[name if begin == 0 else name + "-seed-2^63+5-from-sample-2^24-3" for name, _, begin in FEATURE_CASES])
+def test_feature_sums_match_the_oracle_derived_expectation(name, seed, begin):
     from pathed_amd.integrator import HipScene
     built, desc = SCENES[name]()
     gpu = HipScene(desc, device=0)
-    images = gpu.render_features(SEED, 0, SPP)
-    expected = Expectation(built, desc).features()
+    images = gpu.render_features(seed, begin, SPP)
+    expected = Expectation(built, desc, seed=seed, spp_begin=begin).features()
     assert expected["hits"].max() == SPP and (name in ("materials",) or expected["hits"].min() == 0)   # hits and misses both occur
     _assert_features(images, expected)
     stats = gpu.stats()
     assert stats["path_kernel"] == 8 and stats["camera_samples"] == WIDTH * HEIGHT * SPP and stats["closest_rays"] == WIDTH * HEIGHT * SPP
+    if begin:
+        # the inputs can tell: the low word alone, or the sample index cut to a float's 24 bits, jitter the camera otherwise
+        import oracle_lib
+        jitter = lambda s, k: [oracle_lib.rng(s, pixel, k, d) for pixel in (0, 1, WIDTH * HEIGHT - 1) for d in (0, 1)]
+        assert jitter(seed, begin + 4) != jitter(seed & 0xFFFFFFFF, begin + 4) and jitter(seed, begin + 4) != jitter(seed, begin + 3)   # (2^24 + 1 rounds to 2^24)
 
     # 3 + 5 samples in two calls are the 8 of one call, bit for bit
-    split = gpu.render_features(SEED, 0, 3)
-    gpu.render_features(SEED, 3, 5, *split)
+    split = gpu.render_features(seed, begin, 3)
+    gpu.render_features(seed, begin + 3, 5, *split)
     assert _equal(split, images)
 
     # a subset of the buffers: the same floats, and the others keep their bits
-    albedo, normal, depth, hits = gpu.render_features(SEED, 0, SPP, normal=np.zeros((HEIGHT, WIDTH, 3), dtype=F), hits=np.zeros((HEIGHT, WIDTH), dtype=F))
+    albedo, normal, depth, hits = gpu.render_features(seed, begin, SPP, normal=np.zeros((HEIGHT, WIDTH, 3), dtype=F), hits=np.zeros((HEIGHT, WIDTH), dtype=F))
     assert albedo is None and depth is None and np.array_equal(hits, images[3]) and np.array_equal(normal, images[1])
 
 

@@ -120,6 +120,55 @@ def test_both_launchers_render_every_sample_of_a_count_that_is_no_power_of_two(t
     assert np.allclose(final["cpp"], half, rtol=2e-3, atol=2e-3)
 
 
+def test_both_launchers_render_the_seed_as_written(tmp_path):
+    """"seed": 9007199254740993 = 2^53 + 1, which no double holds: a host that reads the seed through one renders 2^53.  Both
+    launchers' images are the library's render with exactly that seed and not its render with 2^53; the C++ host's state
+    file holds the library's sums bit for bit and its uint64 seed: a resume with 2^53 + 1 is accepted, one with 2^53 refused."""
+    import sys
+    from pathed_amd import _capi
+    from pathed_amd.integrator import HipScene
+    from pathed_amd.scene import LoadedScene
+
+    seed, spp = 9007199254740993, 4
+    job = json.load(open(os.path.join(_capi.REPO_ROOT, "jobs", "cornell-c1.json")))
+    job.update(width=32, height=32, spp=spp, seed=seed)
+    scene = LoadedScene(job["scene"], 32, 32)
+    gpu = HipScene(scene.desc, device=0)
+    as_written = gpu.render(seed, 0, spp, job["startBounce"], job["lastBounce"])
+    through_a_double = gpu.render(int(float(seed)), 0, spp, job["startBounce"], job["lastBounce"])
+    assert int(float(seed)) == 2 ** 53 and as_written.any()
+    half = lambda sums: (sums / np.float32(spp))[::-1].astype(np.float16).astype(np.float32)   # Image::set flips: EXR row 0 is the top scanline
+    apart = np.linalg.norm(half(as_written) - half(through_a_double)) / np.linalg.norm(half(as_written))
+    assert apart > 0.1, apart                                       # the two seeds are other images altogether
+    for name in ("cpp", "py"):
+        out_dir = str(tmp_path / name)
+        job["output_directory"] = out_dir
+        job_path = str(tmp_path / (name + ".json"))
+        json.dump(job, open(job_path, "w"))
+        assert "\"seed\": 9007199254740993" in open(job_path).read()
+        command = ([os.path.join(_capi.REPO_ROOT, "pathed_amd", "bin", "pathed")] if name == "cpp" else [sys.executable, "-m", "pathed_amd.run_job"]) + [job_path, _capi.REPO_ROOT]
+        result = subprocess.run(command, capture_output=True, text=True, cwd=_capi.REPO_ROOT)
+        assert result.returncode == 0, result.stdout + result.stderr
+        assert json.load(open(os.path.join(out_dir, "report.json")))["seed"] == seed, name
+        image = _read_exr(os.path.join(out_dir, "auto.exr"))[..., :3]
+        rel = np.linalg.norm(image - half(as_written)) / np.linalg.norm(half(as_written))
+        other = np.linalg.norm(image - half(through_a_double)) / np.linalg.norm(half(as_written))
+        print("%s: relL2 to the render with the seed as written %.3g, to the render with 2^53 %.3g" % (name, rel, other))
+        assert np.allclose(image, half(as_written), rtol=2e-3, atol=2e-3), (name, rel)
+        assert other > 0.1, (name, other)
+    # the C++ host's sums are the library's, bit for bit
+    done, sums = _read_state(os.path.join(str(tmp_path / "cpp"), "auto.state"))
+    assert done == spp and np.array_equal(sums, as_written)
+    blob = open(os.path.join(str(tmp_path / "cpp"), "auto.state"), "rb").read(48)
+    assert int(np.frombuffer(blob, dtype="<u8", count=1, offset=32)[0]) == seed
+    _, result = _run_job(tmp_path, "cpp", dict(job, spp=2 * spp, resume=True, seed=int(float(seed))))
+    assert result.returncode != 0 and "another seed" in (result.stdout + result.stderr)
+    _, result = _run_job(tmp_path, "cpp", dict(job, spp=2 * spp, resume=True))
+    assert result.returncode == 0 and "resuming at sample %d/%d" % (spp, 2 * spp) in result.stdout, result.stdout + result.stderr
+    done, sums = _read_state(os.path.join(str(tmp_path / "cpp"), "auto.state"))
+    assert done == 2 * spp and np.array_equal(sums, gpu.render(seed, 0, 2 * spp, job["startBounce"], job["lastBounce"]))
+
+
 def test_bvh_builder_job_key_changes_the_build_not_the_image(tmp_path):
     """job.json "bvh_builder": the on-GPU PLOC / LBVH builds give the checkpoint the host SAH build gives,
     byte for byte (hits do not depend on the tree); an unknown name is an error."""

@@ -185,12 +185,14 @@ def test_summation_order_matches_the_oracle_bit_for_bit_on_transcendental_free_p
     built.quad([(-3, 3, -3), (3, 3, -3), (3, 3, 3), (-3, 3, 3)], light)  # faces down
     desc = built.finish()
     gpu, cpu = HipScene(desc, device=0), oracle_lib.OracleScene(desc)
-    for chunk in (1, 4):
-        gpu.set_samples_per_unit(chunk)
-        image = gpu.render(5, 0, 8, 0, 6)
-        expected, _ = cpu.render(40, 40, 5, 0, 8, 0, 6, chunk=chunk)
-        assert image.any()
-        assert np.array_equal(image.view(np.int32), expected.view(np.int32)), chunk
+    # ... and seed 2^64 - 1 with samples 2^31 - 9 .. 2^31 - 2: the last unit ends on the last index a call may name
+    for seed, begin in ((5, 0), ((1 << 64) - 1, (1 << 31) - 9)):
+        for chunk in (1, 4):
+            gpu.set_samples_per_unit(chunk)
+            image = gpu.render(seed, begin, 8, 0, 6)
+            expected, _ = cpu.render(40, 40, seed, begin, 8, 0, 6, chunk=chunk)
+            assert image.any() and gpu.stats()["dropped_samples"] == 0
+            assert np.array_equal(image.view(np.int32), expected.view(np.int32)), (seed, begin, chunk)
 
 
 def test_stats_mode_counts_match_the_oracle(libs):
