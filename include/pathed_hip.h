@@ -42,7 +42,8 @@ extern "C" {
  * pathed_hip_accum_add / pathed_hip_accum_copy_peer (multi-GPU fan-in of the radiance sums),
  * PathedFeatureBuffers / pathed_hip_render_features[_device] (first-hit feature images), PATHED_INTEGRATOR_ALBEDO,
  * pathed_hip_render_moments[_device] / PathedNoise / pathed_hip_noise_estimate_device (per-pixel second moments and the noise figure),
- * pathed_hip_select_pixels_device / pathed_hip_render_pixels_device (adaptive sampling over pixel lists). */
+ * pathed_hip_select_pixels_device / pathed_hip_render_pixels_device (adaptive sampling over pixel lists),
+ * PathedInstanceDesc / pathed_hip_scene_create_instanced (instanced geometry). */
 
 /* error codes */
 #define PATHED_OK            0
@@ -224,7 +225,8 @@ typedef struct PathedStats {
                                       7 hybrid path kernel (scenes of 65 .. 4096 triangles, the last render call),
                                       8 feature kernel (the last call was pathed_hip_render_features[_device], or a render call
                                         of PATHED_INTEGRATOR_ALBEDO; its samples count in camera_samples and closest_rays),
-                                      9 multiple-scattering volume kernel (PATHED_INTEGRATOR_BASIC_VOLUME) */
+                                      9 multiple-scattering volume kernel (PATHED_INTEGRATOR_BASIC_VOLUME),
+                                      10 wavefront of an instanced scene (k_trace_instanced + k_shade_instanced) */
     uint32_t reserved0;
     uint64_t local_closest_rays;   /* closest-hit queries the shade kernel resolved itself (rays that cannot meet anything but the
                                       scene's few large triangles, PathedSceneOptions.local_rays) -- stats mode; NOT in closest_rays */
@@ -338,6 +340,55 @@ typedef struct PathedSceneOptions {
 } PathedSceneOptions;
 int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOptions *options, PathedScene **out);
 int pathed_hip_scene_device(const PathedScene *scene);   /* the HIP device the scene lives on, or a negative error */
+
+/* Instanced geometry -- the reference's "instance" / "instanced" models (src/scene_parser.cpp:231-249, 279-285, 449-492, which
+ * hands them to Embree as RTC_GEOMETRY_TYPE_INSTANCE): a PROTOTYPE is a run of mesh geoms of the description that is not
+ * placed in the world, an INSTANCE is one prototype under an affine transform.  One level: a host resolves nesting.
+ *
+ * Layout of the description: the mesh geoms cover the triangles in order without gaps; the world's geoms come first
+ * (triangles [0, T0)), then the prototypes' geoms, prototype after prototype, to the end of the geom array.  A prototype's
+ * vertices are in ITS space.
+ *
+ * Primitive ids are VIRTUAL: world triangles keep [0, T0); instance k owns [base_k, base_k + T_prototype(k)) in instance
+ * order, base_0 = T0.  These are the ids of the FLATTENED scene -- every placement written out as world triangles in that
+ * order by the flatten routine below -- so the acceptance rule "smaller t, then smaller primitive id" is the flattened
+ * scene's, pathed_hip_trace reports them, and every shading quantity of a hit equals what the flattened scene's records
+ * give for the same (t, u, v, prim).  The total must stay below 2^31 (PATHED_E_INVALID otherwise).
+ *
+ * The flatten routine (fp32, one rounding per operation, no fused multiply-add), with m = transform:
+ *   point   x' = ((m[0] x + m[1] y) + m[2] z) + m[3]      y', z' from m[4..7], m[8..11]
+ *   normal  x' = ((i[0] x + i[4] y) + i[8] z)             y' from i[1], i[5], i[9]; z' from i[2], i[6], i[10]   (not renormalised)
+ * where i is the inverse of m, formed in double from the floats of m by cofactors -- c00 = e k - f h, c01 = c h - b k,
+ * c02 = b f - c e, c10 = f g - d k, c11 = a k - c g, c12 = c d - a f, c20 = d h - e g, c21 = b g - a h, c22 = a e - b d for
+ * m's 3 x 3 part (a b c / d e f / g h k), det = (a c00 + b c10) + c c20, i3x3 = c / det, translation -((r0 tx + r1 ty) + r2 tz)
+ * per row -- and rounded once to float.  pathed_amd.flatten_instances is this routine in numpy.
+ *
+ * Memory: per instance one 112-byte record; nodes, leaf triangles and shading records exist once per prototype.
+ * Such a scene renders on the wavefront with k_trace_instanced / k_shade_instanced whatever its size (PathedStats.path_kernel
+ * 10); render, render_moments, select_pixels and render_pixels work as on every scene.
+ *
+ * PATHED_E_UNSUPPORTED, by name and before anything is allocated or launched: sphere primitives; media and passthrough
+ * (container) materials; an emissive material inside a prototype (a host bakes such faces into world triangles, one copy per
+ * placement); PathedSceneOptions.refittable; the device BVH builders; a shade_kernel other than 0 / 1.  On the created scene:
+ * pathed_hip_scene_refit, every integrator but the path tracer, pathed_hip_render_features[_device],
+ * pathed_hip_debug_small_candidates and pathed_hip_debug_light_records. */
+typedef struct PathedPrototype {
+    int32_t first_geom;      /* index into PathedSceneDesc.geoms */
+    int32_t n_geoms;         /* >= 1, mesh geoms with at least one triangle together */
+} PathedPrototype;
+typedef struct PathedInstance {
+    int32_t prototype;       /* index into PathedInstanceDesc.prototypes */
+    float transform[12];     /* row-major 3 x 4, prototype space -> world; invertible */
+} PathedInstance;
+typedef struct PathedInstanceDesc {
+    uint32_t struct_size;    /* sizeof(PathedInstanceDesc) */
+    uint32_t n_prototypes;
+    const PathedPrototype *prototypes;
+    uint32_t n_instances;
+    const PathedInstance *instances;
+} PathedInstanceDesc;
+int pathed_hip_scene_create_instanced(const PathedSceneDesc *desc, const PathedSceneOptions *options,
+                                      const PathedInstanceDesc *instances, PathedScene **out);
 /* Another view of the same scene: replaces the camera (reference Camera, src/camera.cpp:13-30) without rebuilding or
  * re-uploading anything; the resolution must stay (the caller's radiance sums are per pixel). */
 int pathed_hip_scene_set_camera(PathedScene *scene, const PathedCamera *camera);

@@ -6,5 +6,6 @@ Python here is plumbing over two native libraries:
 """
 from . import _capi  # noqa: F401
 from .scene import LoadedScene  # noqa: F401
+from .instances import InstanceSet, flatten_instances  # noqa: F401
 
 __version__ = "0.1.0"

@@ -185,6 +185,24 @@ class PathedSceneOptions(C.Structure):
     ]
 
 
+class PathedPrototype(C.Structure):
+    _fields_ = [("first_geom", C.c_int32), ("n_geoms", C.c_int32)]
+
+
+class PathedInstance(C.Structure):
+    _fields_ = [("prototype", C.c_int32), ("transform", C.c_float * 12)]
+
+
+class PathedInstanceDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_prototypes", C.c_uint32),
+        ("prototypes", C.POINTER(PathedPrototype)),
+        ("n_instances", C.c_uint32),
+        ("instances", C.POINTER(PathedInstance)),
+    ]
+
+
 class PathedFeatureBuffers(C.Structure):
     _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p)]
 
@@ -217,6 +235,7 @@ HIP_SYMBOLS = [
     "pathed_hip_init",
     "pathed_hip_scene_create",
     "pathed_hip_scene_create_ex",
+    "pathed_hip_scene_create_instanced",
     "pathed_hip_scene_device",
     "pathed_hip_scene_set_camera",
     "pathed_hip_scene_set_grid_medium",
@@ -297,6 +316,9 @@ def load_hip():
     lib.pathed_hip_scene_create.restype = C.c_int
     lib.pathed_hip_scene_create_ex.argtypes = [C.POINTER(PathedSceneDesc), C.POINTER(PathedSceneOptions), C.POINTER(vp)]
     lib.pathed_hip_scene_create_ex.restype = C.c_int
+    if hasattr(lib, "pathed_hip_scene_create_instanced"):   # (PATHED_HIP_LIB may name an older build of the same ABI)
+        lib.pathed_hip_scene_create_instanced.argtypes = [C.POINTER(PathedSceneDesc), C.POINTER(PathedSceneOptions), C.POINTER(PathedInstanceDesc), C.POINTER(vp)]
+        lib.pathed_hip_scene_create_instanced.restype = C.c_int
     lib.pathed_hip_scene_device.argtypes = [vp]
     lib.pathed_hip_scene_device.restype = C.c_int
     lib.pathed_hip_scene_set_camera.argtypes = [vp, C.POINTER(PathedCamera)]
@@ -419,6 +441,9 @@ def load_host():
     lib.pathed_host_scene_grid.restype = C.POINTER(PathedGridMedium)
     lib.pathed_host_last_error.argtypes = []
     lib.pathed_host_last_error.restype = C.c_char_p
+    if hasattr(lib, "pathed_host_scene_instances"):
+        lib.pathed_host_scene_instances.argtypes = [C.c_void_p]
+        lib.pathed_host_scene_instances.restype = C.POINTER(PathedInstanceDesc)
     if hasattr(lib, "pathed_host_run_job"):
         lib.pathed_host_run_job.argtypes = [C.c_char_p, C.c_char_p]
         lib.pathed_host_run_job.restype = C.c_int

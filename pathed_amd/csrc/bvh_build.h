@@ -228,8 +228,11 @@ inline void putInt(float *slot, int value) { std::memcpy(slot, &value, 4); }
 // positions: 3 floats per vertex; indices: 3 per triangle; spheres: (centre.xyz, radius) each, may be null.
 // Sphere s becomes the leaf reference -(((s + 1) << 3) | 0) - 1: count 0 marks it, trace.h tests it.
 // `buildThreads` > 0 fixes the number of host threads (PathedSceneOptions.build_threads); the tree does not depend on it
+// `sphereBoxes`: the entries of `spheres` are BOXES, (lo.xyz, hi.xyz) each, taken as they are -- the top tree of an instanced
+// scene hands its placements in this way and rewrites their one-primitive leaves into instance leaves (trace.h)
 inline FlatBvh buildBvh(const float *positions, const uint32_t *indices, uint32_t triangleCount,
-                        const float *spheres = nullptr, uint32_t sphereCount = 0, int buildThreads = 0, uint32_t maxLeaf = 0)
+                        const float *spheres = nullptr, uint32_t sphereCount = 0, int buildThreads = 0, uint32_t maxLeaf = 0,
+                        bool sphereBoxes = false)
 {
     using namespace bvh_detail;
     FlatBvh out;
@@ -241,6 +244,14 @@ inline FlatBvh buildBvh(const float *positions, const uint32_t *indices, uint32_
         Prim &p = prims[triangleCount + s];
         p.index = triangleCount + s;
         p.sphere = true;
+        if (sphereBoxes) {
+            for (int a = 0; a < 3; a++) {
+                p.bmin[a] = spheres[6 * s + a];
+                p.bmax[a] = spheres[6 * s + 3 + a];
+                p.centroid[a] = 0.5f * (p.bmin[a] + p.bmax[a]);
+            }
+            continue;
+        }
         const float radius = std::fabs(spheres[4 * s + 3]);
         for (int a = 0; a < 3; a++) {
             // a hit point computed in fp32 may sit an ulp outside centre +- radius: pad by a relative 1e-5 as well

@@ -1393,14 +1393,132 @@ __global__ __launch_bounds__(kBlock) void k_trace_rays(
     }
 }
 
+// ---- instanced scenes (trace.h: "Instances"): the wavefront's trace stage over the two-level tree.  A plain grid-stride kernel
+// in the shape of k_trace_small -- the pool is [closest ray of every live slot | dense shadow list], one ray per lane, hit[] and
+// pend[] written the same way -- with the per-lane stack in LDS rows [row][thread] and the HBM overflow column.  No refill,
+// no parking, no suspension: the first version, not the tuned one.
+template <int STACK, bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_trace_instanced(RenderParams p, DInstanceSet instances)
+{
+    extern __shared__ float4 ldsRaw[];
+    LaneStack stack;
+    stack.lds = reinterpret_cast<int *>(ldsRaw) + threadIdx.x;
+    stack.overflowStride = (size_t)gridDim.x * kBlock;
+    stack.overflow = p.stackOverflow + ((size_t)blockIdx.x * kBlock + threadIdx.x);
+
+    TraceGeometry geometry;
+    geometry.nodes = p.scene.nodes;
+    geometry.tris = p.scene.leafTris;
+    geometry.nNodes = p.scene.nNodes;
+    geometry.nTris = p.scene.nTris;
+    geometry.spheres = nullptr;
+    geometry.nSpheres = 0;
+
+    const int lane = threadIdx.x & 63;
+    const unsigned int waveId = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const unsigned int waveCount = gridDim.x * kWavesPerBlock;
+    const unsigned int slotBatches = (unsigned int)p.nSlots / 64u;
+    const unsigned int shadowCount = p.counters[kCtrShadowCount + (p.parity ^ 1) * kCursorStride];
+    const unsigned int totalBatches = slotBatches + (shadowCount + 63u) / 64u;
+
+    TraceCounters counters;
+    counters.boxes = 0;
+    counters.tris = 0;
+    unsigned int closestRays = 0, shadowRays = 0;
+
+    for (unsigned int batch = waveId; batch < totalBatches; batch += waveCount) {
+        LaneRay ray;
+        const float4 *worldO = nullptr, *worldD = nullptr;
+        unsigned int target = 0;
+        if (batch < slotBatches) {
+            const unsigned int slot = batch * 64u + lane;
+            const float4 rd = p.state.rayD[slot];
+            if (!(floatAsInt(rd.w) & kStDone)) {
+                const float4 ro = p.state.rayO[slot];
+                laneRayInit(ray, v3(ro.x, ro.y, ro.z), v3(rd.x, rd.y, rd.z), PATHED_TNEAR, PATHED_TFAR, false);
+                worldO = p.state.rayO + slot;
+                worldD = p.state.rayD + slot;
+                target = slot;
+            }
+        } else {
+            const unsigned int entry = (batch - slotBatches) * 64u + lane;
+            if (entry < shadowCount) {
+                const float4 so = p.state.shO[entry];
+                const float4 sd = p.state.shD[entry];
+                laneRayInit(ray, v3(so.x, so.y, so.z), v3(sd.x, sd.y, sd.z), PATHED_TNEAR, so.w, true);
+                worldO = p.state.shO + entry;
+                worldD = p.state.shD + entry;
+                target = (unsigned int)floatAsInt(sd.w);
+            }
+        }
+        if (worldO == nullptr) { continue; }
+        traverseInstanced<COUNT, STACK, kBlock>(geometry, instances, stack, p.maxStack, worldO, worldD, ray, &counters);
+        if (ray.anyHit) {
+            if (ray.occluded) { p.state.pend[target] = make_float4(0.f, 0.f, 0.f, 0.f); }
+            if (COUNT) { shadowRays++; }
+        } else {
+            p.state.hit[target] = make_float4(ray.best, ray.bestU, ray.bestV, intAsFloat(ray.bestPrim));
+            if (COUNT) { closestRays++; }
+        }
+    }
+
+    if (COUNT) {
+        atomicAdd(&p.stats[kStatBoxes], (unsigned long long)counters.boxes);
+        atomicAdd(&p.stats[kStatTris], (unsigned long long)counters.tris);
+        atomicAdd(&p.stats[kStatClosest], (unsigned long long)closestRays);
+        atomicAdd(&p.stats[kStatShadow], (unsigned long long)shadowRays);
+    }
+}
+
+// ... and the test hook's kernel behind pathed_hip_trace on such a scene: k_trace_rays over the two-level tree
+template <int STACK>
+__global__ __launch_bounds__(kBlock) void k_trace_rays_instanced(
+    DScene scene, DInstanceSet instances, const float4 *rays, int n, int anyHit, float4 *hitsOut, int *occludedOut,
+    int *stackOverflow, int maxStack
+) {
+    extern __shared__ float4 ldsRaw[];
+    LaneStack stack;
+    stack.lds = reinterpret_cast<int *>(ldsRaw) + threadIdx.x;
+    stack.overflowStride = (size_t)gridDim.x * kBlock;
+    stack.overflow = stackOverflow + ((size_t)blockIdx.x * kBlock + threadIdx.x);
+
+    TraceGeometry geometry;
+    geometry.nodes = scene.nodes;
+    geometry.tris = scene.leafTris;
+    geometry.nNodes = scene.nNodes;
+    geometry.nTris = scene.nTris;
+    geometry.spheres = nullptr;
+    geometry.nSpheres = 0;
+
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) { return; }
+    const float4 ro = rays[2 * i + 0];
+    const float4 rd = rays[2 * i + 1];
+    TraceCounters counters;
+    LaneRay ray;
+    laneRayInit(ray, v3(ro.x, ro.y, ro.z), v3(rd.x, rd.y, rd.z), ro.w, rd.w, anyHit != 0);
+    traverseInstanced<false, STACK, kBlock>(geometry, instances, stack, maxStack, rays + 2 * i, rays + 2 * i + 1, ray, &counters);
+    if (anyHit) {
+        occludedOut[i] = ray.occluded ? 1 : 0;
+    } else if (ray.bestPrim >= 0) {
+        hitsOut[i] = make_float4(ray.best, ray.bestU, ray.bestV, intAsFloat(ray.bestPrim));
+    } else {
+        hitsOut[i] = make_float4(0.f, 0.f, 0.f, intAsFloat(-1));
+    }
+}
+
 // ------------------------------------------------------------------------- shade
 
 // Ng = (v1-v0) x (v2-v0), normalised: ONE definition, used where a hit is shaded and where the 16-byte records are built
 __device__ inline V3 triangleNormal(V3 p0, V3 p1, V3 p2) { return normalized(xcross(p1 - p0, p2 - p0)); }
 
 // Scene::testIntersect's record construction, reference src/scene.cpp:121-218
-template <typename TRAITS = TraitsAll>
-__device__ inline Isect makeIsect(const DScene &scene, V3 o, V3 d, float4 h)
+// INSTANCED (k_shade_instanced): a primitive id at or above instances->worldTris is a VIRTUAL id (trace.h: "Instances") -- the
+// prototype triangle's record is flattened here, corners by flattenPoint and vertex normals by flattenNormal, the host's own
+// routine in the host's operation order, and then goes through the statements of the general branch: every quantity is what
+// the flattened scene's record gives for the same (t, u, v, prim)
+template <typename TRAITS = TraitsAll, bool INSTANCED = false>
+__device__ inline Isect makeIsect(const DScene &scene, V3 o, V3 d, float4 h, const DInstanceSet *instances = nullptr)
 {
     const float t = h.x, u = h.y, v = h.z;
 #if defined(PATHED_ABLATE) && PATHED_ABLATE == 1
@@ -1414,7 +1532,33 @@ __device__ inline Isect makeIsect(const DScene &scene, V3 o, V3 d, float4 h)
     float uvU = 0.f, uvV = 0.f;
     int material;
 
-    if (!TRAITS::spheres || prim < scene.nTris) {
+    if (INSTANCED && prim >= instances->worldTris) {
+        // the instance whose id range holds prim: the last base that is not above it
+        int low = 0, high = instances->nInstances - 1;
+        while (low < high) {
+            const int middle = (low + high + 1) >> 1;
+            if (instances->bases[middle] <= prim) { low = middle; } else { high = middle - 1; }
+        }
+        const float4 *record = instances->records + (size_t)kInstanceQuads * low;
+        const float4 m0 = record[0], m1 = record[1], m2 = record[2], i0 = record[3], i1 = record[4], i2 = record[5], ids = record[6];
+        const float m[12] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w };
+        const float inverse[12] = { i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w, i2.x, i2.y, i2.z, i2.w };
+        const float4 *q = scene.triShade + (size_t)kTriShadeQuads * (size_t)(floatAsInt(ids.w) + (prim - floatAsInt(ids.x)));
+        const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6];
+        const V3 p0 = flattenPoint(m, v3(q0.x, q0.y, q0.z)), p1 = flattenPoint(m, v3(q1.x, q1.y, q1.z)), p2 = flattenPoint(m, v3(q2.x, q2.y, q2.z));
+        const V3 n0 = flattenNormal(inverse, v3(q3.x, q3.y, q3.z)), n1 = flattenNormal(inverse, v3(q4.x, q4.y, q4.z)), n2 = flattenNormal(inverse, v3(q5.x, q5.y, q5.z));
+        const float w = 1.f - u - v;
+        uvU = fmaf(w, q1.w, fmaf(u, q3.w, v * q5.w));
+        uvV = fmaf(w, q2.w, fmaf(u, q4.w, v * q6.x));
+        shadingNormal = v3(
+            fmaf(w, n0.x, fmaf(u, n1.x, v * n2.x)),
+            fmaf(w, n0.y, fmaf(u, n1.y, v * n2.y)),
+            fmaf(w, n0.z, fmaf(u, n1.z, v * n2.z)));
+        geometricNormal = triangleNormal(p0, p1, p2);
+        material = floatAsInt(q0.w);
+        if (length(shadingNormal) == 0.f) { shadingNormal = geometricNormal; }
+        shadingNormal = normalized(shadingNormal);
+    } else if (!TRAITS::spheres || prim < scene.nTris) {
         // A triangle without vertex normals and uvs (all exactly zero: the interpolated shading normal has length 0 and
         // the geometric normal takes its place, uv = 0) is shaded from a 32-byte record.  Which primitives are plain is a
         // few id ranges in the kernel arguments (scalar compares), so either load is issued at once.
@@ -2165,8 +2309,10 @@ struct MaterialAccess {
 #else
 #define PATHED_SHADE_ATTRIBUTE
 #endif
-template <bool LDS_MATERIALS, bool ENV_ONLY, typename TRAITS = TraitsAll>
-__global__ __launch_bounds__(kBlock) PATHED_SHADE_ATTRIBUTE void k_shade(RenderParams p)
+// The shade stage of the wavefront, one lane per slot: the body of k_shade and of k_shade_instanced (INSTANCED: makeIsect
+// flattens the record of a hit on an instance), as pathVolume serves k_path_volume and k_list_volume.
+template <bool LDS_MATERIALS, bool ENV_ONLY, typename TRAITS, bool INSTANCED>
+__device__ __forceinline__ void shadeSlots(const RenderParams &p, const DInstanceSet *instances)
 {
     __shared__ DMaterial ldsMaterials[LDS_MATERIALS ? kMaxLdsMaterials : 1];
     __shared__ unsigned int scratch[kWavesPerBlock + 1];
@@ -2276,7 +2422,7 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ATTRIBUTE void k_shade(RenderP
         // the lanes of a wave sit at different path depths, and code inlined in both branches is
         // executed twice by every mixed wave
         SHADE_REGION(2, !miss);   // makeIsect
-        if (!miss) { isect = makeIsect<TRAITS>(scene, o, d, h); }
+        if (!miss) { isect = makeIsect<TRAITS, INSTANCED>(scene, o, d, h, instances); }
         SHADE_REGION(3, rayBounce == 0);
         SHADE_REGION(4, rayBounce != 0 && (st & kStEligible) != 0);   // finishes the previous vertex's MIS term
 
@@ -2557,6 +2703,20 @@ __global__ __launch_bounds__(kBlock) PATHED_SHADE_ATTRIBUTE void k_shade(RenderP
     if (lane == 0 && retiredMask != 0ull) {
         atomicSub(&p.counters[kCtrRemaining], (unsigned int)__popcll(retiredMask));
     }
+}
+
+template <bool LDS_MATERIALS, bool ENV_ONLY, typename TRAITS = TraitsAll>
+__global__ __launch_bounds__(kBlock) PATHED_SHADE_ATTRIBUTE void k_shade(RenderParams p)
+{
+    shadeSlots<LDS_MATERIALS, ENV_ONLY, TRAITS, false>(p, nullptr);
+}
+
+// ... of an instanced scene (trace.h: "Instances"): the same stage behind k_trace_instanced.  Such a scene's prototypes hold no
+// emitter (the ABI refuses them), so every light record, lightsPDF and the emitter look-ups only ever see world triangles.
+template <bool LDS_MATERIALS, bool ENV_ONLY>
+__global__ __launch_bounds__(kBlock) void k_shade_instanced(RenderParams p, DInstanceSet instances)
+{
+    shadeSlots<LDS_MATERIALS, ENV_ONLY, TraitsAll, true>(p, &instances);
 }
 
 // the wavefront's local rays (RenderParams::localTris): can a ray meet anything but the scene's large triangles, and its closest

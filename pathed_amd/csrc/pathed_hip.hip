@@ -313,6 +313,13 @@ struct PathedScene {
     int parkMinCards = 1;                    // PATHED_PARK_MIN_CARDS
     int computeUnits = 256;
 
+    // instanced scenes (trace.h: "Instances"; pathed_hip_scene_create_instanced): the records and id bases of the placements
+    bool instanced = false;
+    DeviceBuffer<float4> instanceRecords;
+    DeviceBuffer<int> instanceBases;
+    DInstanceSet instanceSet = { nullptr, nullptr, 0, 0 };
+    int instancedMaxStack = 0;    // the top tree's bound + the deepest prototype's + 1
+
     bool countMode = false;
     bool timeKernels = false;
     int timeInterval = 1;                 // HIP-event pairs around every n-th launch pair of a pool
@@ -580,8 +587,26 @@ void launchTraceStack(PathedScene *scene, const RenderParams &params, hipStream_
     });
 }
 
+// k_trace_instanced<STACK, COUNT>: the three stack-row counts, with and without counting
+void launchTraceInstanced(PathedScene *scene, const RenderParams &params, hipStream_t stream)
+{
+    // a grid-stride kernel: at most the grid the overflow columns were sized for, at most a wave per batch of slots and one more
+    // block's worth for the shadow list
+    const int wanted = 2 * params.nSlots / kBlock;
+    const dim3 grid((unsigned)(wanted < scene->traceGrid ? (wanted > 0 ? wanted : 1) : scene->traceGrid)), block(kBlock);
+    const size_t lds = (size_t)(scene->stackRows + 1) * kBlock * sizeof(int);
+    withBool(scene->countMode, [&](auto COUNT) {
+        switch (scene->stackRows) {
+        case 8: hipLaunchKernelGGL((k_trace_instanced<8, COUNT>), grid, block, lds, stream, params, scene->instanceSet); break;
+        case 16: hipLaunchKernelGGL((k_trace_instanced<16, COUNT>), grid, block, lds, stream, params, scene->instanceSet); break;
+        default: hipLaunchKernelGGL((k_trace_instanced<22, COUNT>), grid, block, lds, stream, params, scene->instanceSet); break;
+        }
+    });
+}
+
 void launchTrace(PathedScene *scene, const RenderParams &params, hipStream_t stream)
 {
+    if (scene->instanced) { launchTraceInstanced(scene, params, stream); return; }
     if (scene->bruteForce) {
         // uniform cost per batch and no per-block setup: one 64-ray batch per wave, the hardware
         // dispatcher balances (a persistent grid quantises 3.3 batches per wave to 4 rounds)
@@ -707,6 +732,14 @@ void launchShade(PathedScene *scene, const RenderParams &params, hipStream_t str
         return;
     }
 #endif
+    if (scene->instanced) {
+        const dim3 slotGrid((unsigned)(params.nSlots / kBlock));
+        withBool(ldsMaterials, [&](auto LDS_MATERIALS) {
+            if (scene->traits.envOnly) { hipLaunchKernelGGL((k_shade_instanced<LDS_MATERIALS, true>), slotGrid, dim3(kBlock), 0, stream, params, scene->instanceSet); }
+            else { hipLaunchKernelGGL((k_shade_instanced<LDS_MATERIALS, false>), slotGrid, dim3(kBlock), 0, stream, params, scene->instanceSet); }
+        });
+        return;
+    }
     const dim3 grid((unsigned)(params.nSlots / kBlock)), block(kBlock);
     // (k_shade narrowed further to {Lambertian, plastic, environment} -- 88 VGPRs against 92 -- shortens the shade launches of
     // the 5.2 M-triangle mesh by 13 % and LENGTHENS the other pool's trace launches by 23 %: -4.8 % overall, not adopted,
@@ -749,6 +782,7 @@ void configureTrace(PathedScene *scene)
     const int requested = requestedNodeFormat(options);
     const bool mayWalkNode8 = requested == 3 || (requested == 0 && PATHED_DEFAULT_NODE_FORMAT == 2);
     scene->maxStack = mayWalkNode8 ? 7 * scene->bvh.maxDepth + 9 : 3 * scene->bvh.maxDepth + 1;
+    if (scene->instanced) { scene->maxStack = scene->instancedMaxStack; }
     scene->stackRows = scene->maxStack <= 8 ? 8 : scene->maxStack <= 16 ? 16 : 22;
     if (options.stack_rows == 8 || options.stack_rows == 16 || options.stack_rows == 22) { scene->stackRows = options.stack_rows; }
     if (const char *override = tuningEnv("PATHED_STACK_ROWS")) {   // experiments: force the HBM spill path
@@ -761,7 +795,7 @@ void configureTrace(PathedScene *scene)
         + (scene->splitShade ? (size_t)kWavesPerBlock * 2 * 128 * sizeof(unsigned int) : 0);
     const size_t sceneBytes = (size_t)scene->device.nNodes * 128 + (size_t)scene->device.nTris * 48;
     // stage the BVH in LDS when it is small enough to leave >= 4 blocks per CU
-    scene->sceneInLds = scene->device.nNodes > 0 && (stackBytes + sceneBytes) <= 36 * 1024;
+    scene->sceneInLds = scene->device.nNodes > 0 && (stackBytes + sceneBytes) <= 36 * 1024 && !scene->instanced;   // (k_trace_instanced walks HBM)
     scene->traceLdsBytes = stackBytes + (scene->sceneInLds ? sceneBytes : 0);
 
     int blocksPerCu = (int)((160 * 1024) / (scene->traceLdsBytes ? scene->traceLdsBytes : 1));
@@ -772,6 +806,8 @@ void configureTrace(PathedScene *scene)
     // and 1 411 / 1 829 / 1 106 with one: two 96-VGPR trace waves leave a SIMD room for THREE 104-VGPR k_shade waves.
     // 448 .. 640 blocks are within 2 % (PATHED_TRACE_GRID).  A single pool wants at least four (tools/occupancy_sweep.sh).
     if (!scene->sceneInLds) { blocksPerCu = scene->pools > 1 ? (blocksPerCu < 2 ? blocksPerCu : 2) : (blocksPerCu < 5 ? blocksPerCu : 5); }
+    // (k_trace_instanced: one ray per lane and no refill, so latency is hidden by waves alone: four blocks per CU)
+    if (scene->instanced) { blocksPerCu = 4; }
     if (blocksPerCu < 1) { blocksPerCu = 1; }
     if (options.trace_blocks_per_cu >= 1 && options.trace_blocks_per_cu <= 16) { blocksPerCu = options.trace_blocks_per_cu; }
     if (const char *override = tuningEnv("PATHED_TRACE_BLOCKS_PER_CU")) {
@@ -1459,7 +1495,176 @@ static SceneTraitFlags sceneTraits(const PathedSceneDesc *desc, const std::vecto
     return t;
 }
 
-int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOptions *optionsIn, PathedScene **out)
+// ---- instanced scenes (include/pathed_hip.h: PathedInstanceDesc; pathed_amd/csrc/trace.h: "Instances")
+struct InstancedLayout {
+    int worldTris = 0;                        // T0
+    std::vector<int> protoFirst, protoCount;  // triangle range of each prototype in the description
+    std::vector<int> bases;                   // nInstances + 1 virtual-id bases
+    std::vector<float> inverses;              // 12 floats per instance
+};
+
+// Everything that can be refused about an instanced scene, before anything is allocated or launched.
+static int planInstances(const PathedSceneDesc *desc, const PathedSceneOptions &options, const PathedInstanceDesc *in, InstancedLayout *layout)
+{
+    if (in->struct_size != sizeof(PathedInstanceDesc)) { return fail(PATHED_E_INVALID, "PathedInstanceDesc.struct_size mismatch"); }
+    if ((in->n_prototypes && !in->prototypes) || (in->n_instances && !in->instances)) { return fail(PATHED_E_INVALID, "prototype or instance array missing"); }
+    if (in->n_instances >= (1u << 30) - 1u) { return fail(PATHED_E_INVALID, "too many instances (the limit is 2^30 - 2)"); }
+    if (desc->n_spheres > 0) { return fail(PATHED_E_UNSUPPORTED, "sphere primitives in a scene with instances are not supported"); }
+    bool containers = false;
+    for (uint32_t i = 0; i < desc->n_materials; i++) { containers = containers || desc->materials[i].type == PATHED_MAT_PASSTHROUGH; }
+    if (desc->n_media > 0 || containers) { return fail(PATHED_E_UNSUPPORTED, "media and containers (passthrough materials) in a scene with instances are not supported"); }
+    if (options.refittable) { return fail(PATHED_E_UNSUPPORTED, "refittable: a scene with instances cannot be refitted"); }
+    if (options.bvh_builder > PATHED_BVH_SAH_HOST + 1) { return fail(PATHED_E_UNSUPPORTED, "the device builders (LBVH, PLOC) do not build a scene with instances: use the host SAH builder"); }
+    if (options.shade_kernel != 0 && options.shade_kernel != 1) { return fail(PATHED_E_UNSUPPORTED, "shade_kernel: a scene with instances renders on the wavefront's per-slot pair only (0 or 1)"); }
+    if (options.node_format >= 2) { return fail(PATHED_E_UNSUPPORTED, "node_format: a scene with instances is walked over the 128-byte float nodes"); }
+    // the geoms cover the triangles in order; the prototypes' geoms are the tail of the array, prototype after prototype
+    uint32_t nextTriangle = 0;
+    for (uint32_t g = 0; g < desc->n_geoms; g++) {
+        if (desc->geoms[g].type != PATHED_GEOM_MESH || (uint32_t)desc->geoms[g].first != nextTriangle) {
+            return fail(PATHED_E_INVALID, "a scene with instances: the mesh geoms must cover the triangles in order, without gaps");
+        }
+        nextTriangle += (uint32_t)desc->geoms[g].count;
+    }
+    if (nextTriangle != desc->n_triangles) { return fail(PATHED_E_INVALID, "a scene with instances: the mesh geoms must cover all triangles"); }
+    if (desc->n_triangles >= (1u << 27)) { return fail(PATHED_E_INVALID, "a scene with instances stores fewer than 2^27 triangles (the instance leaf encoding)"); }
+    uint32_t firstProtoGeom = desc->n_geoms;
+    if (in->n_prototypes > 0) { firstProtoGeom = (uint32_t)in->prototypes[0].first_geom; }
+    uint32_t nextGeom = firstProtoGeom;
+    for (uint32_t p = 0; p < in->n_prototypes; p++) {
+        const PathedPrototype &proto = in->prototypes[p];
+        if (proto.first_geom < 0 || proto.n_geoms < 1 || (uint32_t)proto.first_geom != nextGeom || (uint64_t)nextGeom + (uint64_t)proto.n_geoms > desc->n_geoms) {
+            return fail(PATHED_E_INVALID, "prototypes must name consecutive, non-empty geom ranges that end the geom array");
+        }
+        const int first = desc->geoms[nextGeom].first;
+        int count = 0;
+        for (int g = 0; g < proto.n_geoms; g++) { count += desc->geoms[nextGeom + (uint32_t)g].count; }
+        if (count < 1) { return fail(PATHED_E_INVALID, "a prototype needs at least one triangle"); }
+        for (int i = 0; i < count; i++) {
+            const PathedMaterial &material = desc->materials[(size_t)desc->tri_material[first + i]];
+            if (!(material.emit[0] == 0.f && material.emit[1] == 0.f && material.emit[2] == 0.f)) {
+                return fail(PATHED_E_UNSUPPORTED, "an emissive material inside a prototype is not supported: bake such faces into world triangles, one copy per placement");
+            }
+        }
+        layout->protoFirst.push_back(first);
+        layout->protoCount.push_back(count);
+        nextGeom += (uint32_t)proto.n_geoms;
+    }
+    if (nextGeom != desc->n_geoms) { return fail(PATHED_E_INVALID, "prototypes must name consecutive, non-empty geom ranges that end the geom array"); }
+    layout->worldTris = firstProtoGeom < desc->n_geoms ? desc->geoms[firstProtoGeom].first : (int)desc->n_triangles;
+    uint64_t virtualTris = (uint64_t)layout->worldTris;
+    layout->inverses.resize((size_t)12 * in->n_instances);
+    for (uint32_t k = 0; k < in->n_instances; k++) {
+        const PathedInstance &instance = in->instances[k];
+        if (instance.prototype < 0 || (uint32_t)instance.prototype >= in->n_prototypes) { return fail(PATHED_E_INVALID, "instance prototype index out of range"); }
+        for (int i = 0; i < 12; i++) { if (!(instance.transform[i] - instance.transform[i] == 0.f)) { return fail(PATHED_E_INVALID, "instance transform is not finite"); } }
+        if (!instanceInverse(instance.transform, &layout->inverses[(size_t)12 * k])) { return fail(PATHED_E_INVALID, "instance transform is not invertible"); }
+        layout->bases.push_back((int)virtualTris);
+        virtualTris += (uint64_t)layout->protoCount[(size_t)instance.prototype];
+        if (virtualTris >= (1ull << 31)) { return fail(PATHED_E_INVALID, "a scene with instances: the virtual primitive ids (world triangles + every placement's) must stay below the limit of 2^31"); }
+    }
+    layout->bases.push_back((int)virtualTris);
+    return PATHED_OK;
+}
+
+// The two-level tree in one node array and one leaf-triangle array (trace.h): the top tree over the world triangles and the
+// placements' world boxes, then one object-space tree per prototype, refs and firsts made absolute.
+static FlatBvh buildInstancedBvh(const PathedSceneDesc *desc, const PathedInstanceDesc *in, const InstancedLayout &layout, int buildThreads,
+                                 std::vector<float4> *records, int *maxStack)
+{
+    const size_t nProto = layout.protoFirst.size();
+    std::vector<FlatBvh> trees(nProto);
+    std::vector<float> protoLo(3 * nProto), protoHi(3 * nProto);
+    int deepest = 0;
+    for (size_t p = 0; p < nProto; p++) {
+        const int first = layout.protoFirst[p], count = layout.protoCount[p];
+        trees[p] = buildBvh(desc->positions, desc->indices + (size_t)3 * first, (uint32_t)count, nullptr, 0, buildThreads);
+        deepest = std::max(deepest, trees[p].maxDepth);
+        bvh_detail::Box box;
+        box.reset();
+        for (int i = 0; i < 3 * count; i++) {
+            const float *corner = desc->positions + (size_t)3 * desc->indices[(size_t)3 * first + i];
+            box.grow(corner, corner);
+        }
+        bvh_detail::padBox(box, &protoLo[3 * p], &protoHi[3 * p]);   // what the prototype's root children span at most
+    }
+    // a placement's world box: the corners of the padded prototype box through the flatten routine, padded once more for the
+    // roundings of the object-space ray (the builder pads the node's copy a third time, as it pads every child box)
+    std::vector<float> boxes((size_t)6 * in->n_instances);
+    for (uint32_t k = 0; k < in->n_instances; k++) {
+        const PathedInstance &instance = in->instances[k];
+        const float *lo = &protoLo[(size_t)3 * instance.prototype], *hi = &protoHi[(size_t)3 * instance.prototype];
+        bvh_detail::Box box;
+        box.reset();
+        for (int corner = 0; corner < 8; corner++) {
+            const V3 world = flattenPoint(instance.transform, v3((corner & 1) ? hi[0] : lo[0], (corner & 2) ? hi[1] : lo[1], (corner & 4) ? hi[2] : lo[2]));
+            const float point[3] = { world.x, world.y, world.z };
+            box.grow(point, point);
+        }
+        for (int a = 0; a < 3; a++) {
+            const float pad = 1e-5f * std::max(1.f, std::max(std::fabs(box.lo[a]), std::fabs(box.hi[a]))) + 1e-5f * (box.hi[a] - box.lo[a]);
+            boxes[(size_t)6 * k + a] = box.lo[a] - pad;
+            boxes[(size_t)6 * k + 3 + a] = box.hi[a] + pad;
+        }
+    }
+    FlatBvh out = buildBvh(desc->positions, desc->indices, (uint32_t)layout.worldTris, boxes.data(), in->n_instances, buildThreads, 0, true);
+    // the placements' one-primitive leaves (count 0, first = index + 1) become instance leaves
+    for (int n = 0; n < out.nodeCount; n++) {
+        for (int k = 0; k < 4; k++) {
+            int ref;
+            std::memcpy(&ref, &out.nodes[(size_t)kNodeFloats * n + 24 + k], 4);
+            if (ref == kEmptyChildRef || ref >= 0) { continue; }
+            const int payload = -ref - 1;
+            if ((payload & 7) != 0) { continue; }
+            bvh_detail::putInt(&out.nodes[(size_t)kNodeFloats * n + 24 + k], -(kInstanceLeafBit | ((payload >> 3) - 1)) - 1);
+        }
+    }
+    if (out.nodeCount == 0) {
+        // nothing in the world: an empty root, so that node 0 is never a prototype's
+        out.nodes.assign((size_t)kNodeFloats, 0.f);
+        for (int k = 0; k < 4; k++) { bvh_detail::putInt(&out.nodes[24 + k], kEmptyChildRef); }
+        out.nodeCount = 1;
+        out.maxDepth = 1;
+    }
+    *maxStack = (3 * out.maxDepth + 1) + (3 * deepest + 1) + 1;
+    out.maxDepth += deepest;
+    std::vector<int> protoRoot(nProto);
+    int triOffset = layout.worldTris;
+    for (size_t p = 0; p < nProto; p++) {
+        const int nodeOffset = out.nodeCount;
+        protoRoot[p] = nodeOffset;
+        const size_t nodeBase = out.nodes.size();
+        out.nodes.insert(out.nodes.end(), trees[p].nodes.begin(), trees[p].nodes.end());
+        for (int n = 0; n < trees[p].nodeCount; n++) {
+            for (int k = 0; k < 4; k++) {
+                float *slot = &out.nodes[nodeBase + (size_t)kNodeFloats * n + 24 + k];
+                int ref;
+                std::memcpy(&ref, slot, 4);
+                if (ref == kEmptyChildRef) { continue; }
+                if (ref >= 0) { bvh_detail::putInt(slot, ref + nodeOffset); continue; }
+                const int payload = -ref - 1;
+                bvh_detail::putInt(slot, -((((payload >> 3) + triOffset) << 3) | (payload & 7)) - 1);
+            }
+        }
+        out.leafTris.insert(out.leafTris.end(), trees[p].leafTris.begin(), trees[p].leafTris.end());   // (prim = the index inside the prototype)
+        out.nodeCount += trees[p].nodeCount;
+        triOffset += layout.protoCount[p];
+    }
+    records->resize((size_t)kInstanceQuads * in->n_instances);
+    for (uint32_t k = 0; k < in->n_instances; k++) {
+        const float *m = in->instances[k].transform, *inverse = &layout.inverses[(size_t)12 * k];
+        const int prototype = in->instances[k].prototype;
+        float4 *record = records->data() + (size_t)kInstanceQuads * k;
+        for (int row = 0; row < 3; row++) {
+            record[row] = make_float4(m[4 * row], m[4 * row + 1], m[4 * row + 2], m[4 * row + 3]);
+            record[3 + row] = make_float4(inverse[4 * row], inverse[4 * row + 1], inverse[4 * row + 2], inverse[4 * row + 3]);
+        }
+        const int ids[4] = { layout.bases[k], prototype, protoRoot[(size_t)prototype], layout.protoFirst[(size_t)prototype] };
+        std::memcpy(&record[6], ids, sizeof ids);
+    }
+    return out;
+}
+
+static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *optionsIn, const PathedInstanceDesc *instanceDesc, PathedScene **out)
 {
     if (!out) { return fail(PATHED_E_INVALID, "out pointer is null"); }
     *out = nullptr;
@@ -1495,6 +1700,11 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
         if (options.hybrid_batch < 0 || options.hybrid_batch > 128) { return fail(PATHED_E_INVALID, "hybrid_batch must be 0 (default) or 1..128"); }
         if (options.hybrid_ready < -1 || options.hybrid_ready > 64) { return fail(PATHED_E_INVALID, "hybrid_ready must be -1 (never), 0 (default) or 1..64"); }
     }
+    InstancedLayout instancedLayout;
+    if (instanceDesc) {
+        code = planInstances(desc, options, instanceDesc, &instancedLayout);
+        if (code != PATHED_OK) { return code; }
+    }
     int deviceId = options.device;
     if (deviceId == PATHED_DEVICE_CURRENT) {
         if (g_device < 0) {
@@ -1516,6 +1726,7 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
     scene->options = options;
     scene->width = desc->camera.width;
     scene->height = desc->camera.height;
+    scene->instanced = instanceDesc != nullptr;
 
     hipDeviceProp_t properties;
     if (hipGetDeviceProperties(&properties, deviceId) == hipSuccess) {
@@ -1752,14 +1963,27 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
             }
         }
         scene->spheresInTree = !sphereBounds.empty();
-        scene->bvh = buildBvh(desc->positions, desc->indices, desc->n_triangles, sphereBounds.data(), (uint32_t)(sphereBounds.size() / 4),
-                              scene->options.build_threads);
+        std::vector<float4> instanceRecords;
+        if (instanceDesc) {
+            scene->bvh = buildInstancedBvh(desc, instanceDesc, instancedLayout, scene->options.build_threads, &instanceRecords, &scene->instancedMaxStack);
+        } else {
+            scene->bvh = buildBvh(desc->positions, desc->indices, desc->n_triangles, sphereBounds.data(), (uint32_t)(sphereBounds.size() / 4),
+                                  scene->options.build_threads);
+        }
         scene->bvhBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - buildStart).count();
         std::vector<float4> nodes(scene->bvh.nodes.size() / 4), tris(scene->bvh.leafTris.size() / 4);
         std::memcpy(nodes.data(), scene->bvh.nodes.data(), scene->bvh.nodes.size() * sizeof(float));
         std::memcpy(tris.data(), scene->bvh.leafTris.data(), scene->bvh.leafTris.size() * sizeof(float));
         if ((status = scene->nodes.upload(nodes)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload nodes"); }
         if ((status = scene->leafTris.upload(tris)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload triangles"); }
+        if (instanceDesc) {
+            if ((status = scene->instanceRecords.upload(instanceRecords)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload instance records"); }
+            if ((status = scene->instanceBases.upload(instancedLayout.bases)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload instance bases"); }
+            scene->instanceSet.records = scene->instanceRecords.ptr;
+            scene->instanceSet.bases = scene->instanceBases.ptr;
+            scene->instanceSet.nInstances = (int)instanceDesc->n_instances;
+            scene->instanceSet.worldTris = instancedLayout.worldTris;
+        }
     }
     status = hipDeviceSynchronize();   // the shading-record gather reads the soup
     if (status == hipSuccess && options.refittable && desc->n_triangles > 0) {
@@ -1868,7 +2092,7 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
         scene->pools = value < 1 ? 1 : value > kMaxPools ? kMaxPools : value;
     }
     scene->bruteForce = scene->device.nTris <= kBruteForceMaxTris && scene->device.nSpheres <= kBruteForceMaxSpheres
-        && options.intersector != 1 && !tuningEnv("PATHED_NO_BRUTE_FORCE");
+        && options.intersector != 1 && !tuningEnv("PATHED_NO_BRUTE_FORCE") && !scene->instanced;
     // BVH scenes: more slots = more rays per persistent wave to refill finished lanes from (ray cost is heavy-tailed) and
     // fewer, longer launches: 8 Mi slots (1.3 GB of path state) against 4 Mi: +3.6 % on the teapot, +6.1 % on the 5.2 M-
     // triangle mesh at >= 256 spp per call, 16 Mi +1 % / +7.6 %, 32 Mi less again (tools/slots_sweep.py); short calls want
@@ -1881,7 +2105,8 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
     // shade stage (k_vertex + k_regen over lists the trace kernel writes) are selectable: both issue fewer
     // instructions on fuller waves and both lose to the coalesced per-slot kernel (DESIGN.md has the measurements)
     int shadeKernel = options.shade_kernel;
-    if (const char *text = tuningEnv("PATHED_SHADE_KERNEL")) {   // experiments: "per-slot" | "staged" | "fused" | "split"
+    if (scene->instanced) { shadeKernel = 1; }   // always the wavefront, with k_trace_instanced / k_shade_instanced
+    else if (const char *text = tuningEnv("PATHED_SHADE_KERNEL")) {   // experiments: "per-slot" | "staged" | "fused" | "split"
         if (!strcmp(text, "per-slot")) { shadeKernel = 1; }
         else if (!strcmp(text, "staged")) { shadeKernel = 2; }
         else if (!strcmp(text, "fused")) { shadeKernel = 3; }
@@ -1909,7 +2134,7 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
         // the compressed tree: sphere-free scenes whose tree stays in HBM, walked by the per-slot pipeline's trace kernel
         const int nodeFormat = requestedNodeFormat(options);
         const bool eligible = !scene->bruteForce && !scene->sceneInLds && !scene->splitShade && scene->device.nSpheres == 0
-            && scene->device.nNodes > 0 && options.generic_kernels == 0;
+            && scene->device.nNodes > 0 && options.generic_kernels == 0 && !scene->instanced;
         if (nodeFormat >= 2 && !eligible) {
             delete scene;
             return fail(PATHED_E_INVALID, "compressed nodes serve sphere-free scenes whose tree is walked in HBM by the per-slot pipeline (not generic_kernels, not the split stage)");
@@ -1939,13 +2164,14 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
     if (const char *text = tuningEnv("PATHED_REGEN_GRID")) { const int value = atoi(text); if (value >= 1 && value <= 65536) { scene->regenGrid = value; } }
     scene->fusedPath = scene->bruteForce && (shadeKernel == 0 || shadeKernel == 3);
     scene->waveMode = shadeKernel == 5 ? 2 : (shadeKernel == 0 || shadeKernel == 6) ? 0 : 1;
-    scene->waveAvailable = !scene->bruteForce && scene->device.nMaterials <= kMaxLdsMaterials && scene->nodeFormat == 0;
+    scene->waveAvailable = !scene->bruteForce && scene->device.nMaterials <= kMaxLdsMaterials && scene->nodeFormat == 0 && !scene->instanced;
     {
         // [r5] k_path_hybrid: BVH scenes small enough that a handful of large triangles carry most of the hits (path_hybrid.h)
         // (shade_kernel 6 asks for it on a larger mesh as well: the walk is the same, the tree just stops being cache-resident)
         const bool eligible = !scene->bruteForce && desc->n_spheres == 0
             && scene->device.nMaterials <= kMaxLdsMaterials && scene->nodeFormat == 0 && options.intersector != 1 && !scene->hasContainers
-            && !options.refittable;   // (a refittable scene keeps ONE tree, the one pathed_hip_scene_refit moves)
+            && !options.refittable    // (a refittable scene keeps ONE tree, the one pathed_hip_scene_refit moves)
+            && !scene->instanced;
         if (shadeKernel == 6 && !eligible) {
             delete scene;
             return fail(PATHED_E_INVALID, "the hybrid path kernel serves sphere-free scenes of more than 64 triangles and at most 96 materials (intersector 0, not refittable)");
@@ -1956,7 +2182,7 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
         }
     }
     // (not for refittable scenes: their vertices move, the large triangles' records and the bounds of the rest would go stale)
-    if (!scene->bruteForce && options.local_rays != 1 && scene->nodeFormat == 0 && !options.refittable) { buildLocalSet(scene, desc); }
+    if (!scene->bruteForce && options.local_rays != 1 && scene->nodeFormat == 0 && !options.refittable && !scene->instanced) { buildLocalSet(scene, desc); }
     if (shadeKernel == 5 && !scene->waveAvailable) {
         delete scene;
         return fail(PATHED_E_INVALID, "the wave path kernel serves BVH scenes (more than 64 triangles or intersector 1) of at most 96 materials over the float nodes");
@@ -2023,6 +2249,17 @@ int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOpt
     }
     *out = scene;
     return PATHED_OK;
+}
+
+int pathed_hip_scene_create_ex(const PathedSceneDesc *desc, const PathedSceneOptions *optionsIn, PathedScene **out)
+{
+    return createScene(desc, optionsIn, nullptr, out);
+}
+
+int pathed_hip_scene_create_instanced(const PathedSceneDesc *desc, const PathedSceneOptions *optionsIn, const PathedInstanceDesc *instances, PathedScene **out)
+{
+    if (!instances) { return fail(PATHED_E_INVALID, "instance description is null"); }
+    return createScene(desc, optionsIn, instances, out);
 }
 
 void pathed_hip_scene_destroy(PathedScene *scene)
@@ -2511,7 +2748,7 @@ static int renderPass(PathedScene *scene, const Pass &pass)
             q.listCap = scene->listCap;
         }
         const size_t traceWaves = (size_t)scene->traceGrid * kWavesPerBlock;
-        q.suspendLanes = scene->bruteForce ? 0 : scene->suspendLanes;
+        q.suspendLanes = (scene->bruteForce || scene->instanced) ? 0 : scene->suspendLanes;   // (k_trace_small and k_trace_instanced park nothing)
         q.suspendPatience = scene->suspendPatience;
         q.parkMinCardsPerWave = scene->parkMinCards;
         q.suspendMask = scene->bruteForce ? nullptr : scene->suspendMask.ptr + (size_t)h * traceWaves;
@@ -2754,6 +2991,10 @@ static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uin
     }
     if (spp_count == 0) { return PATHED_OK; }
     if ((uint64_t)spp_begin + spp_count > 0x7fffffffull) { return fail(PATHED_E_INVALID, "sample index overflow"); }
+    if (scene->instanced && scene->integrator != PATHED_INTEGRATOR_PATH_TRACER) {
+        return fail(PATHED_E_UNSUPPORTED, "a scene with instances renders with the PathTracer integrator only: the volume integrators, the basic volume "
+                                          "integrator and the albedo integrator do not know the two-level tree");
+    }
     if (scene->integrator == PATHED_INTEGRATOR_ALBEDO) {
         // AlbedoIntegrator::L never looks at the bounce window: last_bounce is ignored, start_bounce decides bounce 0's emission
         if (scene->hasContainers) { return fail(PATHED_E_UNSUPPORTED, "the albedo integrator does not render scenes with passthrough (medium container) surfaces"); }
@@ -2808,7 +3049,7 @@ static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uin
     // [r5] ... and scenes of 65 .. 4096 triangles on the hybrid kernel at every length (counting is the wavefront's)
     const bool hybridPath = scene->hybridPath && !usesVolumeKernel(scene) && !scene->countMode;
     const bool listPass = pixels != nullptr;   // ... and a call over a pixel list on the wavefront (k_list_volume with media), whatever the scene
-    scene->lastCallWave = wavePath && !hybridPath && !listPass;
+    scene->lastCallWave = wavePath && !hybridPath && !listPass && !scene->instanced;
     scene->lastCallHybrid = hybridPath && !listPass;
     scene->lastCallList = listPass;
     Pass pass;
@@ -2831,7 +3072,8 @@ static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uin
         const unsigned long long nUnits = (unsigned long long)pass.unitPixels() * (unsigned long long)pass.chunksPerPixel;
         if (nUnits >= 0xFFFFFFF0ull) { return fail(PATHED_E_INVALID, "too many work units in one pass"); }
         pass.nUnits = (unsigned int)nUnits;
-        const int code = usesVolumeKernel(scene) ? renderPassVolume(scene, pass)
+        const int code = scene->instanced ? renderPass(scene, pass)
+            : usesVolumeKernel(scene) ? renderPassVolume(scene, pass)
             : listPass ? renderPass(scene, pass)
             : scene->fusedPath ? renderPassFused(scene, pass)
             : hybridPath ? renderPassHybrid(scene, pass)
@@ -3079,6 +3321,7 @@ int pathed_hip_render_features_device(PathedScene *scene, uint64_t seed, uint32_
     if (!buffers || (!buffers->albedo_sum && !buffers->normal_sum && !buffers->depth_sum && !buffers->hit_count)) {
         return fail(PATHED_E_INVALID, "no feature buffer: pass at least one of albedo, normal, depth, hits");
     }
+    if (scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "feature images do not cover scenes with instances"); }
     if (spp_count == 0) { return PATHED_OK; }
     if ((uint64_t)spp_begin + spp_count > 0x7fffffffull) { return fail(PATHED_E_INVALID, "sample index overflow"); }
     if (scene->hasContainers) { return fail(PATHED_E_UNSUPPORTED, "feature images do not cover scenes with passthrough (medium container) surfaces"); }
@@ -3140,7 +3383,15 @@ int pathed_hip_trace(PathedScene *scene, const float *rays, size_t n, int any_hi
         const size_t lds = (size_t)(scene->stackRows + 1) * kBlock * sizeof(int);
         const size_t overflowRows = (size_t)(scene->maxStack > scene->stackRows ? scene->maxStack - scene->stackRows : 0);
         status = hipMalloc((void **)&deviceOverflow, (size_t)grid.x * kBlock * (overflowRows ? overflowRows : 1) * sizeof(int));
-        if (status == hipSuccess) {
+        if (status == hipSuccess && scene->instanced) {
+            switch (scene->stackRows) {
+            case 8: hipLaunchKernelGGL((k_trace_rays_instanced<8>), grid, block, lds, 0, scene->device, scene->instanceSet, deviceRays, (int)n, any_hit, deviceHits, deviceOccluded, deviceOverflow, scene->maxStack); break;
+            case 16: hipLaunchKernelGGL((k_trace_rays_instanced<16>), grid, block, lds, 0, scene->device, scene->instanceSet, deviceRays, (int)n, any_hit, deviceHits, deviceOccluded, deviceOverflow, scene->maxStack); break;
+            default: hipLaunchKernelGGL((k_trace_rays_instanced<22>), grid, block, lds, 0, scene->device, scene->instanceSet, deviceRays, (int)n, any_hit, deviceHits, deviceOccluded, deviceOverflow, scene->maxStack); break;
+            }
+            status = hipGetLastError();
+            if (status == hipSuccess) { status = hipDeviceSynchronize(); }
+        } else if (status == hipSuccess) {
             #define PATHED_HOOK(STACK, FORMAT) hipLaunchKernelGGL((k_trace_rays<STACK, FORMAT>), grid, block, lds, 0, scene->device, deviceRays, (int)n, any_hit, deviceHits, deviceOccluded, deviceOverflow, scene->maxStack)
             #define PATHED_HOOK_ROWS(FORMAT) switch (scene->stackRows) { \
                 case 8: PATHED_HOOK(8, FORMAT); break; \
@@ -3376,6 +3627,7 @@ int pathed_hip_has_experiments(void) { return PATHED_EXPERIMENTS ? 1 : 0; }
 int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out)
 {
     if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector's hook does not serve scenes with instances"); }
     if (!scene->bruteForce || scene->device.nTris < 1) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector serves scenes of 1..64 triangles"); }
     if (n == 0) { return PATHED_OK; }
     if (!rays || !out) { return fail(PATHED_E_INVALID, "null ray or output buffer"); }
@@ -3412,6 +3664,7 @@ int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, siz
 int pathed_hip_debug_light_records(PathedScene *scene, float *triangles, size_t n_triangles, float *lights, size_t max_lights, int *n_lights)
 {
     if (!scene || !triangles || !lights || !n_lights) { return fail(PATHED_E_INVALID, "null scene or output buffer"); }
+    if (scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "the light-record hook assumes a flat scene: it does not serve scenes with instances"); }
     SELECT_DEVICE(scene);
     const size_t nTris = (size_t)scene->device.nTris, nLights = (size_t)scene->device.nLights;
     if (n_triangles != nTris) { return fail(PATHED_E_INVALID, "n_triangles must be the scene's triangle count"); }
@@ -3450,6 +3703,7 @@ int pathed_hip_debug_light_records(PathedScene *scene, float *triangles, size_t 
 int pathed_hip_scene_refit(PathedScene *scene, const float *positions, const float *normals, uint32_t n_vertices, float *device_ms)
 {
     if (!scene || !positions) { return fail(PATHED_E_INVALID, "null scene or positions"); }
+    if (scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "refit: a scene with instances cannot be refitted"); }
     if (!scene->refittable) { return fail(PATHED_E_INVALID, "create the scene with PathedSceneOptions.refittable = 1: the refit needs the triangle soup on the device"); }
     if ((size_t)n_vertices != scene->soupVertices) { return fail(PATHED_E_INVALID, "refit keeps the topology: the vertex count must be the scene's"); }
     if (scene->bruteForce) { return fail(PATHED_E_UNSUPPORTED, "scenes of at most 64 triangles carry no tree to refit: create the scene again (microseconds)"); }
@@ -3572,7 +3826,7 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
     out->bvh_build_ms = scene->bvhBuildMs;
     out->bvh_builder = (uint32_t)scene->bvhBuilder;
     out->trace_launches_all = (uint32_t)scene->traceLaunchesAll;
-    out->path_kernel = scene->lastCallFeatures ? 8u : (scene->lastCallList && !usesVolumeKernel(scene)) ? 1u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? 9u : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
+    out->path_kernel = scene->instanced ? 10u : scene->lastCallFeatures ? 8u : (scene->lastCallList && !usesVolumeKernel(scene)) ? 1u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? 9u : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
     if (tuningEnv("PATHED_SHADE_PROFILE")) {   // counters exist in -DPATHED_SHADE_PROFILE builds only
         static const char *regions[11] = { "all waves", "active slots", "makeIsect (hit)", "camera-ray vertex", "finish previous MIS term",
                                            "new vertex: BSDF sample", "light sampling", "sample finished", "startSample (regeneration)", "shadow ray pushed",

@@ -6,6 +6,10 @@
 //          (lo.x[4]) (lo.y[4]) (lo.z[4]) (hi.x[4]) (hi.y[4]) (hi.z[4]) (ref[4]) (-)
 //          ref >= 0: inner node index; ref <= -2: leaf, -ref - 1 = (first triangle << 3) | count;
 //          ref == kEmptyChild: empty slot
+//          INSTANCED scenes only (below: "Instances"): -ref - 1 with bit 30 set = instance leaf, the low 30 bits are the
+//          instance index.  A triangle leaf's payload stays below 2^30 there (fewer than 2^27 stored triangles) and a sphere
+//          leaf (count 0, first >= 1) has bit 30 clear, so the three kinds cannot collide; the payload 0x7FFFFFFF -- the
+//          stack entry kEmptyChild, which no node visit ever pushes -- is the traversal's "back to the world ray" sentinel
 //   nodeQ  4 x float4 = 64 B, the COMPRESSED form of the same node (same index, same refs; k_compress_nodes): the
 //          children's boxes on an 8-bit grid over their union,
 //          (origin.xyz, scale.x) (scale.y, scale.z, qlo.x[4], qlo.y[4]) (qlo.z[4], qhi.x[4], qhi.y[4], qhi.z[4]) (ref[4])
@@ -542,6 +546,140 @@ __device__ inline bool traverse(
     hit->v = ray.bestV;
     hit->prim = ray.bestPrim;
     return ray.bestPrim >= 0;
+}
+
+// ---- Instances: a two-level tree in ONE node array and ONE leaf-triangle array.
+// The top tree (root 0) holds the world triangles and, as instance leaves (header comment), the placements; the trees of the
+// prototypes follow it in the same arrays, in OBJECT space, refs and firsts absolute.  A prototype's leaf triangles carry
+// the triangle's index inside the prototype; the ids hits report are VIRTUAL: world triangles [0, T0), then instance k's
+// range [base_k, base_k + T_prototype(k)) in instance order -- the ids of the flattened scene (flattenPoint below applied to
+// every placement, triangles in that order), so "smaller t, then smaller id" is the flattened scene's rule.
+//
+// The flatten routine, fp32, one rounding per operation, no fused multiply-add (the host flattens with the same statements):
+//   point   p' = ((m[0] x + m[1] y) + m[2] z) + m[3], ... rows of the 3 x 4 transform m
+//   normal  n' = ((i[0] x + i[4] y) + i[8] z), ...    columns of the inverse's 3 x 3: the inverse transpose, not renormalised
+// and the inverse i is formed in double from the floats of m by cofactors (instanceInverse) and rounded once to float.
+// A ray enters a prototype as (i o, i3x3 d): the direction is NOT renormalised, so t is the world t and best / tfar carry over.
+struct DInstanceSet {
+    const float4 *records;   // kInstanceQuads per instance: m rows (3), inverse rows (3), (base, prototype, root node, first shading record) as ints
+    const int *bases;        // nInstances + 1 ascending virtual-id bases (the last: the scene's virtual triangle count)
+    int nInstances;
+    int worldTris;           // T0
+};
+static const int kInstanceQuads = 7;
+static const int kInstanceLeafBit = 1 << 30;
+static const int kInstanceSentinel = 0x7FFFFFFF;
+
+__host__ __device__ inline V3 flattenPoint(const float *m, V3 p)
+{
+    return v3(((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3],
+              ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7],
+              ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]);
+}
+__host__ __device__ inline V3 flattenDirection(const float *m, V3 d)
+{
+    return v3((m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z, (m[8] * d.x + m[9] * d.y) + m[10] * d.z);
+}
+__host__ __device__ inline V3 flattenNormal(const float *inverse, V3 n)
+{
+    return v3((inverse[0] * n.x + inverse[4] * n.y) + inverse[8] * n.z,
+              (inverse[1] * n.x + inverse[5] * n.y) + inverse[9] * n.z,
+              (inverse[2] * n.x + inverse[6] * n.y) + inverse[10] * n.z);
+}
+// the inverse of the affine 3 x 4 transform m, in double, rounded once; false when m is singular or not finite
+inline bool instanceInverse(const float *m, float *inverse)
+{
+    const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], k = m[10];
+    const double c00 = e * k - f * h, c01 = c * h - b * k, c02 = b * f - c * e;
+    const double c10 = f * g - d * k, c11 = a * k - c * g, c12 = c * d - a * f;
+    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
+    const double det = (a * c00 + b * c10) + c * c20;
+    if (!(det != 0.0) || !(det - det == 0.0)) { return false; }
+    const double r[9] = { c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det };
+    const double tx = m[3], ty = m[7], tz = m[11];
+    for (int row = 0; row < 3; row++) {
+        for (int col = 0; col < 3; col++) { inverse[4 * row + col] = (float)r[3 * row + col]; }
+        inverse[4 * row + 3] = (float)(-((r[3 * row] * tx + r[3 * row + 1] * ty) + r[3 * row + 2] * tz));
+    }
+    for (int i = 0; i < 12; i++) { if (!(inverse[i] - inverse[i] == 0.f)) { return false; } }
+    return true;
+}
+
+// leafStep for the two-level tree: the leaf's stored ids plus `base` are the virtual ids the acceptance rule compares
+template <bool COUNT, int ROWS, int STRIDE>
+__device__ inline bool leafStepInstanced(const TraceGeometry &g, const LaneStack &stack, LaneRay &ray, int base, TraceCounters *counters)
+{
+    const int first = ray.pendingLeaf >> 3;
+    const int count = ray.pendingLeaf & 7;
+    ray.pendingLeaf = 0;
+    float4 t0 = g.tris[3 * first + 0];
+    float4 t1 = g.tris[3 * first + 1];
+    float4 t2 = g.tris[3 * first + 2];
+    bool terminate = false;
+    for (int k = 0; k < count; k++) {
+        pinLoaded(t0);
+        pinLoaded(t1);
+        pinLoaded(t2);
+        float4 c0 = t0;
+        const float4 c1 = t1, c2 = t2;
+        if (k + 1 < count) {
+            t0 = g.tris[3 * (first + k + 1) + 0];
+            t1 = g.tris[3 * (first + k + 1) + 1];
+            t2 = g.tris[3 * (first + k + 1) + 2];
+        }
+        if (COUNT) { counters->tris++; }
+        c0.w = intAsFloat(floatAsInt(c0.w) + base);
+        testLeafTriangle(ray, c0, c1, c2, &terminate);
+        if (terminate) { return true; }
+    }
+    return popWork<ROWS, STRIDE>(stack, ray);
+}
+
+// One whole ray through the two-level tree on one lane: innerStep / leafStep with one addition.  On an instance leaf the lane
+// pushes the sentinel, takes the ray into the prototype's space and goes on at the prototype's root; popping the sentinel
+// brings the world ray back (worldO / worldD: the lane reloads it from where the caller read it, so it costs no registers meanwhile).
+// maxStack = the top tree's bound + the deepest prototype's + 1 (the sentinel).
+template <bool COUNT, int ROWS, int STRIDE>
+__device__ inline void traverseInstanced(
+    const TraceGeometry &g, const DInstanceSet &instances, const LaneStack &stack, int maxStack,
+    const float4 *worldO, const float4 *worldD, LaneRay &ray, TraceCounters *counters
+) {
+    if (g.nNodes <= 0) { return; }
+    int base = 0;
+    bool done = false;
+    while (!done) {
+        if (ray.pendingLeaf == 0) {
+            done = innerStep<COUNT, ROWS, STRIDE>(g, stack, maxStack, ray, counters);
+        } else if (ray.pendingLeaf == kInstanceSentinel) {
+            // back in the world: the world ray, its reciprocals, virtual ids = stored ids
+            const float kHuge = 3e30f;
+            const float4 wo = *worldO, wd = *worldD;
+            const V3 o = v3(wo.x, wo.y, wo.z), d = v3(wd.x, wd.y, wd.z);
+            ray.o = o;
+            ray.d = d;
+            ray.invD = v3(fminf(fmaxf(1.f / d.x, -kHuge), kHuge), fminf(fmaxf(1.f / d.y, -kHuge), kHuge), fminf(fmaxf(1.f / d.z, -kHuge), kHuge));
+            ray.oInvD = v3(o.x * ray.invD.x, o.y * ray.invD.y, o.z * ray.invD.z);
+            base = 0;
+            ray.pendingLeaf = 0;
+            done = popWork<ROWS, STRIDE>(stack, ray);
+        } else if (ray.pendingLeaf & kInstanceLeafBit) {
+            const float4 *record = instances.records + (size_t)kInstanceQuads * (ray.pendingLeaf & (kInstanceLeafBit - 1));
+            const float4 i0 = record[3], i1 = record[4], i2 = record[5], ids = record[6];
+            const float inverse[12] = { i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w, i2.x, i2.y, i2.z, i2.w };
+            if (ray.sp < maxStack) { stackWrite<ROWS, STRIDE>(stack, ray.sp, kEmptyChild); ray.sp++; }
+            const float kHuge = 3e30f;
+            const float4 wo = *worldO, wd = *worldD;
+            ray.o = flattenPoint(inverse, v3(wo.x, wo.y, wo.z));
+            ray.d = flattenDirection(inverse, v3(wd.x, wd.y, wd.z));
+            ray.invD = v3(fminf(fmaxf(1.f / ray.d.x, -kHuge), kHuge), fminf(fmaxf(1.f / ray.d.y, -kHuge), kHuge), fminf(fmaxf(1.f / ray.d.z, -kHuge), kHuge));
+            ray.oInvD = v3(ray.o.x * ray.invD.x, ray.o.y * ray.invD.y, ray.o.z * ray.invD.z);
+            base = floatAsInt(ids.x);
+            ray.current = floatAsInt(ids.z);
+            ray.pendingLeaf = 0;
+        } else {
+            done = leafStepInstanced<COUNT, ROWS, STRIDE>(g, stack, ray, base, counters);
+        }
+    }
 }
 
 }  // namespace pathed

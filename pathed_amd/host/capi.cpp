@@ -12,6 +12,7 @@ thread_local std::string g_hostError;
 struct LoadedScene {
     pathed::FlatScene scene;
     PathedSceneDesc desc;
+    PathedInstanceDesc instances;
 };
 }  // namespace
 
@@ -39,6 +40,16 @@ const PathedSceneDesc *pathed_host_scene_desc(void *handle)
 {
     if (!handle) { return nullptr; }
     return &((LoadedScene *)handle)->desc;
+}
+
+// the instanced geometry of a loaded scene (scene_loader.h: FlatScene::prototypes / instances), or null for a flat scene
+const PathedInstanceDesc *pathed_host_scene_instances(void *handle)
+{
+    if (!handle) { return nullptr; }
+    LoadedScene *loaded = (LoadedScene *)handle;
+    if (!loaded->scene.instanced()) { return nullptr; }
+    loaded->instances = loaded->scene.instanceDesc();
+    return &loaded->instances;
 }
 
 // the voxel-grid media of a loaded scene (scene_loader.h: FlatGrid): how many, and grid i with the medium slot it belongs to
@@ -154,6 +165,8 @@ static std::string flatSceneDigest(const pathed::FlatScene &flat)
         add(desc.textures[i].rgb, (size_t)3 * desc.textures[i].width * desc.textures[i].height);
     }
     add(desc.media, sizeof(PathedMedium) * desc.n_media);
+    for (const PathedPrototype &prototype : flat.prototypes) { add(&prototype.first_geom, sizeof(int32_t)); add(&prototype.n_geoms, sizeof(int32_t)); }
+    for (const PathedInstance &instance : flat.instances) { add(&instance.prototype, sizeof(int32_t)); add(instance.transform, sizeof instance.transform); }
     for (const pathed::FlatGrid &grid : flat.grids) {   // the .vol file's bytes as loaded, and what the scene file says about the medium
         add(&grid.medium, sizeof grid.medium);
         add(&grid.desc.cells_x, sizeof(uint32_t)); add(&grid.desc.cells_y, sizeof(uint32_t)); add(&grid.desc.cells_z, sizeof(uint32_t));
@@ -207,6 +220,17 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
         const auto loadBegin = std::chrono::steady_clock::now();
         FlatScene flat = loadScene(job.scene(), width, height, assetRoot);
         const std::string sceneDigest = flatSceneDigest(flat);
+        if (flat.instanced()) {
+            // a scene file with "instance" / "instanced" models: what the library refuses beside instances (include/pathed_hip.h)
+            // stops the job here, by name, before a tree is built or anything is uploaded
+            const std::string name = job.integratorName();
+            if (builder != "auto" && builder != "sah") { throw std::runtime_error("job: \"bvh_builder\": \"" + builder + "\" does not build a scene with instances (\"auto\" or \"sah\")"); }
+            if (!features.empty()) { throw std::runtime_error("job: \"features\" does not go with a scene with instances"); }
+            if (name == "AlbedoIntegrator" || name == "VolumePathTracer" || name == "BasicVolumeIntegrator") {
+                throw std::runtime_error("job: the " + name + " does not render a scene with instances (the PathTracer does)");
+            }
+            builder = "sah";
+        }
         if (builder == "auto") {
             // several replicas of a large mesh: each GPU builds its own tree in milliseconds (PLOC) instead of N host SAH
             // builds competing for the cores before the first sample (include/pathed_hip.h: PATHED_BVH_*)

@@ -135,6 +135,7 @@ void Scene::upload(int bvhBuilderPlusOne)
 {
     m_handles.assign(m_devices.size(), nullptr);
     const PathedSceneDesc desc = m_flat.desc();
+    const PathedInstanceDesc instances = m_flat.instanceDesc();   // scene files with "instance" / "instanced" models
     for (size_t i = 0; i < m_flat.grids.size(); i++) { (void)m_flat.gridDesc(i); }   // (sets the data pointers once, before the replica threads read them)
     try {
         // every device builds / uploads its own replica, in parallel
@@ -145,7 +146,11 @@ void Scene::upload(int bvhBuilderPlusOne)
             options.struct_size = sizeof options;
             options.device = m_devices[r];
             options.bvh_builder = bvhBuilderPlusOne;
-            if (pathed_hip_scene_create_ex(&desc, &options, &m_handles[r]) != PATHED_OK) {
+            if (m_flat.instanced()) {
+                if (pathed_hip_scene_create_instanced(&desc, &options, &instances, &m_handles[r]) != PATHED_OK) {
+                    throw std::runtime_error(hipError("pathed_hip_scene_create_instanced"));
+                }
+            } else if (pathed_hip_scene_create_ex(&desc, &options, &m_handles[r]) != PATHED_OK) {
                 throw std::runtime_error(hipError("pathed_hip_scene_create_ex"));
             }
             for (size_t i = 0; i < m_flat.grids.size(); i++) {   // the scene file's voxel-grid media, each on its medium slot

@@ -20,8 +20,25 @@ namespace {
 
 using MaterialMap = std::map<std::string, int>;
 
+// A prototype while the scene file is read: its meshes (own space), split into the faces that stay in the prototype and the
+// emissive ones that are baked per placement, and the "instanced" models found inside it.
+struct NestedPlacement {
+    int prototype;
+    double transform[12];   // row-major 3 x 4, the floats of the file
+};
+struct PrototypeBuild {
+    std::string name;
+    FlatScene geometry;     // positions / normals / uvs / indices / triMaterial / geoms only
+    std::vector<NestedPlacement> nested;
+};
+
 struct LoaderContext {
     FlatScene *scene;
+    FlatScene *geometry = nullptr;          // where models go: the scene itself, or the prototype being read
+    PrototypeBuild *prototype = nullptr;    // ... that prototype (null: the world)
+    std::vector<PrototypeBuild> prototypes;
+    std::map<std::string, int> prototypeLookup;
+    std::vector<NestedPlacement> worldPlacements;
     std::string assetRoot;
     MaterialMap materialLookup;
     std::map<std::string, int> mediumLookup;   // scene JSON "media" by name -> index into FlatScene::media
@@ -766,9 +783,29 @@ int requireMaterial(int material, const char *what)
     return material;
 }
 
+// "instanced": instance_name + 16 numbers, COLUMN-major as the reference hands them to Embree (src/scene_parser.cpp:461-480):
+// element 4 c + r is row r, column c; the translation is elements 12..14
+NestedPlacement parseInstanced(const Json &model, LoaderContext &context)
+{
+    const std::string name = model["instance_name"].isString() ? model["instance_name"].asString() : "";
+    auto found = context.prototypeLookup.find(name);
+    if (found == context.prototypeLookup.end()) { throw SceneLoadError("instanced: unknown instance_name \"" + name + "\""); }
+    if (!model["transform"].isArray() || model["transform"].elements().size() != 16) {
+        throw SceneLoadError("instanced \"" + name + "\": transform must be an array of 16 numbers (column-major)");
+    }
+    float columnMajor[16];
+    for (int i = 0; i < 16; i++) { columnMajor[i] = parseFloat(model["transform"].elements()[(size_t)i], "instanced transform"); }
+    NestedPlacement placement;
+    placement.prototype = found->second;
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 4; c++) { placement.transform[4 * r + c] = (double)columnMajor[4 * c + r]; }
+    }
+    return placement;
+}
+
 void parseModels(const Json &models, LoaderContext &context)
 {
-    FlatScene &scene = *context.scene;
+    FlatScene &scene = *context.geometry;
     for (const Json &model : models.elements()) {
         if (parseBool(model["skip"], false)) { continue; }
         const std::string type = model["type"].isString() ? model["type"].asString() : "";
@@ -806,6 +843,34 @@ void parseModels(const Json &models, LoaderContext &context)
                 else { throw SceneLoadError("Unsupported axis: " + axis); }
             }
             appendMesh(scene, makeQuad(transform, material, zUp), -1);
+        } else if (type == "sphere" && context.prototype) {
+            throw SceneLoadError("instance \"" + context.prototype->name + "\": a sphere inside an instance is not supported (obj, ply, quad and instanced are)");
+        } else if (type == "instance") {
+            // reference parseInstance (src/scene_parser.cpp:231-249): the models go to a scene of their own, known by name
+            if (!model["name"].isString()) { throw SceneLoadError("instance: needs a string \"name\""); }
+            PrototypeBuild build;
+            build.name = model["name"].asString();
+            FlatScene *outerGeometry = context.geometry;
+            PrototypeBuild *outerPrototype = context.prototype;
+            context.geometry = &build.geometry;
+            context.prototype = &build;
+            parseModels(model["models"], context);
+            context.geometry = outerGeometry;
+            context.prototype = outerPrototype;
+            context.prototypeLookup[build.name] = (int)context.prototypes.size();
+            context.prototypes.push_back(std::move(build));
+        } else if (type == "instanced") {
+            const NestedPlacement placement = parseInstanced(model, context);
+            if (context.prototype) {
+                // the reference nests two levels at most (src/rtc_manager.cpp:46)
+                if (!context.prototypes[(size_t)placement.prototype].nested.empty()) {
+                    throw SceneLoadError("instance \"" + context.prototype->name + "\": instances nest two levels at most (\""
+                                         + context.prototypes[(size_t)placement.prototype].name + "\" holds instances itself)");
+                }
+                context.prototype->nested.push_back(placement);
+            } else {
+                context.worldPlacements.push_back(placement);
+            }
         } else if (type == "sphere") {
             PathedSphere sphere;
             sphere.material = requireMaterial(parseMaterial(model["bsdf"], context), "sphere");
@@ -821,14 +886,143 @@ void parseModels(const Json &models, LoaderContext &context)
             geom.medium = medium;
             scene.geoms.push_back(geom);
             scene.spheres.push_back(sphere);
-        } else if (type == "instance" || type == "instanced" || type == "pbrt-curve" || type == "b-spline") {
+        } else if (type == "pbrt-curve" || type == "b-spline") {
             throw SceneLoadError("Unsupported model type (outside hot-path scope, SURVEY.md §2 #3/#16): " + type);
         }
         // unknown types are ignored, as the reference's if-chain does
     }
 }
 
+bool emitsLight(const PathedMaterial &material) { return !(material.emit[0] == 0.f && material.emit[1] == 0.f && material.emit[2] == 0.f); }
+
+// the faces of `source` that do (emissive = true) or do not emit, as one mesh
+MeshBuffers selectFaces(const FlatScene &source, const std::vector<PathedMaterial> &materials, bool emissive)
+{
+    MeshBuffers mesh;
+    mesh.positions = source.positions;
+    mesh.normals = source.normals;
+    mesh.uvs = source.uvs;
+    for (size_t i = 0; i < source.triMaterial.size(); i++) {
+        if (emitsLight(materials[(size_t)source.triMaterial[i]]) != emissive) { continue; }
+        for (int k = 0; k < 3; k++) { mesh.indices.push_back(source.indices[3 * i + k]); }
+        mesh.faceMaterial.push_back(source.triMaterial[i]);
+    }
+    return mesh;
+}
+
+// After the world's models: every placement of the file as one-level placements (nesting composed in double, rounded once),
+// the prototypes' emissive faces baked into world triangles per placement, then the prototypes' geoms as the LAST geoms.
+void finishInstances(LoaderContext &context)
+{
+    FlatScene &scene = *context.scene;
+    if (context.prototypes.empty()) { return; }
+    struct Placement { int prototype; float transform[12]; };
+    std::vector<Placement> placements;
+    auto rounded = [](int prototype, const double *transform) {
+        Placement placement;
+        placement.prototype = prototype;
+        for (int i = 0; i < 12; i++) { placement.transform[i] = (float)transform[i]; }
+        return placement;
+    };
+    for (const NestedPlacement &outer : context.worldPlacements) {
+        placements.push_back(rounded(outer.prototype, outer.transform));
+        for (const NestedPlacement &inner : context.prototypes[(size_t)outer.prototype].nested) {
+            double composed[12];
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 4; c++) {
+                    double sum = 0.0;
+                    for (int k = 0; k < 3; k++) { sum += outer.transform[4 * r + k] * inner.transform[4 * k + c]; }
+                    composed[4 * r + c] = sum + (c == 3 ? outer.transform[4 * r + 3] : 0.0);
+                }
+            }
+            placements.push_back(rounded(inner.prototype, composed));
+        }
+    }
+    // emissive faces: ordinary world triangles and ordinary lights, once per placement
+    std::vector<MeshBuffers> emissive, plain;
+    for (const PrototypeBuild &build : context.prototypes) {
+        emissive.push_back(selectFaces(build.geometry, scene.materials, true));
+        plain.push_back(selectFaces(build.geometry, scene.materials, false));
+    }
+    for (const Placement &placement : placements) {
+        const MeshBuffers &source = emissive[(size_t)placement.prototype];
+        if (source.indices.empty()) { continue; }
+        float inverse[12];
+        if (!instanceInverse(placement.transform, inverse)) { throw SceneLoadError("instanced \"" + context.prototypes[(size_t)placement.prototype].name + "\": the transform is not invertible"); }
+        MeshBuffers baked = source;
+        for (size_t v = 0; v < source.positions.size() / 3; v++) {
+            flattenInstancePoint(placement.transform, &source.positions[3 * v], &baked.positions[3 * v]);
+            if (3 * v + 2 < source.normals.size()) { flattenInstanceNormal(inverse, &source.normals[3 * v], &baked.normals[3 * v]); }
+        }
+        appendMesh(scene, baked, -1);
+    }
+    // the prototypes: what is left of each, as the last geoms; one without such faces is not a prototype of the ABI
+    std::vector<int> abiIndex(context.prototypes.size(), -1);
+    for (size_t p = 0; p < context.prototypes.size(); p++) {
+        if (plain[p].indices.empty()) { continue; }
+        PathedPrototype prototype;
+        prototype.first_geom = (int32_t)scene.geoms.size();
+        prototype.n_geoms = 1;
+        appendMesh(scene, plain[p], -1);
+        abiIndex[p] = (int)scene.prototypes.size();
+        scene.prototypes.push_back(prototype);
+        scene.prototypeNames.push_back(context.prototypes[p].name);
+    }
+    for (const Placement &placement : placements) {
+        if (abiIndex[(size_t)placement.prototype] < 0) { continue; }
+        PathedInstance instance;
+        instance.prototype = abiIndex[(size_t)placement.prototype];
+        std::memcpy(instance.transform, placement.transform, sizeof instance.transform);
+        scene.instances.push_back(instance);
+    }
+}
+
 }  // namespace
+
+void flattenInstancePoint(const float *m, const float *p, float *out)
+{
+    const float x = p[0], y = p[1], z = p[2];
+    out[0] = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
+    out[1] = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
+    out[2] = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+}
+
+void flattenInstanceNormal(const float *inverse, const float *n, float *out)
+{
+    const float x = n[0], y = n[1], z = n[2];
+    out[0] = (inverse[0] * x + inverse[4] * y) + inverse[8] * z;
+    out[1] = (inverse[1] * x + inverse[5] * y) + inverse[9] * z;
+    out[2] = (inverse[2] * x + inverse[6] * y) + inverse[10] * z;
+}
+
+bool instanceInverse(const float *m, float *inverse)
+{
+    const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], k = m[10];
+    const double c00 = e * k - f * h, c01 = c * h - b * k, c02 = b * f - c * e;
+    const double c10 = f * g - d * k, c11 = a * k - c * g, c12 = c * d - a * f;
+    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
+    const double det = (a * c00 + b * c10) + c * c20;
+    if (!(det != 0.0) || !(det - det == 0.0)) { return false; }
+    const double r[9] = { c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det };
+    const double tx = m[3], ty = m[7], tz = m[11];
+    for (int row = 0; row < 3; row++) {
+        for (int col = 0; col < 3; col++) { inverse[4 * row + col] = (float)r[3 * row + col]; }
+        inverse[4 * row + 3] = (float)(-((r[3 * row] * tx + r[3 * row + 1] * ty) + r[3 * row + 2] * tz));
+    }
+    for (int i = 0; i < 12; i++) { if (!(inverse[i] - inverse[i] == 0.f)) { return false; } }
+    return true;
+}
+
+PathedInstanceDesc FlatScene::instanceDesc() const
+{
+    PathedInstanceDesc out;
+    out.struct_size = (uint32_t)sizeof(PathedInstanceDesc);
+    out.n_prototypes = (uint32_t)prototypes.size();
+    out.prototypes = prototypes.data();
+    out.n_instances = (uint32_t)instances.size();
+    out.instances = instances.data();
+    return out;
+}
 
 PathedMaterial makeLambertian(const float diffuse[3], const float emit[3])
 {
@@ -927,6 +1121,7 @@ FlatScene loadScene(
     FlatScene scene;
     LoaderContext context;
     context.scene = &scene;
+    context.geometry = &scene;
     context.assetRoot = assetRoot;
 
     Json json;
@@ -997,6 +1192,7 @@ FlatScene loadScene(
     }
 
     parseModels(json["models"], context);
+    finishInstances(context);
 
     // environment light: scene_parser.cpp:540-553
     const Json &envJson = json["environmentLight"];

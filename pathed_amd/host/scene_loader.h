@@ -66,6 +66,18 @@ struct FlatScene {
     std::vector<std::vector<uint8_t>> textureData;
     std::map<std::string, int> textureByPath;
 
+    // Instanced geometry (scene JSON "instance" / "instanced", reference src/scene_parser.cpp:231-249, 449-492), ONE level:
+    // a prototype is a run of the LAST geoms (its meshes, in its own space), a placement one prototype under a row-major
+    // 3 x 4 transform.  Nesting is resolved here: an "instanced" inside an "instance" becomes, for every placement of the
+    // outer prototype, a placement of the inner one under the composed transform (formed in double, rounded once to float).
+    // Emissive faces of a prototype are BAKED: per placement they are ordinary world triangles (flattenInstancePoint /
+    // flattenInstanceNormal below), after the scene's other world geoms, and ordinary lights.
+    std::vector<PathedPrototype> prototypes;
+    std::vector<std::string> prototypeNames;
+    std::vector<PathedInstance> instances;
+    bool instanced() const { return !prototypes.empty() || !instances.empty(); }
+    PathedInstanceDesc instanceDesc() const;
+
     // valid as long as this FlatScene is alive and unmodified
     PathedSceneDesc desc() const;
     // grid i ready for pathed_hip_scene_set_grid_medium (same lifetime rule)
@@ -85,6 +97,13 @@ FlatScene loadScene(
 );
 
 PathedMaterial makeLambertian(const float diffuse[3], const float emit[3]);
+
+// The flatten routine of include/pathed_hip.h (PathedInstanceDesc), fp32, one rounding per operation, in the operation order
+// the device applies to a prototype's shading record (pathed_amd/csrc/trace.h) and pathed_amd.flatten_instances applies in
+// numpy: transform / inverse are row-major 3 x 4; instanceInverse forms the inverse in double by cofactors and rounds once.
+void flattenInstancePoint(const float *transform, const float *point, float *out);
+void flattenInstanceNormal(const float *inverse, const float *normal, float *out);
+bool instanceInverse(const float *transform, float *inverse);
 
 // The text layer under the OBJ / MTL readers, exposed so the tests can hold it against the reference's own
 // tokenizer and MtlParser (src/string_util.cpp:7-38, src/mtl_parser.cpp:16-113; test/string_util_test.cpp:9-37).

@@ -1,0 +1,154 @@
+"""Instanced geometry on the Python side: the description HipScene hands pathed_hip_scene_create_instanced, and
+`flatten_instances`, the shared definition of "the same scene, flattened".
+
+A scene with instances is a PathedSceneDesc whose last geoms are PROTOTYPES (meshes in their own space, not placed in the
+world) plus a list of placements, each one prototype under an affine 3 x 4 transform (include/pathed_hip.h:
+PathedInstanceDesc).  Primitive ids are virtual: world triangles [0, T0), then placement k's triangles in placement order.
+
+The flatten routine is the one of the header, operation for operation in float32 (numpy rounds every operation once and
+fuses nothing): the device applies the same statements to the prototype's shading record when a ray hits a placement, so
+the flattened scene and the instanced scene shade a hit (t, u, v, prim) to the same floats.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+
+
+def _f32(value):
+    return np.asarray(value, dtype=np.float32)
+
+
+def instance_inverse(transform):
+    """The inverse of a row-major 3 x 4 transform: cofactors in float64 from the float32 entries, rounded once to float32
+    (pathed_amd/csrc/trace.h: instanceInverse, the same operations in the same order)."""
+    m = _f32(transform).reshape(12).astype(np.float64)
+    a, b, c, tx, d, e, f, ty, g, h, k, tz = (m[i] for i in range(12))
+    c00, c01, c02 = e * k - f * h, c * h - b * k, b * f - c * e
+    c10, c11, c12 = f * g - d * k, a * k - c * g, c * d - a * f
+    c20, c21, c22 = d * h - e * g, b * g - a * h, a * e - b * d
+    det = (a * c00 + b * c10) + c * c20
+    if not (det != 0.0 and np.isfinite(det)):
+        raise ValueError("instance transform is not invertible")
+    r = [c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det]
+    out = np.zeros(12, dtype=np.float32)
+    for row in range(3):
+        for col in range(3):
+            out[4 * row + col] = np.float32(r[3 * row + col])
+        out[4 * row + 3] = np.float32(-((r[3 * row] * tx + r[3 * row + 1] * ty) + r[3 * row + 2] * tz))
+    return out
+
+
+def flatten_points(transform, points):
+    """x' = ((m[0] x + m[1] y) + m[2] z) + m[3], ... in float32, for (n, 3) float32 points."""
+    m = _f32(transform).reshape(12)
+    p = _f32(points).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3] for r in range(3)], axis=1).astype(np.float32)
+
+
+def flatten_normals(inverse, normals):
+    """n' = inverse-transpose times n, x' = ((i[0] x + i[4] y) + i[8] z), ... in float32; not renormalised."""
+    i = _f32(inverse).reshape(12)
+    n = _f32(normals).reshape(-1, 3)
+    x, y, z = n[:, 0], n[:, 1], n[:, 2]
+    return np.stack([(i[c] * x + i[4 + c] * y) + i[8 + c] * z for c in range(3)], axis=1).astype(np.float32)
+
+
+class InstanceSet:
+    """Prototypes [(first_geom, n_geoms), ...] and placements [(prototype, 12 floats row-major 3 x 4), ...] as the
+    PathedInstanceDesc of the C ABI; keeps its arrays alive."""
+
+    def __init__(self, prototypes, instances):
+        self.prototypes = [(int(first), int(count)) for first, count in prototypes]
+        self.instances = [(int(prototype), _f32(transform).reshape(12).copy()) for prototype, transform in instances]
+        self._prototype_array = (_capi.PathedPrototype * max(1, len(self.prototypes)))()
+        for slot, (first, count) in zip(self._prototype_array, self.prototypes):
+            slot.first_geom, slot.n_geoms = first, count
+        self._instance_array = (_capi.PathedInstance * max(1, len(self.instances)))()
+        for slot, (prototype, transform) in zip(self._instance_array, self.instances):
+            slot.prototype = prototype
+            slot.transform[:] = transform.tolist()
+        self.desc = _capi.PathedInstanceDesc()
+        self.desc.struct_size = C.sizeof(_capi.PathedInstanceDesc)
+        self.desc.n_prototypes, self.desc.prototypes = len(self.prototypes), self._prototype_array
+        self.desc.n_instances, self.desc.instances = len(self.instances), self._instance_array
+
+
+class FlattenedScene:
+    """What flatten_instances returns: `.desc` is a pointer to a flat PathedSceneDesc (it shares the camera, materials,
+    textures and environment of the description it came from, which must outlive it); `.bases` the virtual-id base of every
+    placement and, last, the triangle count."""
+
+    def __init__(self):
+        self.desc = None
+        self.bases = None
+        self._keep = []
+
+
+def flatten_instances(desc_pointer, prototypes, instances):
+    """The flat description of an instanced scene: the world's triangles, then every placement's triangles written out as
+    world triangles by the flatten routine, in placement order -- the triangle at index i is the one the instanced scene
+    reports as primitive i.  Each placement becomes one mesh geom after the world's geoms."""
+    source = desc_pointer.contents
+    instance_set = instances if isinstance(instances, InstanceSet) else InstanceSet(prototypes, instances)
+    n_vertices, n_triangles = int(source.n_vertices), int(source.n_triangles)
+    positions = np.ctypeslib.as_array(source.positions, shape=(n_vertices, 3)) if n_vertices else np.zeros((0, 3), np.float32)
+    normals = np.ctypeslib.as_array(source.normals, shape=(n_vertices, 3)) if n_vertices else np.zeros((0, 3), np.float32)
+    uvs = np.ctypeslib.as_array(source.uvs, shape=(n_vertices, 2)) if n_vertices else np.zeros((0, 2), np.float32)
+    indices = np.ctypeslib.as_array(source.indices, shape=(n_triangles, 3)) if n_triangles else np.zeros((0, 3), np.uint32)
+    tri_material = np.ctypeslib.as_array(source.tri_material, shape=(n_triangles,)) if n_triangles else np.zeros(0, np.int32)
+    geoms = [source.geoms[g] for g in range(int(source.n_geoms))]
+
+    first_prototype_geom = instance_set.prototypes[0][0] if instance_set.prototypes else len(geoms)
+    world_triangles = geoms[first_prototype_geom].first if first_prototype_geom < len(geoms) else n_triangles
+    ranges = []
+    for first_geom, n_geoms in instance_set.prototypes:
+        first = geoms[first_geom].first
+        ranges.append((first, sum(geoms[first_geom + g].count for g in range(n_geoms))))
+
+    out_positions, out_normals, out_uvs = [positions.copy()], [normals.copy()], [uvs.copy()]
+    out_indices, out_materials = [indices[:world_triangles].copy()], [tri_material[:world_triangles].copy()]
+    out_geoms = [_capi.PathedGeom(g.type, g.first, g.count, g.medium) for g in geoms[:first_prototype_geom]]
+    vertex_base, triangle_base, bases = n_vertices, world_triangles, []
+    for prototype, transform in instance_set.instances:
+        first, count = ranges[prototype]
+        triangles = indices[first:first + count].astype(np.int64)
+        low, high = int(triangles.min()), int(triangles.max()) + 1
+        inverse = instance_inverse(transform)
+        out_positions.append(flatten_points(transform, positions[low:high]))
+        out_normals.append(flatten_normals(inverse, normals[low:high]))
+        out_uvs.append(uvs[low:high].copy())
+        out_indices.append((triangles - low + vertex_base).astype(np.uint32))
+        out_materials.append(tri_material[first:first + count].copy())
+        out_geoms.append(_capi.PathedGeom(_capi.GEOM_MESH, triangle_base, count, -1))
+        bases.append(triangle_base)
+        vertex_base += high - low
+        triangle_base += count
+    bases.append(triangle_base)
+
+    flat = FlattenedScene()
+    flat.bases = np.asarray(bases, dtype=np.int64)
+    desc = _capi.PathedSceneDesc()
+    C.memmove(C.byref(desc), C.byref(source), C.sizeof(_capi.PathedSceneDesc))   # camera, materials, textures, environment, media
+    arrays = {
+        "positions": np.ascontiguousarray(np.concatenate(out_positions), dtype=np.float32),
+        "normals": np.ascontiguousarray(np.concatenate(out_normals), dtype=np.float32),
+        "uvs": np.ascontiguousarray(np.concatenate(out_uvs), dtype=np.float32),
+        "indices": np.ascontiguousarray(np.concatenate(out_indices), dtype=np.uint32),
+        "tri_material": np.ascontiguousarray(np.concatenate(out_materials), dtype=np.int32),
+    }
+    flat.positions, flat.indices = arrays["positions"], arrays["indices"]
+    desc.n_vertices = len(arrays["positions"])
+    desc.positions = arrays["positions"].ctypes.data_as(C.POINTER(C.c_float))
+    desc.normals = arrays["normals"].ctypes.data_as(C.POINTER(C.c_float))
+    desc.uvs = arrays["uvs"].ctypes.data_as(C.POINTER(C.c_float))
+    desc.n_triangles = len(arrays["indices"])
+    desc.indices = arrays["indices"].ctypes.data_as(C.POINTER(C.c_uint32))
+    desc.tri_material = arrays["tri_material"].ctypes.data_as(C.POINTER(C.c_int32))
+    geom_array = (_capi.PathedGeom * max(1, len(out_geoms)))(*out_geoms)
+    desc.n_geoms, desc.geoms = len(out_geoms), geom_array
+    flat._keep = [arrays, geom_array, desc, desc_pointer, instance_set]
+    flat.desc = C.pointer(desc)
+    return flat

@@ -81,11 +81,14 @@ class HipScene:
     trace_blocks_per_cu, shade_kernel ("auto" | "per-slot" | "staged" | "fused" | "split" | "wave" | "hybrid"), stage_slots,
     unit_order ("auto" | "stripes" | "stripes-tiled" | "tiles"), node_format ("auto" | "wide" | "compressed" | "compressed8"), small_phase1 ("auto" | "valu" | "mfma").  `device=None` keeps the device of an earlier pathed_hip_init.
     `grids`: (medium slot, _capi.PathedGridMedium) pairs set on the created scene (LoadedScene.grids; see set_grid_medium).
+    `prototypes`, `instances`: instanced geometry (pathed_hip_scene_create_instanced) -- prototypes [(first geom, geoms), ...]
+    naming the description's last geoms, instances [(prototype, 12 floats: row-major 3 x 4), ...], or an instances.InstanceSet
+    as `instances`; hits then carry virtual primitive ids, those of pathed_amd.flatten_instances of the same arguments.
     """
 
     BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2}  # PATHED_BVH_SAH_HOST / _LBVH_DEVICE / _PLOC_DEVICE
 
-    def __init__(self, desc_pointer, device=None, bvh_builder="sah", grids=(), **options):
+    def __init__(self, desc_pointer, device=None, bvh_builder="sah", grids=(), prototypes=None, instances=None, **options):
         self._lib = _capi.load_hip()
         packed = _capi.PathedSceneOptions()
         packed.struct_size = C.sizeof(_capi.PathedSceneOptions)
@@ -104,8 +107,14 @@ class HipScene:
         if options:
             raise TypeError("unknown scene options: %s" % sorted(options))
         handle = C.c_void_p()
-        _check(self._lib, self._lib.pathed_hip_scene_create_ex(desc_pointer, C.byref(packed), C.byref(handle)),
-               "pathed_hip_scene_create_ex")
+        if instances is not None or prototypes is not None:
+            from .instances import InstanceSet
+            self.instance_set = instances if isinstance(instances, InstanceSet) else InstanceSet(prototypes or (), instances or ())
+            _check(self._lib, self._lib.pathed_hip_scene_create_instanced(desc_pointer, C.byref(packed), C.byref(self.instance_set.desc), C.byref(handle)),
+                   "pathed_hip_scene_create_instanced")
+        else:
+            _check(self._lib, self._lib.pathed_hip_scene_create_ex(desc_pointer, C.byref(packed), C.byref(handle)),
+                   "pathed_hip_scene_create_ex")
         self._handle = handle
         self.device = int(self._lib.pathed_hip_scene_device(handle))
         self.width = int(desc_pointer.contents.camera.width)

@@ -94,7 +94,7 @@ def main(argv=None):
         raise SystemExit("spp_per_launch must be >= 1")
 
     scene = LoadedScene(job["scene"], width, height, asset_root if asset_root is not None else job.get("asset_root"))
-    gpu = HipScene(scene.desc, device=local_rank, grids=scene.grids, bvh_builder=(lambda name: ("ploc" if world_size > 1 and scene.n_triangles > 1000000 else "sah") if name == "auto" else name)(job.get("bvh_builder", "auto")))
+    gpu = HipScene(scene.desc, device=local_rank, grids=scene.grids, prototypes=scene.prototypes, instances=scene.instances, bvh_builder=(lambda name: ("ploc" if world_size > 1 and scene.n_triangles > 1000000 else "sah") if name == "auto" else name)(job.get("bvh_builder", "auto")))
     gpu.set_integrator(job["integrator"])
     host = _capi.load_host()
     stream = torch.cuda.current_stream().cuda_stream

@@ -21,6 +21,14 @@ class LoadedScene:
             slot = C.c_int(-1)
             grid = self._host.pathed_host_scene_grid(self._handle, i, C.byref(slot))
             self.grids.append((slot.value, grid.contents))
+        # "instance" / "instanced" models: (prototypes, instances) as HipScene(..., prototypes=, instances=) and
+        # pathed_amd.flatten_instances take them -- one level, nesting resolved and emissive faces baked by the loader; None = flat
+        self.prototypes, self.instances = None, None
+        found = self._host.pathed_host_scene_instances(self._handle)
+        if found:
+            described = found.contents
+            self.prototypes = [(described.prototypes[i].first_geom, described.prototypes[i].n_geoms) for i in range(described.n_prototypes)]
+            self.instances = [(described.instances[i].prototype, [float(x) for x in described.instances[i].transform]) for i in range(described.n_instances)]
         self.width = width
         self.height = height
 
