@@ -643,6 +643,17 @@ int pathed_hip_trace(PathedScene *scene, const float *rays, size_t n,
  * Phase 1 is correct iff accepted is a subset of candidates for every ray. */
 int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out);
 
+/* Test hook onto the per-pixel candidate masks of the camera rays (scenes on the fused path kernel only; built at scene
+ * creation and again by pathed_hip_scene_set_camera, pathed_amd/csrc/camera_masks.h).
+ * out: n_pixels x uint64, row-major pixels, host memory; n_pixels must be width * height.  Bit 63 - k = triangle k of the
+ *      ITEM order (the order phase 2 of the fused kernel indexes; pathed_hip_debug_item_order maps it to primitive ids).
+ * The masks are correct iff, for every ray through a pixel's footprint, what phase 2 accepts is a subset of the pixel's mask. */
+int pathed_hip_debug_camera_masks(PathedScene *scene, uint64_t *out, size_t n_pixels);
+
+/* The item order of a scene of <= 64 triangles: primitives[k] = original primitive id of item-order triangle k.
+ * n_triangles must be the scene's triangle count. */
+int pathed_hip_debug_item_order(PathedScene *scene, int32_t *primitives, size_t n_triangles);
+
 /* Test hook onto the records that hold per-triangle and per-light constants of the shading code (built on the device at scene
  * creation and again by a refit), next to what the per-vertex functions compute for the same triangles.
  * triangles: n_triangles * 20 floats, host memory, per primitive

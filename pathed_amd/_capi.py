@@ -254,6 +254,8 @@ HIP_SYMBOLS = [
     "pathed_hip_render_pixels_device",
     "pathed_hip_trace",
     "pathed_hip_debug_small_candidates",
+    "pathed_hip_debug_camera_masks",
+    "pathed_hip_debug_item_order",
     "pathed_hip_debug_light_records",
     "pathed_hip_has_experiments",
     "pathed_hip_scene_refit",
@@ -381,6 +383,11 @@ def load_hip():
     lib.pathed_hip_debug_small_candidates.restype = C.c_int
     lib.pathed_hip_debug_light_records.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int)]
     lib.pathed_hip_debug_light_records.restype = C.c_int
+    if hasattr(lib, "pathed_hip_debug_camera_masks"):   # (an older build of the same ABI, as above)
+        lib.pathed_hip_debug_camera_masks.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t]
+        lib.pathed_hip_debug_camera_masks.restype = C.c_int
+        lib.pathed_hip_debug_item_order.argtypes = [vp, C.POINTER(C.c_int32), C.c_size_t]
+        lib.pathed_hip_debug_item_order.restype = C.c_int
     if hasattr(lib, "pathed_hip_debug_shading_queries"):   # (an older build of the same ABI, as above)
         lib.pathed_hip_debug_shading_queries.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.pathed_hip_debug_shading_queries.restype = C.c_int

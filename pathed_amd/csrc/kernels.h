@@ -35,6 +35,7 @@
 #endif
 #include "mfma_candidates.h"
 #include "small_items.h"
+#include "camera_masks.h"
 #include "shading.h"
 #include "trace.h"
 #include "volume.h"
@@ -215,7 +216,8 @@ struct RenderParams {
     // sphere of radius -1 that no ray touches): phase 1 of the sphere queries (smallSphereCandidates)
     float spherePairs[8][4][2];   // [pair][component][half], kBruteForceMaxSpheres / 2 pairs
     float smallKappaT;        // ... and the absolute slack of their t bounds per det^2
-    float4 *cameraQueue;      // k_path_small: per wave of the grid kCameraQueueWords float4 of started samples (the camera queue);
+    float4 *cameraQueue;      // k_path_small: per wave of the grid kCameraQueueWords float4 of started samples (the camera queue),
+                              // and AHEAD of it the per-pixel candidate masks of the camera rays (cameraMasks(), camera_masks.h);
                               // a list pass (kOrderList, wavefront kernels): the pixel list, uint32 (pixelList())
     const float *mfmaTable;   // k_path_small<.., MFMA>: the A-side rows of the matrix-pipe phase 1 (mfma_candidates.h), kMfmaTableFloats
     MfmaFrame mfmaFrame;
@@ -239,6 +241,28 @@ static const int kMaxLocalTris = 8;
 // k_path_small's camera queue: entries per wave (two refills of 64: a power of two), float4 per wave
 static const unsigned int kCameraQueueEntries = 128u;
 static const size_t kCameraQueueWords = 3 * (size_t)kCameraQueueEntries;
+// ... and the candidate masks of its camera rays (camera_masks.h), one uint64 per pixel, in the same allocation AHEAD of the
+// queues: RenderParams gains no field (THE UNIT ORDER, below, on what a change of its layout does to three dozen kernels).
+// The pixel count is rounded up to even so that the queues stay 16-byte aligned.
+__host__ __device__ inline size_t cameraMaskWords(int nPixels) { return ((size_t)(nPixels > 0 ? nPixels : 0) + 1u) & ~(size_t)1u; }
+__device__ inline const unsigned long long *cameraMasks(const RenderParams &p)
+{
+    return reinterpret_cast<const unsigned long long *>(p.cameraQueue) - cameraMaskWords(p.nPixels);
+}
+
+// One thread per pixel (and one for the padding word): the pixel's cone against every item-order triangle, in double precision.
+__global__ __launch_bounds__(256) void k_build_camera_masks(DCamera camera, const float4 *itemTris, int nTris, int nPixels, unsigned long long *masks)
+{
+    const size_t index = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (index >= cameraMaskWords(nPixels)) { return; }
+    unsigned long long mask = 0ull;
+    if (index < (size_t)nPixels && nTris > 0) {
+        const int row = (int)(index / (size_t)camera.resX), col = (int)(index - (size_t)row * (size_t)camera.resX);
+        const PixelCone cone = pixelCone(camera.origin, camera.m, camera.filmWidth, camera.filmHeight, camera.resX, camera.resY, row, col);
+        mask = pixelMask(cone, reinterpret_cast<const float *>(itemTris), nTris);
+    }
+    masks[index] = mask;
+}
 
 // BounceController, reference src/bounce_controller.cpp:14-25
 __device__ inline bool checkDone(int lastBounce, int bounce)
@@ -3211,10 +3235,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
 
     // ---- the wave's camera queue: a ring of kCameraQueueEntries started samples in HBM, three float4 each ([part][entry]):
     // (direction, t), (u, v, prim, unit or partial index), (k0, k1 of the sample's random stream).  A camera ray's hit depends
-    // on (pixel, sample) alone, so the wave starts 64 units at a time at full width -- unit bookkeeping, key, camera ray, a
-    // primary-ray-only pass over the triangles -- ahead of need, and a lane whose sample ended takes a finished camera hit
-    // instead of starting a ray a sixth of a wave wide.  Only this wave touches its entries: a workgroup-scope fence after the
-    // writes and before the reads orders them.  Head, count and unitsLeft are wave-uniform.
+    // on (pixel, sample) alone, so the wave starts 64 units at a time at full width -- unit bookkeeping, key, camera ray, the
+    // pixel's candidate mask (the counting instantiations: a primary-ray-only pass over the triangles), phase 2 -- ahead of
+    // need, and a lane whose sample ended takes a finished camera hit instead of starting a ray a sixth of a wave wide.  Only
+    // this wave touches its entries: a workgroup-scope fence after the writes and before the reads orders them.  Head, count
+    // and unitsLeft are wave-uniform.
     float4 *const cameraQueue = p.cameraQueue + (size_t)waveId * kCameraQueueWords;
     unsigned int queueHead = 0u, queueCount = 0u;
     bool unitsLeft = true;           // UnitTaker::take has not yet come back short
@@ -3256,15 +3281,27 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
             Rng cameraRandom;
             cameraRandom.k0 = 0u; cameraRandom.k1 = 0u; cameraRandom.dimension = 0u;
             V3 cameraO = v3(0.f, 0.f, 0.f), cameraD = v3(0.f, 0.f, 1.f);
+            // The candidates of a camera ray come from the pixel's mask (camera_masks.h: every triangle a ray through the pixel's
+            // footprint can meet; 8 bytes per lane, a batch of the default unit order reads 64 consecutive pixels), not from a pass
+            // over the records.  The counting instantiations keep that pass: their counts stay the per-slot path's, and the
+            // library carries a reference for the masks inside itself (GPU test: the two render the same bytes).
+            constexpr bool kMasks = !COUNT && !MFMA;
+            uint32_t unitPixel = 0u;
             if (got) {
-                uint32_t unitPixel, unitFirst, unitEnd;
+                uint32_t unitFirst, unitEnd;
                 unitSamples(p, newUnit, &unitPixel, &unitFirst, &unitEnd);
                 cameraSampleRay(p, seed, unitPixel, unitFirst, cameraRandom, &cameraO, &cameraD);
             }
             LaneRay cameraHit;
             laneRayInit(cameraHit, cameraO, cameraD, PATHED_TNEAR, PATHED_TFAR, false);
             unsigned int candidatesLow = 0, candidatesHigh = 0;
-            if (got) {
+            if (kMasks) {
+                if (got) {
+                    const unsigned long long pixelCandidates = cameraMasks(p)[unitPixel];
+                    candidatesLow = (unsigned int)(pixelCandidates >> 32);
+                    candidatesHigh = (unsigned int)pixelCandidates;
+                }
+            } else if (got) {
                 if (QUADS || MFMA) {
                     unsigned int unusedLow = 0, unusedHigh = 0;
                     smallCandidatesItems<false, true, true>(smallTris.data, p.smallQuads, nTris, p.smallKappaT, cameraO, cameraD, cameraD,

@@ -218,7 +218,11 @@ struct PathedScene {
     std::vector<DGrid> gridsHost;
     std::vector<std::vector<float>> gridCells;   // per grid
     DeviceBuffer<int> volumeOverflow;   // the volume kernel's traversal-stack spill, per thread
-    DeviceBuffer<float4> cameraQueue;   // the fused kernel's started samples, per wave of its largest grid (kernels.h: the camera queue)
+    // the fused kernel's per-pixel camera-ray candidate masks (camera_masks.h), then its started samples, per wave of its largest
+    // grid (kernels.h: the camera queue)
+    DeviceBuffer<float4> cameraQueue;
+    bool cameraMasksBuilt = false;
+    double cameraMaskMs = 0.0;          // device time of the last build (HIP events)
 
     // render state, allocated on first use
     int nSlots = 0;               // capacity of the per-slot state buffers
@@ -1276,6 +1280,44 @@ static hipError_t rebuildSmallItems(PathedScene *scene)
     return status;
 }
 
+// The fused kernel's camera-ray candidate masks (camera_masks.h) live in the camera queues' allocation, ahead of the queues:
+// this sizes it and builds them on the device.  They depend on (item-order triangles, camera, resolution): built at
+// scene_create, again when the camera moves (after rebuildSmallItems: the item order is its), and by renderPassFused should
+// the allocation ever be found too small.  PATHED_DEBUG_STATS=1 reports the last build's device time with the statistics.
+static size_t cameraQueueWords(const PathedScene *scene)
+{
+    const size_t queueBlocks = (size_t)(scene->computeUnits > 0 ? scene->computeUnits : 1) * PATHED_FUSED_WAVES;
+    return queueBlocks * kWavesPerBlock * kCameraQueueWords;
+}
+
+static size_t cameraMaskQuads(const PathedScene *scene) { return cameraMaskWords(scene->width * scene->height) / 2; }   // float4 = two masks
+
+static hipError_t rebuildCameraMasks(PathedScene *scene)
+{
+    if (!scene->bruteForce || !scene->fusedPath) { return hipSuccess; }
+    hipError_t status;
+    scene->cameraMasksBuilt = false;   // until the build below has run to its end: a failure leaves no table marked as valid
+    const size_t quads = cameraMaskQuads(scene) + cameraQueueWords(scene);
+    if (scene->cameraQueue.count < quads && (status = scene->cameraQueue.allocate(quads)) != hipSuccess) { return status; }
+    const int nPixels = scene->width * scene->height;
+    const size_t words = cameraMaskWords(nPixels);
+    hipEvent_t start = nullptr, stop = nullptr;
+    const bool timed = hipEventCreate(&start) == hipSuccess && hipEventCreate(&stop) == hipSuccess;
+    if (timed) { (void)hipEventRecord(start, nullptr); }
+    hipLaunchKernelGGL(k_build_camera_masks, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, nullptr, scene->device.camera,
+                       scene->itemTris.ptr, scene->device.nTris, nPixels, reinterpret_cast<unsigned long long *>(scene->cameraQueue.ptr));
+    if (timed) { (void)hipEventRecord(stop, nullptr); }
+    status = hipGetLastError();
+    if (status == hipSuccess) { status = hipDeviceSynchronize(); }
+    float ms = 0.f;
+    if (timed && status == hipSuccess && hipEventElapsedTime(&ms, start, stop) == hipSuccess) { scene->cameraMaskMs = ms; }
+    if (start) { (void)hipEventDestroy(start); }
+    if (stop) { (void)hipEventDestroy(stop); }
+    if (status != hipSuccess) { return status; }
+    scene->cameraMasksBuilt = true;
+    return hipSuccess;
+}
+
 // [r5] the phase-1 records of the hybrid kernel's direct set (they depend on the camera only through the scene's extent)
 static hipError_t rebuildHybridItems(PathedScene *scene)
 {
@@ -2241,6 +2283,7 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
             scene->mfmaPhase1 = true;
         }
     }
+    if ((status = rebuildCameraMasks(scene)) != hipSuccess) { return fail_cleanup(status, "build the camera-ray candidate masks"); }
     scene->unitOrder = unitOrderFromEnvironment(options.unit_order == 2 ? kOrderStripesTiled : options.unit_order == 3 ? kOrderTiles : kOrderStripes);
     if (options.max_slots >= kBlock) { scene->maxSlots = options.max_slots; scene->adaptiveSlots = false; }
     if (const char *slots = tuningEnv("PATHED_MAX_SLOTS")) {
@@ -2479,15 +2522,15 @@ static int renderPassFused(PathedScene *scene, const Pass &pass)
 {
     // the camera queues: once per scene, for every wave of the largest grid persistentPass starts; the launch below checks
     // its grid against what is there
-    const size_t queueBlocks = (size_t)(scene->computeUnits > 0 ? scene->computeUnits : 1) * PATHED_FUSED_WAVES;
-    const size_t queueWords = queueBlocks * kWavesPerBlock * kCameraQueueWords;
-    if (scene->cameraQueue.count < queueWords) { HIP_TRY(scene->cameraQueue.allocate(queueWords)); }
+    // (the allocation starts with the camera-ray candidate masks, rebuildCameraMasks: made with the scene, so this is a check)
+    const size_t maskQuads = cameraMaskQuads(scene);
+    if (scene->cameraQueue.count < maskQuads + cameraQueueWords(scene) || !scene->cameraMasksBuilt) { HIP_TRY(rebuildCameraMasks(scene)); }
     bool queueShort = false;
     const int code = persistentPass(scene, pass, PATHED_FUSED_WAVES, 0, 0, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
-        if ((size_t)grid.x * kWavesPerBlock * kCameraQueueWords > scene->cameraQueue.count) { queueShort = true; return; }   // nothing is launched
+        if ((size_t)grid.x * kWavesPerBlock * kCameraQueueWords > scene->cameraQueue.count - maskQuads) { queueShort = true; return; }   // nothing is launched
         const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
         const size_t lds = ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0;
-        params.cameraQueue = scene->cameraQueue.ptr;
+        params.cameraQueue = scene->cameraQueue.ptr + maskQuads;
         params.mfmaTable = scene->mfmaTable.ptr;
         params.mfmaFrame = scene->mfmaFrame;
         params.smallQuads = scene->smallLayout.nQuads;
@@ -3267,6 +3310,7 @@ int pathed_hip_scene_set_camera(PathedScene *scene, const PathedCamera *camera)
     buildCamera(*camera, &scene->device.camera);
     SELECT_DEVICE(scene);
     HIP_TRY(rebuildSmallItems(scene));   // tiny scenes: the phase-1 tolerances depend on how far away a ray may start
+    HIP_TRY(rebuildCameraMasks(scene));  // ... and which triangles a pixel's camera rays can meet on where the camera is
     HIP_TRY(rebuildHybridItems(scene));  // ... and so do the hybrid kernel's direct set's
     return PATHED_OK;
 }
@@ -3661,6 +3705,26 @@ int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, siz
     return PATHED_OK;
 }
 
+int pathed_hip_debug_camera_masks(PathedScene *scene, uint64_t *out, size_t n_pixels)
+{
+    if (!scene || !out) { return fail(PATHED_E_INVALID, "null scene or output buffer"); }
+    if (!scene->bruteForce || !scene->fusedPath) { return fail(PATHED_E_UNSUPPORTED, "only scenes on the fused path kernel carry camera-ray candidate masks"); }
+    if (n_pixels != (size_t)scene->width * (size_t)scene->height) { return fail(PATHED_E_INVALID, "n_pixels must be the scene's pixel count"); }
+    SELECT_DEVICE(scene);
+    if (!scene->cameraMasksBuilt) { HIP_TRY(rebuildCameraMasks(scene)); }
+    HIP_TRY(hipMemcpy(out, scene->cameraQueue.ptr, n_pixels * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PATHED_OK;
+}
+
+int pathed_hip_debug_item_order(PathedScene *scene, int32_t *primitives, size_t n_triangles)
+{
+    if (!scene || !primitives) { return fail(PATHED_E_INVALID, "null scene or output buffer"); }
+    if (!scene->bruteForce) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector serves scenes of 1..64 triangles"); }
+    if (n_triangles != (size_t)scene->device.nTris || scene->itemTrisHost.size() < 12 * n_triangles) { return fail(PATHED_E_INVALID, "n_triangles must be the scene's triangle count"); }
+    for (size_t k = 0; k < n_triangles; k++) { std::memcpy(&primitives[k], &scene->itemTrisHost[12 * k + 3], sizeof(int32_t)); }
+    return PATHED_OK;
+}
+
 int pathed_hip_debug_light_records(PathedScene *scene, float *triangles, size_t n_triangles, float *lights, size_t max_lights, int *n_lights)
 {
     if (!scene || !triangles || !lights || !n_lights) { return fail(PATHED_E_INVALID, "null scene or output buffer"); }
@@ -3889,6 +3953,10 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
         }
     }
     if (getenv("PATHED_DEBUG_STATS")) {
+        if (scene->cameraMasksBuilt) {
+            fprintf(stderr, "[pathed] camera masks: %d pixels x %d triangles, last built in %.3f ms on the device\n", scene->width * scene->height,
+                    scene->device.nTris, scene->cameraMaskMs);
+        }
         fprintf(stderr, "[pathed] wave steps %llu lane steps %llu (lane utilisation %.3f) refill rounds %llu\n",
                 device[kStatWaveSteps], device[kStatLaneSteps],
                 device[kStatWaveSteps] ? (double)device[kStatLaneSteps] / (64.0 * (double)device[kStatWaveSteps]) : 0.0,

@@ -387,6 +387,21 @@ class HipScene:
         _check(self._lib, code, "pathed_hip_debug_small_candidates")
         return out
 
+    def camera_masks(self):
+        """The per-pixel candidate masks of the camera rays (pathed_hip_debug_camera_masks; scenes on the fused path kernel):
+        (height, width) uint64, bit 63 - k = triangle k of the item order."""
+        out = np.zeros((self.height, self.width), dtype=np.uint64)
+        code = self._lib.pathed_hip_debug_camera_masks(self._handle, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size)
+        _check(self._lib, code, "pathed_hip_debug_camera_masks")
+        return out
+
+    def item_order(self, n_triangles):
+        """Original primitive id of every item-order triangle (pathed_hip_debug_item_order): (n_triangles,) int32."""
+        out = np.zeros(n_triangles, dtype=np.int32)
+        code = self._lib.pathed_hip_debug_item_order(self._handle, out.ctypes.data_as(C.POINTER(C.c_int32)), n_triangles)
+        _check(self._lib, code, "pathed_hip_debug_item_order")
+        return out
+
     def light_records(self, n_triangles, max_lights):
         """The stored per-triangle and per-light constants beside what the per-vertex functions compute
         (pathed_hip_debug_light_records): (n_triangles, 20) and (the scene's light count, 18) float32."""

@@ -182,10 +182,10 @@ def write_bench_mix(kernels, pretty, args):
             "kernel": shown, "kernel_sources": sources_digest(),
             "method": "compiler assembly (hipcc -S), every basic block once, the parallelogram-pair loop x %d and the lone-pair loop x %d "
                       "(their trip counts on scenes/cornell.json); v_div_scale / v_div_fmas / v_div_fixup counted with the plain instructions.  "
-                      "The refill of the camera queue (unit bookkeeping, camera ray, a one-ray copy of both loops at one trip each) is "
-                      "counted once per iteration like every block although it ran in 0.196 of the iterations when it was measured "
-                      "(profiles/camera_queue_profile.log, scenes/cornell.json): valu_per_iteration overstates the loop by about four "
-                      "fifths of the refill's share of the ~1 100 static instructions the queue added" % (args.quad_pairs, args.lone_pairs),
+                      "The refill of the camera queue (unit bookkeeping, camera ray, the pixel's candidate mask, phase 2; it holds no "
+                      "copy of the phase-1 loops) is counted once per iteration like every block although it ran in 0.196 of the "
+                      "iterations when it was measured (profiles/camera_queue_profile.log, scenes/cornell.json): valu_per_iteration "
+                      "overstates the loop by about four fifths of the refill's static instructions" % (args.quad_pairs, args.lone_pairs),
             "loops": {label: {"trips": trips, "valu": sum(v for k, v in blocks[label]["ops"].items() if k.startswith("valu")),
                               "packed": blocks[label]["ops"]["valu_packed"]} for label, trips in weights.items()},
             "valu_per_iteration": sum(valu.values()),
