@@ -389,6 +389,32 @@ typedef struct PathedInstanceDesc {
 } PathedInstanceDesc;
 int pathed_hip_scene_create_instanced(const PathedSceneDesc *desc, const PathedSceneOptions *options,
                                       const PathedInstanceDesc *instances, PathedScene **out);
+
+/* Moving placements: new transforms for ALL instances of a scene made by pathed_hip_scene_create_instanced, what the reference
+ * repeats rtcCommitScene for (src/scene.cpp:39), without building a prototype's tree or uploading a record again.
+ * transforms: 12 floats per instance, row-major 3 x 4, in instance order -- the meaning of PathedInstance.transform; host
+ * memory, or for the _device form memory on the scene's device (a simulation's tensor).  The host form uploads into a staging
+ * buffer and runs the device form's code: there is one compute path.  n_instances must be the scene's; every instance's
+ * prototype, the instance count, the virtual id bases and the prototypes stay as they are.
+ *
+ * On the device, k_instance_records restates every 112-byte record -- the inverse by the routine above, the same bits as the
+ * host's -- into a second record buffer, and k_refit_top_pass refits the TOP tree bottom-up around the new world boxes (the
+ * box rule of scene creation, pathed_amd.instances.placement_box in numpy).  The tree keeps its SHAPE: hits, ids and shading
+ * are those of a scene created with the new transforms, but placements scattered far from where the tree was built make it
+ * slower to walk (boxes of siblings overlap) -- a caller who moves them that far creates the scene again.  No prototype
+ * node and no leaf triangle is written; the traversal stack's bound is unchanged.
+ *
+ * Order: the call first waits for ALL work on the scene's device (hipDeviceSynchronize), so render calls still running --
+ * the *_device calls on a caller's stream included -- finish on the old tree, and a d_transforms that the caller's own stream
+ * is still writing is complete; it returns once the device holds the new records and tree, so every later call, on any
+ * stream, sees them.  Like pathed_hip_scene_refit it must not run concurrently with another call on the same scene.
+ * device_ms (may be NULL): HIP-event time of the kernels, uploads excluded.
+ *
+ * PATHED_E_UNSUPPORTED: a scene without instances.  PATHED_E_INVALID: a null pointer, a count that is not the scene's, a
+ * transform that is not finite or not invertible or whose inverse is not finite (the rule of scene creation; the message
+ * names the lowest such instance index).  On every error the scene is exactly as it was before the call. */
+int pathed_hip_scene_set_instance_transforms(PathedScene *scene, const float *transforms, uint32_t n_instances, float *device_ms);
+int pathed_hip_scene_set_instance_transforms_device(PathedScene *scene, const float *d_transforms, uint32_t n_instances, float *device_ms);
 /* Another view of the same scene: replaces the camera (reference Camera, src/camera.cpp:13-30) without rebuilding or
  * re-uploading anything; the resolution must stay (the caller's radiance sums are per pixel). */
 int pathed_hip_scene_set_camera(PathedScene *scene, const PathedCamera *camera);
@@ -666,6 +692,12 @@ int pathed_hip_debug_item_order(PathedScene *scene, int32_t *primitives, size_t 
  *       sampling record (p0, material bits) (p1, area) (p2, invPDF) (normal, 1 / invPDF); all zero for a light that is not a triangle.
  * n_triangles must be the scene's triangle count; more lights than max_lights is PATHED_E_INVALID. */
 int pathed_hip_debug_light_records(PathedScene *scene, float *triangles, size_t n_triangles, float *lights, size_t max_lights, int *n_lights);
+
+/* Test hook onto the placements' records as the device holds them (scene creation writes them on the host,
+ * pathed_hip_scene_set_instance_transforms on the device): 28 words per instance, host memory -- the transform's rows (12
+ * floats), the inverse's rows (12 floats), then four int32: virtual id base, prototype, the prototype's root node, its first
+ * shading record.  n_instances must be the scene's.  PATHED_E_UNSUPPORTED on a scene without instances. */
+int pathed_hip_debug_instance_records(PathedScene *scene, float *records /* 28 words per instance */, size_t n_instances);
 
 /* 1 in libpathed_hip_experiments.so (`make experiments`), 0 in the product library.  The experiments build adds the
  * kernel organisations that were measured and rejected: shade_kernel 2 (staged) and 4 (split),

@@ -236,6 +236,9 @@ HIP_SYMBOLS = [
     "pathed_hip_scene_create",
     "pathed_hip_scene_create_ex",
     "pathed_hip_scene_create_instanced",
+    "pathed_hip_scene_set_instance_transforms",
+    "pathed_hip_scene_set_instance_transforms_device",
+    "pathed_hip_debug_instance_records",
     "pathed_hip_scene_device",
     "pathed_hip_scene_set_camera",
     "pathed_hip_scene_set_grid_medium",
@@ -321,6 +324,13 @@ def load_hip():
     if hasattr(lib, "pathed_hip_scene_create_instanced"):   # (PATHED_HIP_LIB may name an older build of the same ABI)
         lib.pathed_hip_scene_create_instanced.argtypes = [C.POINTER(PathedSceneDesc), C.POINTER(PathedSceneOptions), C.POINTER(PathedInstanceDesc), C.POINTER(vp)]
         lib.pathed_hip_scene_create_instanced.restype = C.c_int
+    if hasattr(lib, "pathed_hip_scene_set_instance_transforms"):   # (an older build of the same ABI, as above)
+        lib.pathed_hip_scene_set_instance_transforms.argtypes = [vp, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
+        lib.pathed_hip_scene_set_instance_transforms.restype = C.c_int
+        lib.pathed_hip_scene_set_instance_transforms_device.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_float)]
+        lib.pathed_hip_scene_set_instance_transforms_device.restype = C.c_int
+        lib.pathed_hip_debug_instance_records.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
+        lib.pathed_hip_debug_instance_records.restype = C.c_int
     lib.pathed_hip_scene_device.argtypes = [vp]
     lib.pathed_hip_scene_device.restype = C.c_int
     lib.pathed_hip_scene_set_camera.argtypes = [vp, C.POINTER(PathedCamera)]

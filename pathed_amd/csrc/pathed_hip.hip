@@ -323,6 +323,18 @@ struct PathedScene {
     DeviceBuffer<int> instanceBases;
     DInstanceSet instanceSet = { nullptr, nullptr, 0, 0 };
     int instancedMaxStack = 0;    // the top tree's bound + the deepest prototype's + 1
+    // moving placements (pathed_hip_scene_set_instance_transforms): the top tree is nodes [0, topNodes) of `nodes`, topDepth
+    // 4-wide levels deep; the prototypes' padded boxes (lo, hi per prototype) the placements' world boxes are made from
+    int topNodes = 0, topDepth = 0;
+    DeviceBuffer<float4> protoBoxes;
+    // ... and its working memory, allocated on first use: the second record buffer (a call writes it, then swaps it with
+    // instanceRecords), the uploaded transforms of the host entry, (refused count, lowest refused index), and the refit's
+    // unpadded bounds and two flag arrays, topNodes entries each
+    DeviceBuffer<float4> instanceRecordsStaged;
+    DeviceBuffer<float> instanceTransforms;
+    DeviceBuffer<unsigned int> instanceBad;
+    DeviceBuffer<float4> topLo, topHi;
+    DeviceBuffer<unsigned char> topReady;
 
     bool countMode = false;
     bool timeKernels = false;
@@ -1611,7 +1623,7 @@ static int planInstances(const PathedSceneDesc *desc, const PathedSceneOptions &
 // The two-level tree in one node array and one leaf-triangle array (trace.h): the top tree over the world triangles and the
 // placements' world boxes, then one object-space tree per prototype, refs and firsts made absolute.
 static FlatBvh buildInstancedBvh(const PathedSceneDesc *desc, const PathedInstanceDesc *in, const InstancedLayout &layout, int buildThreads,
-                                 std::vector<float4> *records, int *maxStack)
+                                 std::vector<float4> *records, int *maxStack, std::vector<float4> *protoBoxes, int *topNodes, int *topDepth)
 {
     const size_t nProto = layout.protoFirst.size();
     std::vector<FlatBvh> trees(nProto);
@@ -1666,6 +1678,15 @@ static FlatBvh buildInstancedBvh(const PathedSceneDesc *desc, const PathedInstan
         for (int k = 0; k < 4; k++) { bvh_detail::putInt(&out.nodes[24 + k], kEmptyChildRef); }
         out.nodeCount = 1;
         out.maxDepth = 1;
+    }
+    // what a later move of the placements needs (pathed_hip_scene_set_instance_transforms): the top tree's extent in the node
+    // array, its levels, and the padded prototype boxes the world boxes above came from
+    *topNodes = out.nodeCount;
+    *topDepth = out.maxDepth;
+    protoBoxes->resize(2 * nProto);
+    for (size_t p = 0; p < nProto; p++) {
+        (*protoBoxes)[2 * p] = make_float4(protoLo[3 * p], protoLo[3 * p + 1], protoLo[3 * p + 2], 0.f);
+        (*protoBoxes)[2 * p + 1] = make_float4(protoHi[3 * p], protoHi[3 * p + 1], protoHi[3 * p + 2], 0.f);
     }
     *maxStack = (3 * out.maxDepth + 1) + (3 * deepest + 1) + 1;
     out.maxDepth += deepest;
@@ -2005,9 +2026,10 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
             }
         }
         scene->spheresInTree = !sphereBounds.empty();
-        std::vector<float4> instanceRecords;
+        std::vector<float4> instanceRecords, protoBoxes;
         if (instanceDesc) {
-            scene->bvh = buildInstancedBvh(desc, instanceDesc, instancedLayout, scene->options.build_threads, &instanceRecords, &scene->instancedMaxStack);
+            scene->bvh = buildInstancedBvh(desc, instanceDesc, instancedLayout, scene->options.build_threads, &instanceRecords, &scene->instancedMaxStack,
+                                           &protoBoxes, &scene->topNodes, &scene->topDepth);
         } else {
             scene->bvh = buildBvh(desc->positions, desc->indices, desc->n_triangles, sphereBounds.data(), (uint32_t)(sphereBounds.size() / 4),
                                   scene->options.build_threads);
@@ -2021,6 +2043,7 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
         if (instanceDesc) {
             if ((status = scene->instanceRecords.upload(instanceRecords)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload instance records"); }
             if ((status = scene->instanceBases.upload(instancedLayout.bases)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload instance bases"); }
+            if ((status = scene->protoBoxes.upload(protoBoxes)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload prototype boxes"); }
             scene->instanceSet.records = scene->instanceRecords.ptr;
             scene->instanceSet.bases = scene->instanceBases.ptr;
             scene->instanceSet.nInstances = (int)instanceDesc->n_instances;
@@ -3832,6 +3855,126 @@ int pathed_hip_scene_refit(PathedScene *scene, const float *positions, const flo
     if (!rootReady) { return fail(PATHED_E_DEVICE, "refit: the root was never reached (a cycle in the tree?)"); }
     scene->bvhOnHost = false;   // exports download the refitted tree
     if (device_ms) { *device_ms = ms; }
+    return PATHED_OK;
+}
+
+// ---- moving placements (include/pathed_hip.h; kernels.h: k_instance_records, k_refit_top_pass)
+// The one compute path of both entry points: `deviceTransforms` holds 12 floats per placement on the scene's device.
+static int setInstanceTransforms(PathedScene *scene, const float *deviceTransforms, float *device_ms)
+{
+    const int nInstances = scene->instanceSet.nInstances;
+    const int topNodes = scene->topNodes;
+    if (topNodes <= 0 || (size_t)topNodes > scene->nodes.count / 8) { return fail(PATHED_E_INVALID, "the scene has no top tree"); }
+    // everything a first call allocates, before anything is written: a failure here leaves the scene as it was
+    if (scene->instanceRecordsStaged.count != scene->instanceRecords.count) { HIP_TRY(scene->instanceRecordsStaged.allocate(scene->instanceRecords.count)); }
+    if (!scene->instanceBad.ptr) { HIP_TRY(scene->instanceBad.allocate(2)); }
+    if (!scene->topLo.ptr) {
+        HIP_TRY(scene->topLo.allocate((size_t)topNodes));
+        HIP_TRY(scene->topHi.allocate((size_t)topNodes));
+        HIP_TRY(scene->topReady.allocate(2 * (size_t)topNodes));
+    }
+    // render calls on a caller's stream may still walk the tree, and the caller's own stream may still write the transforms
+    HIP_TRY(hipDeviceSynchronize());
+    const unsigned int clear[2] = { 0u, 0xFFFFFFFFu };
+    unsigned int bad[2] = { 0u, 0u };
+    HIP_TRY(hipMemcpy(scene->instanceBad.ptr, clear, sizeof clear, hipMemcpyHostToDevice));
+    hipEvent_t start = nullptr, stop = nullptr;
+    HIP_TRY(hipEventCreate(&start));
+    hipError_t status = hipEventCreate(&stop);
+    float ms = 0.f;
+    // (the events of one timed stretch of launches on the null stream; its device time joins ms)
+    auto timed = [&](auto &&launches) {
+        float part = 0.f;
+        if (status == hipSuccess) { status = hipEventRecord(start, nullptr); }
+        if (status == hipSuccess) { launches(); status = hipGetLastError(); }
+        if (status == hipSuccess) { status = hipEventRecord(stop, nullptr); }
+        if (status == hipSuccess) { status = hipEventSynchronize(stop); }
+        if (status == hipSuccess) { status = hipEventElapsedTime(&part, start, stop); }
+        ms += part;
+    };
+    auto finish = [&]() {
+        (void)hipEventDestroy(start);
+        if (stop) { (void)hipEventDestroy(stop); }
+    };
+    if (nInstances > 0) {
+        timed([&]() {
+            hipLaunchKernelGGL(k_instance_records, dim3((unsigned)((nInstances + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                               deviceTransforms, nInstances, scene->instanceRecords.ptr, scene->instanceRecordsStaged.ptr, scene->instanceBad.ptr);
+        });
+        if (status == hipSuccess) { status = hipMemcpy(bad, scene->instanceBad.ptr, sizeof bad, hipMemcpyDeviceToHost); }
+        if (status != hipSuccess) { finish(); return fail(PATHED_E_DEVICE, std::string("set_instance_transforms: ") + hipGetErrorString(status)); }
+        if (bad[0] != 0u) {
+            // (the staged records are simply not adopted: the live records, the tree and the flags are untouched)
+            finish();
+            return fail(PATHED_E_INVALID, "instance transform " + std::to_string(bad[1]) + " is not finite or not invertible (" + std::to_string(bad[0])
+                        + " of the " + std::to_string(nInstances) + " transforms are refused; the scene keeps its placements)");
+        }
+        std::swap(scene->instanceRecords.ptr, scene->instanceRecordsStaged.ptr);
+        scene->instanceSet.records = scene->instanceRecords.ptr;
+    }
+    if (status == hipSuccess) { status = hipMemset(scene->topReady.ptr, 0, 2 * (size_t)topNodes); }
+    int passes = 0;
+    unsigned char rootReady = 0;
+    const dim3 grid((unsigned)((topNodes + kBlock - 1) / kBlock)), block(kBlock);
+    auto runPasses = [&](int count) {
+        for (int k = 0; k < count; k++, passes++) {
+            unsigned char *in = scene->topReady.ptr + (size_t)(passes & 1) * topNodes, *out = scene->topReady.ptr + (size_t)((passes + 1) & 1) * topNodes;
+            hipLaunchKernelGGL(k_refit_top_pass, grid, block, 0, nullptr, scene->nodes.ptr, topNodes, scene->instanceRecords.ptr, nInstances,
+                               scene->protoBoxes.ptr, (int)(scene->protoBoxes.count / 2), scene->topLo.ptr, scene->topHi.ptr, in, out);
+        }
+    };
+    // one pass per 4-wide level of the top tree, back to back, then the guard of pathed_hip_scene_refit
+    timed([&]() { runPasses(scene->topDepth > 0 ? scene->topDepth + 1 : 16); });
+    if (status == hipSuccess) { status = hipMemcpy(&rootReady, scene->topReady.ptr + (size_t)(passes & 1) * topNodes, 1, hipMemcpyDeviceToHost); }
+    while (status == hipSuccess && !rootReady && passes < 4096) {
+        timed([&]() { runPasses(4); });
+        if (status == hipSuccess) { status = hipMemcpy(&rootReady, scene->topReady.ptr + (size_t)(passes & 1) * topNodes, 1, hipMemcpyDeviceToHost); }
+    }
+    finish();
+    if (status != hipSuccess) { return fail(PATHED_E_DEVICE, std::string("set_instance_transforms: ") + hipGetErrorString(status)); }
+    if (!rootReady) { return fail(PATHED_E_DEVICE, "set_instance_transforms: the top tree's root was never reached (a cycle in the tree?)"); }
+    scene->bvhOnHost = false;   // exports download the refitted tree
+    if (device_ms) { *device_ms = ms; }
+    return PATHED_OK;
+}
+
+static int checkInstanceMove(PathedScene *scene, const float *transforms, uint32_t n_instances)
+{
+    if (!scene || !transforms) { return fail(PATHED_E_INVALID, "null scene or transforms"); }
+    if (!scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "set_instance_transforms: the scene has no instances (pathed_hip_scene_create_instanced makes one that has)"); }
+    if (n_instances != (uint32_t)scene->instanceSet.nInstances) { return fail(PATHED_E_INVALID, "set_instance_transforms keeps the placements: the instance count must be the scene's"); }
+    return PATHED_OK;
+}
+
+int pathed_hip_scene_set_instance_transforms_device(PathedScene *scene, const float *d_transforms, uint32_t n_instances, float *device_ms)
+{
+    const int code = checkInstanceMove(scene, d_transforms, n_instances);
+    if (code != PATHED_OK) { return code; }
+    SELECT_DEVICE(scene);
+    return setInstanceTransforms(scene, d_transforms, device_ms);
+}
+
+int pathed_hip_scene_set_instance_transforms(PathedScene *scene, const float *transforms, uint32_t n_instances, float *device_ms)
+{
+    const int code = checkInstanceMove(scene, transforms, n_instances);
+    if (code != PATHED_OK) { return code; }
+    SELECT_DEVICE(scene);
+    const size_t floats = (size_t)12 * n_instances;
+    if (scene->instanceTransforms.count != floats) { HIP_TRY(scene->instanceTransforms.allocate(floats)); }
+    if (floats > 0) { HIP_TRY(hipMemcpy(scene->instanceTransforms.ptr, transforms, floats * sizeof(float), hipMemcpyHostToDevice)); }
+    return setInstanceTransforms(scene, scene->instanceTransforms.ptr, device_ms);
+}
+
+int pathed_hip_debug_instance_records(PathedScene *scene, float *records, size_t n_instances)
+{
+    if (!scene || !records) { return fail(PATHED_E_INVALID, "null scene or records"); }
+    if (!scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "instance records: the scene has no instances"); }
+    if (n_instances != (size_t)scene->instanceSet.nInstances) { return fail(PATHED_E_INVALID, "instance records: the instance count must be the scene's"); }
+    SELECT_DEVICE(scene);
+    if (n_instances > 0) {
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(records, scene->instanceRecords.ptr, n_instances * (size_t)kInstanceQuads * sizeof(float4), hipMemcpyDeviceToHost));
+    }
     return PATHED_OK;
 }
 

@@ -40,6 +40,44 @@ def instance_inverse(transform):
     return out
 
 
+def _host_min(a, b):
+    """std::min(a, b) as the C++ library states it: b where b < a, else a (a signed zero stays where the host leaves it)"""
+    return np.where(b < a, b, a).astype(np.float32)
+
+
+def _host_max(a, b):
+    return np.where(a < b, b, a).astype(np.float32)
+
+
+def pad_box(lo, hi):
+    """bvh_build.h padBox in float32: every child box of a node is its content's box widened by 1e-5 max(1, |lo|, |hi|) per axis."""
+    lo, hi = _f32(lo), _f32(hi)
+    pad = np.float32(1e-5) * _host_max(np.float32(1.0), _host_max(np.abs(lo), np.abs(hi)))
+    return (lo - pad).astype(np.float32), (hi + pad).astype(np.float32)
+
+
+def prototype_box(positions):
+    """The padded box of a prototype's corners ((n, 3) float32, object space): what its root's children span at most."""
+    p = _f32(positions).reshape(-1, 3)
+    return pad_box(p.min(axis=0), p.max(axis=0))
+
+
+def placement_box(transform, proto_lo, proto_hi):
+    """The world box of a placement as scene creation and k_refit_top_pass state it, float32, one rounding per operation: the
+    eight corners of the prototype's padded box (prototype_box) through the flatten routine, min / max, then a pad of
+    1e-5 max(1, |lo|, |hi|) + 1e-5 (hi - lo) per axis for the roundings of the object-space ray.  The node that holds the
+    placement stores pad_box of this box, as it does of every child."""
+    proto_lo, proto_hi = _f32(proto_lo).reshape(3), _f32(proto_hi).reshape(3)
+    corners = np.array([[(proto_hi if corner & (1 << axis) else proto_lo)[axis] for axis in range(3)] for corner in range(8)], dtype=np.float32)
+    world = flatten_points(transform, corners)
+    lo, hi = np.full(3, np.inf, dtype=np.float32), np.full(3, -np.inf, dtype=np.float32)
+    for point in world:
+        lo, hi = _host_min(lo, point), _host_max(hi, point)
+    reach = _host_max(np.float32(1.0), _host_max(np.abs(lo), np.abs(hi)))
+    pad = (np.float32(1e-5) * reach + np.float32(1e-5) * (hi - lo)).astype(np.float32)
+    return (lo - pad).astype(np.float32), (hi + pad).astype(np.float32)
+
+
 def flatten_points(transform, points):
     """x' = ((m[0] x + m[1] y) + m[2] z) + m[3], ... in float32, for (n, 3) float32 points."""
     m = _f32(transform).reshape(12)
@@ -74,6 +112,16 @@ class InstanceSet:
         self.desc.struct_size = C.sizeof(_capi.PathedInstanceDesc)
         self.desc.n_prototypes, self.desc.prototypes = len(self.prototypes), self._prototype_array
         self.desc.n_instances, self.desc.instances = len(self.instances), self._instance_array
+
+    def set_transforms(self, transforms):
+        """Replace every placement's transform ((n, 12) or (n, 3, 4) float32, instance order); the prototypes stay
+        (HipScene.set_instance_transforms keeps the set in step with the device through this)."""
+        transforms = _f32(transforms).reshape(-1, 12)
+        if len(transforms) != len(self.instances):
+            raise ValueError("%d transforms for %d placements" % (len(transforms), len(self.instances)))
+        self.instances = [(prototype, row.copy()) for (prototype, _), row in zip(self.instances, transforms)]
+        for slot, (_, transform) in zip(self._instance_array, self.instances):
+            slot.transform[:] = transform.tolist()
 
 
 class FlattenedScene:

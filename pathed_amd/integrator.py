@@ -429,6 +429,43 @@ class HipScene:
         _check(self._lib, code, "pathed_hip_scene_refit")
         return float(ms.value)
 
+    def set_instance_transforms(self, transforms):
+        """New transforms for all placements of an instanced scene (pathed_hip_scene_set_instance_transforms): the records are
+        restated and the top tree refitted on the device; prototypes, instance count and primitive ids stay.  `transforms` is
+        an (n, 12) or (n, 3, 4) float32 numpy array (row-major 3 x 4 each, instance order), or a contiguous float32 torch
+        tensor of that shape on the scene's device, read in place (the _device entry).  Host data keeps `self.instance_set` in
+        step, so that flatten_instances still describes the scene; after device data it describes the placements of the last
+        host call.  Returns the device time of the kernels in milliseconds."""
+        ms = C.c_float(0.0)
+        if hasattr(transforms, "data_ptr"):
+            import torch
+            if not (transforms.is_cuda and transforms.device.index == self.device):
+                raise ValueError("the transforms tensor must live on the scene's device (cuda:%d)" % self.device)
+            if transforms.dtype != torch.float32 or not transforms.is_contiguous() or transforms.numel() % 12 != 0:
+                raise ValueError("the transforms tensor must be contiguous float32, 12 values per instance")
+            # the tensor may keep some storage address even when it is empty; the count alone decides what is read
+            pointer = C.c_void_p(transforms.data_ptr() or 0)
+            code = self._lib.pathed_hip_scene_set_instance_transforms_device(self._handle, pointer, transforms.numel() // 12, C.byref(ms))
+            _check(self._lib, code, "pathed_hip_scene_set_instance_transforms_device")
+            return float(ms.value)
+        transforms = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 12)
+        padded = transforms if len(transforms) else np.zeros((1, 12), dtype=np.float32)   # (an empty array has no address to pass)
+        code = self._lib.pathed_hip_scene_set_instance_transforms(self._handle, padded.ctypes.data_as(C.POINTER(C.c_float)), len(transforms), C.byref(ms))
+        _check(self._lib, code, "pathed_hip_scene_set_instance_transforms")
+        if getattr(self, "instance_set", None) is not None:
+            self.instance_set.set_transforms(transforms)
+        return float(ms.value)
+
+    def instance_records(self):
+        """The placements' records as the device holds them (pathed_hip_debug_instance_records): (transforms (n, 12) float32,
+        inverses (n, 12) float32, ids (n, 4) int32: virtual id base, prototype, its root node, its first shading record)."""
+        count = int(self.instance_set.desc.n_instances) if getattr(self, "instance_set", None) is not None else 0
+        records = np.zeros((max(1, count), 28), dtype=np.float32)
+        code = self._lib.pathed_hip_debug_instance_records(self._handle, records.ctypes.data_as(C.POINTER(C.c_float)), count)
+        _check(self._lib, code, "pathed_hip_debug_instance_records")
+        records = records[:count]
+        return records[:, 0:12].copy(), records[:, 12:24].copy(), records[:, 24:28].copy().view(np.int32)
+
     def set_samples_per_unit(self, samples):
         """Summation granularity (see include/pathed_hip.h); 1 = the reference's exact order."""
         _check(self._lib, self._lib.pathed_hip_set_samples_per_unit(self._handle, int(samples)),
