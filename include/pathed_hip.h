@@ -669,6 +669,16 @@ int pathed_hip_trace(PathedScene *scene, const float *rays, size_t n,
  * Phase 1 is correct iff accepted is a subset of candidates for every ray. */
 int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out);
 
+/* Test hook onto the shadow ray's phase 1 as the fused kernel runs it: the items that can never occlude a light sample
+ * (pathed_amd/csrc/small_items.h: NEVER-OCCLUDERS) come last in item order and the shadow ray's pass stops before them.
+ * rays: n * 10 floats as pathed_hip_debug_small_candidates takes them (the shadow ray is origin, shadow direction, shadow tfar).
+ * out:  n * 2 x uint64, bit p = ORIGINAL primitive id p: the pruned item-form candidates of the shadow ray, the triangles
+ *       phase 2 accepts for it (t in (1e-3, tfar]).  The pruning is correct iff accepted is a subset of candidates for every ray
+ *       that sampleLightsTerm can build: from a point on a scene surface to a point on an emitter.
+ * layout: 4 x int32: parallelograms, lone triangles, the shadow ray's turns over parallelogram pairs and over lone pairs.
+ * never_occluders: one uint64, bit p = primitive p is a never-occluder.  Both are written even when n is 0. */
+int pathed_hip_debug_shadow_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out, int32_t *layout, uint64_t *never_occluders);
+
 /* Test hook onto the per-pixel candidate masks of the camera rays (scenes on the fused path kernel only; built at scene
  * creation and again by pathed_hip_scene_set_camera, pathed_amd/csrc/camera_masks.h).
  * out: n_pixels x uint64, row-major pixels, host memory; n_pixels must be width * height.  Bit 63 - k = triangle k of the

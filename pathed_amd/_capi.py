@@ -257,6 +257,7 @@ HIP_SYMBOLS = [
     "pathed_hip_render_pixels_device",
     "pathed_hip_trace",
     "pathed_hip_debug_small_candidates",
+    "pathed_hip_debug_shadow_candidates",
     "pathed_hip_debug_camera_masks",
     "pathed_hip_debug_item_order",
     "pathed_hip_debug_light_records",
@@ -391,6 +392,8 @@ def load_hip():
     lib.pathed_hip_trace.restype = C.c_int
     lib.pathed_hip_debug_small_candidates.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint64)]
     lib.pathed_hip_debug_small_candidates.restype = C.c_int
+    lib.pathed_hip_debug_shadow_candidates.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+    lib.pathed_hip_debug_shadow_candidates.restype = C.c_int
     lib.pathed_hip_debug_light_records.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int)]
     lib.pathed_hip_debug_light_records.restype = C.c_int
     if hasattr(lib, "pathed_hip_debug_camera_masks"):   # (an older build of the same ABI, as above)

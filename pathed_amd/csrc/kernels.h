@@ -212,6 +212,7 @@ struct RenderParams {
     uint32_t sppBegin, sppEnd;
     int startBounce, lastBounce;
     int smallQuads;           // k_path_small: parallelograms among the phase-1 records (small_items.h), item-order triangles 2 q, 2 q + 1
+                              // (on the launch of a pruning instantiation of k_path_small: | shadowQuadPairs << 16 | shadowLonePairs << 24)
     // k_path_small<QUADS>: the scene's spheres, two per packed record (centre x, y, z, radius^2; the odd one out paired with a
     // sphere of radius -1 that no ray touches): phase 1 of the sphere queries (smallSphereCandidates)
     float spherePairs[8][4][2];   // [pair][component][half], kBruteForceMaxSpheres / 2 pairs
@@ -936,10 +937,13 @@ __device__ __forceinline__ unsigned int shiftInBit(unsigned int word, unsigned l
 // SHADOW: ray B (the vertex's shadow ray, held to its far bound) exists; otherwise only ray A is tested.
 // QUADS / LONE: which of the two sections the instantiation contains (a scene made of quads only needs no code, and no
 // registers, for the other test).
-template <bool SHADOW, bool QUADS = true, bool LONE = true>
+// PRUNE: ray B is a shadow ray of sampleLightsTerm and runs only the first shadowQuadPairs / shadowLonePairs turns of the two
+// sections: the items behind them can never occlude it (small_items.h: NEVER-OCCLUDERS; wave-uniform counts of the layout).
+// Their bits stay 0.  Without PRUNE both rays run every turn and the two counts are not read.
+template <bool SHADOW, bool QUADS = true, bool LONE = true, bool PRUNE = false>
 __device__ __forceinline__ void smallCandidatesItems(const f2 *records, int nQuads, int nTris, float kappaT, V3 origin, V3 directionA, V3 directionB,
                                                      unsigned int *lowA, unsigned int *highA, unsigned int *lowB, unsigned int *highB,
-                                                     float tnearLow, float tfarHighB)
+                                                     float tnearLow, float tfarHighB, int shadowQuadPairs = 0, int shadowLonePairs = 0)
 {
     // candidate bits of ray A / ray B, appended at the low end of a 64-bit word (two registers: one v_alignbit_b32 for the
     // upper half, then one v_addc per bit -- shiftInBit -- for the lower): after the last item triangle 0 is bit nTris - 1
@@ -952,7 +956,7 @@ __device__ __forceinline__ void smallCandidatesItems(const f2 *records, int nQua
 
     // ---- parallelograms, two per packed instruction
     const int nQuadPairs = QUADS ? (nQuads + 1) >> 1 : 0;
-    for (int pair = 0; QUADS && pair < nQuadPairs; pair++) {
+    auto quadTurn = [&](int pair, bool withShadow) __attribute__((always_inline)) {
         const f2 *record = records + kSmallQuadWords * pair;   // uniform index into the kernarg segment: scalar loads
         const f2 c0x = record[0], c0y = record[1], c0z = record[2];
         const f2 a1x = record[3], a1y = record[4], a1z = record[5];
@@ -1004,10 +1008,19 @@ __device__ __forceinline__ void smallCandidatesItems(const f2 *records, int nQua
         };
         oneRay(ax, ay, az, false, loA, hiA);
         __builtin_amdgcn_sched_barrier(0);   // one ray's temporaries at a time: interleaved, the two chains spilled 39 dwords of path state
-        if (SHADOW) { oneRay(bx, by, bz, true, loB, hiB); }
+        if (withShadow) { oneRay(bx, by, bz, true, loB, hiB); }
         __builtin_amdgcn_sched_barrier(0);
-    }
+    };
+    // (PRUNE: two loops rather than a branch on the turn index inside one: the Cornell-like instantiation of k_path_small has 84
+    // bytes of scratch per lane either way; this is the shape that was measured)
+    const int bothPairs = PRUNE ? (shadowQuadPairs < nQuadPairs ? shadowQuadPairs : nQuadPairs) : nQuadPairs;
+    for (int pair = 0; QUADS && pair < bothPairs; pair++) { quadTurn(pair, SHADOW); }
+    for (int pair = bothPairs; PRUNE && QUADS && pair < nQuadPairs; pair++) { quadTurn(pair, false); }
     unsigned long long accA, accB;
+    if (PRUNE && QUADS && SHADOW) {   // the turns ray B left out: four bits each, none a candidate
+        accB = (((unsigned long long)hiB << 32) | loB) << ((4 * (nQuadPairs - bothPairs)) & 63);   // (64: nothing was appended, the word is 0)
+        loB = (unsigned int)accB; hiB = (unsigned int)(accB >> 32);
+    }
     if (QUADS && (nQuads & 1)) {   // an odd count: the last pair's second half is padding
         accA = (((unsigned long long)hiA << 32) | loA) >> 2; accB = (((unsigned long long)hiB << 32) | loB) >> 2;
         loA = (unsigned int)accA; hiA = (unsigned int)(accA >> 32); loB = (unsigned int)accB; hiB = (unsigned int)(accB >> 32);
@@ -1048,9 +1061,10 @@ __device__ __forceinline__ void smallCandidatesItems(const f2 *records, int nQua
             #undef PATHED_LANES
         };
         oneRay(ax, ay, az, false, loA, hiA);
-        if (SHADOW) { oneRay(bx, by, bz, true, loB, hiB); }
+        if (SHADOW && (!PRUNE || pair < shadowLonePairs)) { oneRay(bx, by, bz, true, loB, hiB); }
     }
     accA = ((unsigned long long)hiA << 32) | loA; accB = ((unsigned long long)hiB << 32) | loB;
+    if (PRUNE && LONE && SHADOW) { accB <<= (2 * (nLonePairs - shadowLonePairs)) & 63; }   // two bits per turn ray B left out
     if (LONE && (nLone & 1)) { accA >>= 1; accB >>= 1; }
 
     // left-align: triangle k is bit 31 - (k & 31) of word k >> 5
@@ -1059,6 +1073,13 @@ __device__ __forceinline__ void smallCandidatesItems(const f2 *records, int nQua
     accB <<= shift;
     *lowA = (unsigned int)(accA >> 32); *highA = (unsigned int)accA; *lowB = (unsigned int)(accB >> 32); *highB = (unsigned int)accB;
 }
+
+// The parallelogram instantiations of k_path_small whose shadow rays skip the never-occluders (there: why not all of them).
+// The kernel branches on this constant and the launch (pathed_hip.hip: renderPassFused, quadsKernel) fills the upper half of
+// RenderParams::smallQuads by it: one definition for both.
+template <bool COUNT, typename TRAITS>
+constexpr bool kSmallPrunes = !COUNT && std::is_same<TRAITS, TraitsLambertianTriangles>::value;
+template <typename TRAITS> struct TraitsTag { typedef TRAITS type; };
 
 // Phase 2 (a wave-level loop: call it from wave-uniform control flow, lanes without a ray pass empty masks):
 // the few candidates of each lane go through the ordinary intersector + acceptance rule.
@@ -3347,9 +3368,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                 // one instantiation of the pass: a wave without a single shadow ray is rare (3 % of the passes) and pays for
                 // the second ray's arithmetic rather than for a second copy of the loop's registers
                 if (tracing) {
-                    smallCandidatesItems<true, true, true>(smallTris.data, p.smallQuads, nTris, p.smallKappaT, path.o, path.d, shadowDirection,
-                                                            &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh,
-                                                            candidateNear(PATHED_TNEAR), candidateFar(shadowTfar));
+                    // The shadow ray leaves out the never-occluders' turns (smallCandidatesItems<PRUNE>) in the Cornell-like
+                    // instantiation, the headline's: its launch alone carries the turn counts in the upper half of smallQuads
+                    // (kSmallPrunes, pathed_hip.hip: renderPassFused).  The counting instantiations run every turn for both rays:
+                    // the library's own reference for the pruning.  The others compile as before.  Veach-like: pruned it LOST
+                    // 0.45 % on the Veach scene, which has no never-occluder to skip (7 408.7 -> 7 375.1 Msamples/s,
+                    // profiles/shadow_prune_profile.log).  The ladder's rungs and the any-BSDF instantiation: pruned, the latter's
+                    // scratch fell from 112 to 84 / 64 bytes per lane while a rung kept 104, and tests/test_kernel_resources.py
+                    // holds the rungs to no more than the instantiation they stand in for.
+                    constexpr bool kPrune = kSmallPrunes<COUNT, TRAITS>;
+                    const int smallQuads = kPrune ? (p.smallQuads & 0xFFFF) : p.smallQuads;
+                    smallCandidatesItems<true, true, true, kPrune>(smallTris.data, smallQuads, nTris, p.smallKappaT, path.o, path.d, shadowDirection,
+                                                                   &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh,
+                                                                   candidateNear(PATHED_TNEAR), candidateFar(shadowTfar),
+                                                                   (p.smallQuads >> 16) & 0xFF, (p.smallQuads >> 24) & 0xFF);
                     if (!traceShadow) { shadowLow = 0u; shadowHigh = 0u; }
                 }
             } else if (__ballot(traceShadow) != 0ull) {
@@ -3551,6 +3583,31 @@ __global__ __launch_bounds__(kBlock) void k_debug_small_candidates(DScene scene,
         unsigned long long *row = out + (size_t)8 * index;
         row[0] = valuA; row[1] = valuB; row[2] = mfmaA; row[3] = mfmaB; row[4] = acceptA; row[5] = acceptB; row[6] = itemsA; row[7] = itemsB;
     }
+}
+
+// Test hook behind pathed_hip_debug_shadow_candidates: the shadow ray's candidates as the non-counting k_path_small computes
+// them -- the item form with the never-occluders' turns left out (smallCandidatesItems<PRUNE>) -- and the set phase 2 accepts for
+// that ray, one bit per ORIGINAL primitive id.  Rays as k_debug_small_candidates takes them; two words per ray.
+__global__ __launch_bounds__(kBlock) void k_debug_shadow_candidates(DScene scene, SmallTris smallItems, int nQuads, float kappaT, int shadowQuadPairs, int shadowLonePairs,
+                                                                    const float4 *itemTris, const float *rays, int n, unsigned long long *out)
+{
+    const int index = blockIdx.x * kBlock + threadIdx.x;
+    const float *r = rays + (size_t)10 * index;
+    const V3 o = v3(r[0], r[1], r[2]), dA = v3(r[3], r[4], r[5]), dB = v3(r[6], r[7], r[8]);
+    const float tfarB = r[9];
+    const int nTris = scene.nTris;
+    unsigned int aLow, aHigh, bLow, bHigh;
+    smallCandidatesItems<true, true, true, true>(smallItems.data, nQuads, nTris, kappaT, o, dA, dB, &aLow, &aHigh, &bLow, &bHigh,
+                                                 candidateNear(PATHED_TNEAR), candidateFar(tfarB), shadowQuadPairs, shadowLonePairs);
+    unsigned long long candidates = 0, accepted = 0;
+    for (int k = 0; k < nTris; k++) {
+        const float4 t0 = itemTris[3 * k + 0], t1 = itemTris[3 * k + 1], t2 = itemTris[3 * k + 2];
+        const unsigned long long bit = 1ull << (floatAsInt(t0.w) & 63);
+        if (((k < 32 ? bLow : bHigh) >> (31 - (k & 31))) & 1u) { candidates |= bit; }
+        float t, u, v;
+        if (intersectTriangle(o, dB, v3(t0.x, t0.y, t0.z), v3(t1.x, t1.y, t1.z), v3(t2.x, t2.y, t2.z), &t, &u, &v) && t > PATHED_TNEAR && t <= tfarB) { accepted |= bit; }
+    }
+    if (index < n) { out[(size_t)2 * index] = candidates; out[(size_t)2 * index + 1] = accepted; }
 }
 
 // ------------------------------------------------------------------------- volume path kernel

@@ -284,6 +284,9 @@ struct PathedScene {
     DeviceBuffer<float4> itemTris;
     std::vector<float> itemTrisHost;       // host copy of itemTris (12 floats per triangle)
     std::vector<float> smallExtraPoints;   // sphere bounds: where else a ray may start (the camera is added when the records are built)
+    std::vector<unsigned char> smallEmitterPrims;   // per original primitive id: the triangle is a light (small_items.h: SmallLights)
+    std::vector<float> smallSphereLights;           // centre.xyz, radius of every sphere light: about center_sample, where sphereSample puts
+                                                    // the samples, and again about center_world (a transformed sphere has two centres)
     // PathedSceneOptions.refittable: the triangle soup stays on the device for pathed_hip_scene_refit
     bool refittable = false;
     DeviceBuffer<float> soupPositions, soupNormals, soupUvs;
@@ -1276,8 +1279,24 @@ static hipError_t rebuildSmallItems(PathedScene *scene)
     const int kMaxQuadMaterials = 64;
     const bool pairQuads = scene->options.generic_kernels == 0 && !tuningEnv("PATHED_NO_QUADS") && scene->device.nMaterials <= kMaxQuadMaterials;
     std::vector<float> ordered;
+    // where the shadow rays end (small_items.h: NEVER-OCCLUDERS): the items no shadow ray has to test go last in item order
+    std::vector<unsigned char> emitter((size_t)scene->device.nTris, 0);
+    bool lightsKnown = true;
+    for (int k = 0; k < scene->device.nTris; k++) {
+        int prim;
+        std::memcpy(&prim, &scene->bvh.leafTris[(size_t)12 * k + 3], sizeof prim);
+        if (prim < 0 || (size_t)prim >= scene->smallEmitterPrims.size()) { lightsKnown = false; break; }
+        emitter[(size_t)k] = scene->smallEmitterPrims[(size_t)prim];
+    }
+    SmallLights lights;
+    lights.known = lightsKnown;
+    lights.environment = scene->device.hasEnv != 0;
+    lights.emitter = emitter.data();
+    lights.spheres = scene->smallSphereLights.data();
+    lights.nSpheres = (int)(scene->smallSphereLights.size() / 4);
+    lights.nSurfacePoints = (int)(scene->smallExtraPoints.size() / 3);
     scene->smallLayout = buildSmallItems(scene->bvh.leafTris.data(), scene->device.nTris, points.data(), (int)(points.size() / 3), pairQuads, PATHED_TNEAR,
-                                         reinterpret_cast<float *>(scene->smallItems.data), &ordered);
+                                         reinterpret_cast<float *>(scene->smallItems.data), &ordered, &lights);
     std::vector<float4> records(ordered.size() / 4);
     std::memcpy(records.data(), ordered.data(), ordered.size() * sizeof(float));
     scene->itemTrisHost = ordered;
@@ -2289,6 +2308,19 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
             for (int a = 0; a < 3; a++) { scene->smallExtraPoints.push_back(desc->spheres[i].center_world[a] + sign * std::fabs(desc->spheres[i].radius) * 1.001f); }
         }
     }
+    scene->smallEmitterPrims.assign((size_t)desc->n_triangles, 0);
+    scene->smallSphereLights.clear();
+    for (const DLight &light : lights) {
+        if (light.kind == 0 && light.index >= 0 && (size_t)light.index < scene->smallEmitterPrims.size()) { scene->smallEmitterPrims[(size_t)light.index] = 1; }
+        if (light.kind == 1) {
+            // sampleLightsTerm samples the light about DSphere::centerSample, the intersector meets it about center_world: the
+            // rule is given both, so neither has to be told from the other
+            for (int a = 0; a < 3; a++) { scene->smallSphereLights.push_back(desc->spheres[light.index].center_sample[a]); }
+            scene->smallSphereLights.push_back(desc->spheres[light.index].radius);
+            for (int a = 0; a < 3; a++) { scene->smallSphereLights.push_back(desc->spheres[light.index].center_world[a]); }
+            scene->smallSphereLights.push_back(desc->spheres[light.index].radius);
+        }
+    }
     if ((status = rebuildSmallItems(scene)) != hipSuccess) { return fail_cleanup(status, "upload the phase-1 records"); }
     scene->mfmaPhase1 = false;
     std::memset(&scene->mfmaFrame, 0, sizeof scene->mfmaFrame);
@@ -2577,15 +2609,26 @@ static int renderPassFused(PathedScene *scene, const Pass &pass)
         } else
 #endif
         if (scene->smallLayout.nQuads > 0 && ldsMaterials) {
+            // (the instantiations that prune the shadow ray's phase 1 -- kernels.h kSmallPrunes<COUNT, TRAITS>, the constant the kernel
+            // itself branches on -- read the turns it runs from the upper half of smallQuads; the others read the word whole, so
+            // quadsKernel sets that half for exactly those and hands out the instantiation in the same breath)
+            const auto quadsKernel = [&](auto COUNT, auto traitsTag) -> void (*)(RenderParams, SmallTris) {
+                using TRAITS = typename decltype(traitsTag)::type;
+                if (kSmallPrunes<decltype(COUNT)::value, TRAITS>) {
+                    params.smallQuads = scene->smallLayout.nQuads | scene->smallLayout.shadowQuadPairs << 16 | scene->smallLayout.shadowLonePairs << 24;
+                }
+                return k_path_small<true, decltype(COUNT)::value, TRAITS, false, true>;
+            };
             // some triangles are halves of parallelograms: phase 1 tests those as parallelograms (small_items.h).  The rough, smooth
             // and triangle-lit sets have no counting instantiation: a counting call of such a scene takes TraitsAll
-            if (traits.lambertianTriangles) { withBool(count, [&](auto COUNT) { run(k_path_small<true, COUNT, TraitsLambertianTriangles, false, true>); }); }
-            else if (traits.lambertianPlasticSpheres) { withBool(count, [&](auto COUNT) { run(k_path_small<true, COUNT, TraitsLambertianPlasticSpheres, false, true>); }); }
-            else if (traits.roughBeckmann && !count) { run(k_path_small<true, false, TraitsRoughBeckmann, false, true>); }
-            else if (traits.roughGgx && !count) { run(k_path_small<true, false, TraitsRoughGgx, false, true>); }
-            else if (traits.smoothSet && !count) { run(k_path_small<true, false, TraitsSmooth, false, true>); }
-            else if (traits.triangleLit && !count) { run(k_path_small<true, false, TraitsTriangleLit, false, true>); }
-            else { withBool(count, [&](auto COUNT) { run(k_path_small<true, COUNT, TraitsAll, false, true>); }); }
+            const std::false_type plain{};
+            if (traits.lambertianTriangles) { withBool(count, [&](auto COUNT) { run(quadsKernel(COUNT, TraitsTag<TraitsLambertianTriangles>())); }); }
+            else if (traits.lambertianPlasticSpheres) { withBool(count, [&](auto COUNT) { run(quadsKernel(COUNT, TraitsTag<TraitsLambertianPlasticSpheres>())); }); }
+            else if (traits.roughBeckmann && !count) { run(quadsKernel(plain, TraitsTag<TraitsRoughBeckmann>())); }
+            else if (traits.roughGgx && !count) { run(quadsKernel(plain, TraitsTag<TraitsRoughGgx>())); }
+            else if (traits.smoothSet && !count) { run(quadsKernel(plain, TraitsTag<TraitsSmooth>())); }
+            else if (traits.triangleLit && !count) { run(quadsKernel(plain, TraitsTag<TraitsTriangleLit>())); }
+            else { withBool(count, [&](auto COUNT) { run(quadsKernel(COUNT, TraitsTag<TraitsAll>())); }); }
         } else if (traits.lambertianTriangles) {
             withBool(ldsMaterials, [&](auto LDS_MATERIALS) { withBool(count, [&](auto COUNT) { run(k_path_small<LDS_MATERIALS, COUNT, TraitsLambertianTriangles>); }); });
         } else if (traits.lambertianPlasticSpheres && ldsMaterials) {
@@ -3725,6 +3768,38 @@ int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, siz
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, deviceOut.ptr, n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PATHED_OK;
+}
+
+int pathed_hip_debug_shadow_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out, int32_t *layout, uint64_t *never_occluders)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector's hook does not serve scenes with instances"); }
+    if (!scene->bruteForce || scene->device.nTris < 1) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector serves scenes of 1..64 triangles"); }
+    if (!layout || !never_occluders) { return fail(PATHED_E_INVALID, "null layout or never-occluder buffer"); }
+    layout[0] = scene->smallLayout.nQuads;
+    layout[1] = scene->smallLayout.nLone;
+    layout[2] = scene->smallLayout.shadowQuadPairs;
+    layout[3] = scene->smallLayout.shadowLonePairs;
+    *never_occluders = scene->smallLayout.neverOccluders;
+    if (n == 0) { return PATHED_OK; }
+    if (!rays || !out) { return fail(PATHED_E_INVALID, "null ray or output buffer"); }
+    if (n > (size_t)1 << 24) { return fail(PATHED_E_INVALID, "too many rays in one call"); }
+    SELECT_DEVICE(scene);
+    const size_t padded = (n + kBlock - 1) / kBlock * kBlock;   // whole blocks: the kernel reads a ray per lane
+    std::vector<float> hostRays(padded * 10, 0.f);
+    std::memcpy(hostRays.data(), rays, n * 10 * sizeof(float));
+    for (size_t i = n; i < padded; i++) { hostRays[10 * i + 5] = 1.f; hostRays[10 * i + 8] = 1.f; }
+    DeviceBuffer<float> deviceRays;
+    DeviceBuffer<unsigned long long> deviceOut;
+    HIP_TRY(deviceRays.upload(hostRays));
+    HIP_TRY(deviceOut.allocate(n * 2));
+    hipLaunchKernelGGL(k_debug_shadow_candidates, dim3((unsigned)(padded / kBlock)), dim3(kBlock), 0, nullptr, scene->device, scene->smallItems,
+                       scene->smallLayout.nQuads, scene->smallLayout.kappaT, scene->smallLayout.shadowQuadPairs, scene->smallLayout.shadowLonePairs,
+                       scene->itemTris.ptr, deviceRays.ptr, (int)n, deviceOut.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, deviceOut.ptr, n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PATHED_OK;
 }
 

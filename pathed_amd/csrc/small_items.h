@@ -26,6 +26,46 @@
 // det cannot be trusted; every bound is then at most Xmax E_det in size, which the K terms include: nothing is rejected there.  The far bound's error grows with the ray's own tfar:
 // tolFar = tolT + tfarHigh (kappa_far det^2 + E_det^2 / (4 kappa_far)), kappa_far = 1e-6 (a light 20 units away is told from
 // an occluder 1e-3 in front of it with 2e-5 of slack).  Triangles that find no partner keep the exact test.
+//
+// NEVER-OCCLUDERS (smallNeverOccluders below).  A shadow ray (kernels.h: sampleLightsTerm) leaves a point found on a scene
+// surface towards a point sampled on an emitter, |d| = 1 up to rounding, accepted hits in (tnear, distance - 1e-3].  A triangle
+// Y that lies in a supporting plane of everything such a ray can start on, with every emitter well off that plane, can only
+// be met within a hair of the origin, below tnear, where phase 2 rejects the hit: the shadow ray need not test it at all (the
+// walls of a room).  Such items are put LAST in item order and the shadow ray's half of phase 1 stops before them.  With Y's
+// plane (unit normal n, offset c, either orientation), s(x) = n . x - c, Y qualifies when
+//     (1) s >= -eta   at every corner of every scene triangle (as the intersector sees them) and over every sphere's bounds,
+//     (2) s >= Dmin   at every point a light sample can land on,
+// with, u = 2^-24, R = the diameter of everything including the camera, L = the diameter of the surfaces alone (the longest
+// shadow ray), M = the largest coordinate, k(X) = |e1||e2| / |e1 x e2| of triangle X (1 / sin of the angle at v0):
+//
+// eta bounds how far an origin isect.point = fl(o + d t) sits off the plane of the triangle X it was found on.  Phase 2
+// (trace.h: intersectTriangle) computes t = fl(N' / det'), N' = N + dN, det' = det + dDet the rounded triple products
+// N = e2 . ((o - v0) x e1), det = e1 . (d x e2); the exact point o + d t has the offset (t det - N) / |e1 x e2| from X's plane, and
+// t det - N = t det' - N' - t dDet + dN, |t det' - N'| <= u |N'| (the division).  With the error model above, 8 u per triple
+// product (|dN| <= 8 u |o - v0||e1||e2|, |dDet| <= 8 u |d||e1||e2|), |o - v0| <= R and t <= R (the largest t the scene and camera
+// allow: premise -- a hit whose det is all rounding can report any t, and then no bound on its point exists, here or anywhere else
+// in this file), and 3 u (M + R) for the two roundings per component of o + d t:
+//     eta = 1.01 (u R + 16 u R max_X k(X)) + 1.01 x 3 u (M + R).
+// (The point is taken to lie inside X along X's plane: how far a grazing hit may overshoot X's edge is not modelled.)
+// Sphere origins: intersectSphere's t lies in the true chord up to sqrt(32 u) R (the root of a difference rounded to 16 u R^2),
+// so a point found on a sphere is within etaSphere = eta + 1.1 sqrt(32 u) R of the sphere's bounds; (1) asks s >= etaSphere - eta
+// of those bounds.
+//
+// Dmin: s is linear along the segment, from s0 >= -2 eta (a corner's -eta and the origin's own eta off its triangle) to s1 >= Dmin
+// over a length <= L.  It can meet Y (|s| <= eta at Y's corners, checked) only where s <= eta: if s0 > eta nowhere at t > 0 short
+// of the light; else it leaves the slab at t* = (eta - s0) L / (s1 - s0) <= 3 eta L / (Dmin - eta), which is 3/8 tnear with
+//     Dmin = eta + 2 eta L x 4 / tnear
+// (tnear / 4 for origins that are themselves within the slab).  The other tnear / 2 cover phase 2's own t for Y.  Origins with s0 <= Dmin / 2 climb at sin(phi) >= Dmin / (2 L): the true
+// crossing is at t <= tnear / 4 (or behind the origin), the computed one at most
+//     Et = 1.01 x 8 u (L + tnear) k(Y) / (Dmin / (2 L) - 8 u k(Y)) + u tnear
+// further, and Et <= tnear / 2 is CHECKED per triangle (margin A).  Origins with s0 > Dmin / 2 stay above min(s0, s1) >= Dmin / 2
+// all the way to the light: an accepted t <= distance would need N' / |det'| <= distance, i.e. min(s0, s1) |e1 x e2| <= |dN| +
+// distance |dDet| <= 16 u L |e1||e2|; Dmin / 2 > 1.01 x 16 u L k(Y) is checked as well (margin B).  Emitters: a sample
+// p0 a + p1 b + p2 c of the light's float corners is within 16 u M of their hull, a sphere light's within 16 u M of radius x 1.001
+// of its centre: (2) is asked with that slack.  NaN, a degenerate Y, a failed margin, an environment light (its shadow rays have no end),
+// a caller that cannot name the emitters: the triangle is an occluder.  A quad is a never-occluder when both halves are.
+// Cornell (extent 3.49, camera 6.8 away, max k = 2.4): eta = 2.1e-5, Dmin = 0.59; the light is 1.98 / 0.82 / 0.77 / 0.78 from floor, back,
+// right and left wall, 0.01 from the ceiling: 3 of the 17 quads and the two lone triangles.
 #pragma once
 
 #include <algorithm>
@@ -45,13 +85,132 @@ struct SmallItemsLayout {
     int nQuads = 0;          // parallelograms: item-order triangles 2 q (A: beta <= alpha) and 2 q + 1 (B)
     int nLone = 0;           // triangles without a partner: item-order 2 nQuads + k
     float kappaT = 0.f;      // absolute slack of the t bounds per det^2 (a length): a sixteenth of tnear
+    // never-occluders come last in both sections: the turns of phase 1 a SHADOW ray needs (an odd count of the others: the pair
+    // that straddles the boundary is run for both rays)
+    int shadowQuadPairs = 0; // <= (nQuads + 1) / 2
+    int shadowLonePairs = 0; // <= (nLone + 1) / 2
+    unsigned long long neverOccluders = 0ull;   // bit (original primitive id & 63)
+    double eta = 0.0, dMin = 0.0;               // what the rule was run with (0: not run)
 };
+
+// Where the shadow rays of a scene end, for smallNeverOccluders.  known = false (the default): nothing is marked.
+struct SmallLights {
+    bool known = false;
+    bool environment = false;               // an environment light: shadow rays without an end point
+    const unsigned char *emitter = nullptr; // per triangle, in the order of leafTris: its material emits
+    const float *spheres = nullptr;         // sphere lights: centre.xyz, radius
+    int nSpheres = 0;
+    int nSurfacePoints = 0;                 // the first extraPoints are surface bounds, (lo, hi) per sphere; the rest (the camera) are not
+};
+
+// marks[k] = 1: triangle k of leafTris can never occlude a shadow ray (header: NEVER-OCCLUDERS).  extraPoints as buildSmallItems takes them.
+inline void smallNeverOccluders(const float *leafTris, int nTris, const float *extraPoints, int nExtra, const SmallLights &lights, float tnear,
+                                std::vector<unsigned char> *marks, double *etaOut = nullptr, double *dMinOut = nullptr)
+{
+    marks->assign((size_t)std::max(nTris, 0), 0);
+    if (etaOut) { *etaOut = 0.0; }
+    if (dMinOut) { *dMinOut = 0.0; }
+    if (!lights.known || lights.environment || nTris <= 0 || !lights.emitter || !(tnear > 0.f)) { return; }
+    const double unit = 1.0 / 16777216.0;
+    const int nSurface = std::min(std::max(lights.nSurfacePoints, 0), nExtra) & ~1;
+    struct Tri { double p[3][3], k; };
+    std::vector<Tri> tris((size_t)nTris);
+    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 }, sLo[3], sHi[3], largest = 0.0, kMax = 0.0;
+    auto cover = [&](const double *point) {
+        for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], point[a]); hi[a] = std::max(hi[a], point[a]); largest = std::max(largest, std::fabs(point[a])); }
+    };
+    auto cross = [](const double *a, const double *b, double *out) {
+        out[0] = a[1] * b[2] - a[2] * b[1]; out[1] = a[2] * b[0] - a[0] * b[2]; out[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    auto norm = [](const double *a) { return std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); };
+    for (int t = 0; t < nTris; t++) {
+        const float *tri = leafTris + (size_t)12 * t;
+        double e1[3], e2[3], n[3];
+        for (int a = 0; a < 3; a++) {
+            e1[a] = tri[4 + a]; e2[a] = tri[8 + a];
+            tris[t].p[0][a] = tri[a]; tris[t].p[1][a] = (double)tri[a] + e1[a]; tris[t].p[2][a] = (double)tri[a] + e2[a];
+        }
+        for (int c = 0; c < 3; c++) { cover(tris[t].p[c]); }
+        cross(e1, e2, n);
+        const double area2 = norm(n), edges = norm(e1) * norm(e2);
+        tris[t].k = area2 > 0.0 ? edges / area2 : 1e300;
+        if (!(tris[t].k >= 1.0)) { tris[t].k = 1e300; }   // NaN
+        if (!(edges == 0.0)) { kMax = std::max(kMax, tris[t].k); }   // (a triangle of zero edges has det = 0 exactly: never hit)
+    }
+    for (int i = 0; i < nSurface; i++) {
+        const double point[3] = { extraPoints[3 * i], extraPoints[3 * i + 1], extraPoints[3 * i + 2] };
+        cover(point);
+    }
+    for (int a = 0; a < 3; a++) { sLo[a] = lo[a]; sHi[a] = hi[a]; }
+    for (int i = nSurface; i < nExtra; i++) {
+        const double point[3] = { extraPoints[3 * i], extraPoints[3 * i + 1], extraPoints[3 * i + 2] };
+        cover(point);
+    }
+    auto diagonal = [](const double *from, const double *to) {
+        double sum = 0.0;
+        for (int a = 0; a < 3; a++) { if (to[a] > from[a]) { sum += (to[a] - from[a]) * (to[a] - from[a]); } }
+        return std::sqrt(sum) * 1.001;
+    };
+    const double R = diagonal(lo, hi), L = diagonal(sLo, sHi);
+    const double eta = 1.01 * (unit * R + 16.0 * unit * R * kMax) + 1.01 * 3.0 * unit * (largest + R);
+    const double etaSphere = 1.1 * std::sqrt(32.0 * unit) * R;   // beyond eta, for points found on spheres
+    const double dMin = eta + 2.0 * eta * L * 4.0 / tnear;
+    const double emitterSlack = 16.0 * unit * largest;
+    if (!(eta > 0.0) || !(dMin > 0.0) || !(dMin < 1e300)) { return; }
+    if (etaOut) { *etaOut = eta; }
+    if (dMinOut) { *dMinOut = dMin; }
+    bool anyEmitter = lights.nSpheres > 0;
+    for (int t = 0; t < nTris; t++) { anyEmitter = anyEmitter || lights.emitter[t] != 0; }
+    if (!anyEmitter) { return; }   // no shadow rays at all: nothing to gain
+
+    for (int y = 0; y < nTris; y++) {
+        const Tri &Y = tris[y];
+        // margins A and B (header)
+        const double climb = dMin / (2.0 * L) - 8.0 * unit * Y.k;
+        if (!(climb > 0.0)) { continue; }
+        const double eT = 1.01 * 8.0 * unit * (L + tnear) * Y.k / climb + unit * tnear;
+        if (!(eT <= 0.5 * tnear)) { continue; }
+        if (!(0.5 * dMin > 1.01 * 16.0 * unit * L * Y.k)) { continue; }
+        double e1[3], e2[3], n[3];
+        for (int a = 0; a < 3; a++) { e1[a] = Y.p[1][a] - Y.p[0][a]; e2[a] = Y.p[2][a] - Y.p[0][a]; }
+        cross(e1, e2, n);
+        const double length = norm(n);
+        if (!(length > 1e-12 * norm(e1) * norm(e2)) || !(length > 0.0)) { continue; }   // degenerate
+        for (int a = 0; a < 3; a++) { n[a] /= length; }
+        for (int orientation = 0; orientation < 2 && !(*marks)[y]; orientation++) {
+            const double sign = orientation ? -1.0 : 1.0;
+            const double c = sign * (n[0] * Y.p[0][0] + n[1] * Y.p[0][1] + n[2] * Y.p[0][2]);
+            auto s = [&](const double *x) { return sign * (n[0] * x[0] + n[1] * x[1] + n[2] * x[2]) - c; };
+            bool holds = true;
+            for (int corner = 0; corner < 3 && holds; corner++) { holds = std::fabs(s(Y.p[corner])) <= eta; }
+            for (int t = 0; t < nTris && holds; t++) {
+                for (int corner = 0; corner < 3 && holds; corner++) {
+                    const double value = s(tris[t].p[corner]);
+                    holds = value >= -eta && (!lights.emitter[t] || value >= dMin + emitterSlack);
+                }
+            }
+            for (int i = 0; i + 1 < nSurface && holds; i += 2) {   // the least of s over a sphere's bounds
+                const float *a = extraPoints + 3 * i, *b = a + 3;
+                double least = -c;
+                for (int x = 0; x < 3; x++) { least += std::min(sign * n[x] * (double)a[x], sign * n[x] * (double)b[x]); }
+                holds = least >= etaSphere;
+            }
+            for (int i = 0; i < lights.nSpheres && holds; i++) {
+                const float *sphere = lights.spheres + 4 * i;
+                const double centre[3] = { sphere[0], sphere[1], sphere[2] };
+                holds = s(centre) - std::fabs((double)sphere[3]) * 1.001 >= dMin + emitterSlack;
+            }
+            if (holds) { (*marks)[y] = 1; }
+        }
+    }
+}
 
 // leafTris: 12 floats per triangle, (v0, prim) (e1, -) (e2, -).  extraPoints: origins rays may have besides the triangles
 // themselves (the camera; sphere bounds).  records: kSmallItemFloats floats, [pair of parallelograms][component][half], then
 // the lone pairs as SmallTris stores them.  itemTris: the 12-float records again, in ITEM order (what phase 2 indexes).
+// lights: where the scene's shadow rays end (SmallLights); without it no item is a never-occluder and the order is the former one.
 inline SmallItemsLayout buildSmallItems(const float *leafTris, int nTris, const float *extraPoints, int nExtra, bool pairQuads, float tnear,
-                                        float *records, std::vector<float> *itemTris)
+                                        float *records, std::vector<float> *itemTris, const SmallLights *lights = nullptr)
 {
     SmallItemsLayout layout;
     std::memset(records, 0, sizeof(float) * kSmallItemFloats);
@@ -188,6 +347,26 @@ inline SmallItemsLayout buildSmallItems(const float *leafTris, int nTris, const 
     layout.nQuads = (int)quads.size();
     layout.nLone = nTris - 2 * layout.nQuads;
 
+    // ---- never-occluders last, in both sections (header); the order within each group stays what it was
+    std::vector<unsigned char> never;
+    smallNeverOccluders(leafTris, nTris, extraPoints, nExtra, lights ? *lights : SmallLights(), tnear, &never, &layout.eta, &layout.dMin);
+    auto neverQuad = [&](const Quad &quad) { return never[quad.a] && never[quad.b]; };
+    std::stable_partition(quads.begin(), quads.end(), [&](const Quad &quad) { return !neverQuad(quad); });
+    int occluderQuads = 0, occluderLone = 0;
+    for (const Quad &quad : quads) { occluderQuads += neverQuad(quad) ? 0 : 1; }
+    std::vector<int> loneOrder;
+    for (int pass = 0; pass < 2; pass++) {
+        for (int t = 0; t < nTris; t++) {
+            if (partner[t] < 0 && (never[t] != 0) == (pass == 1)) { loneOrder.push_back(t); }
+        }
+        if (pass == 0) { occluderLone = (int)loneOrder.size(); }
+    }
+    layout.shadowQuadPairs = (occluderQuads + 1) / 2;
+    layout.shadowLonePairs = (occluderLone + 1) / 2;
+    auto primitive = [&](int t) { int id; std::memcpy(&id, leafTris + (size_t)12 * t + 3, sizeof id); return id; };
+    for (int q = occluderQuads; q < layout.nQuads; q++) { layout.neverOccluders |= 1ull << (primitive(quads[q].a) & 63) | 1ull << (primitive(quads[q].b) & 63); }
+    for (int k = occluderLone; k < layout.nLone; k++) { layout.neverOccluders |= 1ull << (primitive(loneOrder[k]) & 63); }
+
     // ---- records
     const double kappa = kSmallKappa, kappaT = layout.kappaT;
     for (int q = 0; q < layout.nQuads; q++) {
@@ -224,8 +403,7 @@ inline SmallItemsLayout buildSmallItems(const float *leafTris, int nTris, const 
     }
     float *lone = records + (size_t)2 * kSmallQuadWords * ((layout.nQuads + 1) / 2);
     int k = 0;
-    for (int t = 0; t < nTris; t++) {
-        if (partner[t] >= 0) { continue; }
+    for (int t : loneOrder) {
         const float *tri = leafTris + (size_t)12 * t;
         float *record = lone + (size_t)2 * kSmallLoneWords * (k / 2);
         for (int row = 0; row < 3; row++) {

@@ -387,6 +387,20 @@ class HipScene:
         _check(self._lib, code, "pathed_hip_debug_small_candidates")
         return out
 
+    def shadow_candidates(self, rays):
+        """The shadow ray's pruned phase-1 candidates and the set phase 2 accepts for it (pathed_hip_debug_shadow_candidates):
+        rays (n, 10) as small_candidates takes them -> ((n, 2) uint64, bit p = primitive id p; the layout's counts as a dict;
+        the never-occluder set as an int, bit p = primitive id p)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 10)
+        out = np.zeros((rays.shape[0], 2), dtype=np.uint64)
+        layout = (C.c_int32 * 4)()
+        never = C.c_uint64(0)
+        code = self._lib.pathed_hip_debug_shadow_candidates(
+            self._handle, rays.ctypes.data_as(C.POINTER(C.c_float)), rays.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint64)), layout, C.byref(never))
+        _check(self._lib, code, "pathed_hip_debug_shadow_candidates")
+        counts = {"quads": layout[0], "lone": layout[1], "shadow_quad_pairs": layout[2], "shadow_lone_pairs": layout[3]}
+        return out, counts, int(never.value)
+
     def camera_masks(self):
         """The per-pixel candidate masks of the camera rays (pathed_hip_debug_camera_masks; scenes on the fused path kernel):
         (height, width) uint64, bit 63 - k = triangle k of the item order."""

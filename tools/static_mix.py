@@ -99,6 +99,8 @@ def main():
     parser.add_argument("--bench-json", default="", help="write the trip-count-weighted mix of the Cornell instantiation of k_path_small (what bench.py times) here")
     parser.add_argument("--quad-pairs", type=int, default=9, help="trips of the parallelogram-pair loop per pass (Cornell: 17 parallelograms)")
     parser.add_argument("--lone-pairs", type=int, default=1, help="trips of the lone-triangle-pair loop per pass (Cornell: 2 triangles)")
+    parser.add_argument("--shadow-quad-pairs", type=int, default=7, help="... of them run for the shadow ray as well (Cornell: 14 occluder parallelograms)")
+    parser.add_argument("--shadow-lone-pairs", type=int, default=0, help="lone-pair trips that run for the shadow ray as well (Cornell: none)")
     args = parser.parse_args()
     path = args.asm
     if not path:
@@ -163,16 +165,34 @@ def write_bench_mix(kernels, pretty, args):
         total = collections.Counter()
         for block in blocks.values():
             total.update(block["ops"])
+        # the phase-1 loops, in program order: innermost backward branches over at least 40 packed instructions.  With the shadow
+        # ray's pruning (kernels.h smallCandidatesItems<PRUNE>) there are three: parallelogram pairs for both rays, parallelogram
+        # pairs for the path's ray alone, and the lone pairs, whose shadow half is a block of its own between the loop's first
+        # and last block.  Without it two single-block loops, the larger one the parallelogram pairs.
+        order = list(blocks)
+        index = {label: i for i, label in enumerate(order)}
         loops = []
-        for label, block in blocks.items():
-            if label in block["targets"] and block["ops"]["valu_packed"] >= 40:
-                loops.append((block["ops"]["valu_packed"], label))
-        loops.sort(reverse=True)
+        for i, label in enumerate(order):
+            for target in blocks[label]["targets"]:
+                if target in index and index[target] <= i:
+                    body = order[index[target]:i + 1]
+                    if sum(blocks[inner]["ops"]["valu_packed"] for inner in body) >= 40 and not any(set(body) & set(other) for other in loops):
+                        loops.append(body)
         weights = {}
-        if len(loops) >= 1:
-            weights[loops[0][1]] = args.quad_pairs
-        if len(loops) >= 2:
-            weights[loops[1][1]] = args.lone_pairs
+        if len(loops) >= 3:
+            pruned = "; the shadow ray runs %d of the parallelogram-pair turns and %d of the lone-pair turns" % (args.shadow_quad_pairs, args.shadow_lone_pairs)
+            for inner in loops[0]:
+                weights[inner] = args.shadow_quad_pairs
+            for inner in loops[1]:
+                weights[inner] = args.quad_pairs - args.shadow_quad_pairs
+            for inner in loops[2]:
+                weights[inner] = args.lone_pairs if inner in (loops[2][0], loops[2][-1]) else args.shadow_lone_pairs
+        else:
+            pruned = ""
+            loops.sort(key=lambda body: -sum(blocks[inner]["ops"]["valu_packed"] for inner in body))
+            for body, trips in zip(loops, (args.quad_pairs, args.lone_pairs)):
+                for inner in body:
+                    weights[inner] = trips
         weighted = collections.Counter()
         for label, block in blocks.items():
             for key, count in block["ops"].items():
@@ -181,11 +201,11 @@ def write_bench_mix(kernels, pretty, args):
         result = {
             "kernel": shown, "kernel_sources": sources_digest(),
             "method": "compiler assembly (hipcc -S), every basic block once, the parallelogram-pair loop x %d and the lone-pair loop x %d "
-                      "(their trip counts on scenes/cornell.json); v_div_scale / v_div_fmas / v_div_fixup counted with the plain instructions.  "
+                      "(their trip counts on scenes/cornell.json%s); v_div_scale / v_div_fmas / v_div_fixup counted with the plain instructions.  "
                       "The refill of the camera queue (unit bookkeeping, camera ray, the pixel's candidate mask, phase 2; it holds no "
                       "copy of the phase-1 loops) is counted once per iteration like every block although it ran in 0.196 of the "
                       "iterations when it was measured (profiles/camera_queue_profile.log, scenes/cornell.json): valu_per_iteration "
-                      "overstates the loop by about four fifths of the refill's static instructions" % (args.quad_pairs, args.lone_pairs),
+                      "overstates the loop by about four fifths of the refill's static instructions" % (args.quad_pairs, args.lone_pairs, pruned),
             "loops": {label: {"trips": trips, "valu": sum(v for k, v in blocks[label]["ops"].items() if k.startswith("valu")),
                               "packed": blocks[label]["ops"]["valu_packed"]} for label, trips in weights.items()},
             "valu_per_iteration": sum(valu.values()),
