@@ -11,6 +11,7 @@
 #include "kernels_experiments.h"
 #endif
 #include "lbvh.h"
+#include "scene_tables.h"
 
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -171,6 +173,7 @@ struct EventRing {
 }  // namespace
 
 static const int kMaxPools = 4;
+static_assert(kOptionMaxPools == kMaxPools && kOptionMinSlots == kBlock, "scene_tables.h: checkSceneOptions states these limits in its messages");
 static const int kDefaultShadeLaunches = 1;   // shade launches per trace launch of a scene with local rays (PathedSceneOptions.shade_launches = 0): more were
 // measured and lose -- the shade kernel is the slower partner, profiles/r5_ab_local_rays.log
 static const int kDefaultSmallPhase1 = 1;   // PathedSceneOptions.small_phase1 = 0: 1 VALU, 2 matrix pipe
@@ -417,18 +420,12 @@ DMaterial buildMaterial(const PathedMaterial &m)
 
 bool emits(const DMaterial &m) { return !(m.emit[0] == 0.f && m.emit[1] == 0.f && m.emit[2] == 0.f); }
 
-// Distribution ctor, reference src/distribution.cpp:6-33 (sequential float accumulation)
-bool buildCdf(const float *values, size_t size, float *cdf)
+// a float array the device reads as float4 (nodes, leaf triangles, the records of scene_tables.h)
+std::vector<float4> asQuads(const std::vector<float> &floats)
 {
-    float sum = 0.f;
-    for (size_t i = 0; i < size; i++) { sum += values[i]; cdf[i] = 0.f; }
-    if (sum == 0.f) { return true; }  // empty
-    for (size_t i = 0; i < size; i++) {
-        cdf[i] = values[i] / sum;
-        if (i > 0) { cdf[i] += cdf[i - 1]; }
-    }
-    cdf[size - 1] = 1.f;
-    return false;
+    std::vector<float4> quads(floats.size() / 4);
+    std::memcpy(quads.data(), floats.data(), quads.size() * sizeof(float4));
+    return quads;
 }
 
 int validate(const PathedSceneDesc *desc)
@@ -1297,10 +1294,8 @@ static hipError_t rebuildSmallItems(PathedScene *scene)
     lights.nSurfacePoints = (int)(scene->smallExtraPoints.size() / 3);
     scene->smallLayout = buildSmallItems(scene->bvh.leafTris.data(), scene->device.nTris, points.data(), (int)(points.size() / 3), pairQuads, PATHED_TNEAR,
                                          reinterpret_cast<float *>(scene->smallItems.data), &ordered, &lights);
-    std::vector<float4> records(ordered.size() / 4);
-    std::memcpy(records.data(), ordered.data(), ordered.size() * sizeof(float));
     scene->itemTrisHost = ordered;
-    const hipError_t status = scene->itemTris.upload(records);
+    const hipError_t status = scene->itemTris.upload(asQuads(ordered));
     if (status == hipSuccess && scene->mfmaPhase1) {
         // (experiments build) the matrix-pipe rows are expressed in a frame centred on the camera: a new camera is a new table,
         // or phase 1 stops being conservative for rays that start far from the old one
@@ -1358,9 +1353,7 @@ static hipError_t rebuildHybridItems(PathedScene *scene)
     std::vector<float> ordered;
     scene->hybridLayout = buildSmallItems(scene->hybridDirectLeaf.data(), scene->hybridDirectTris, points.data(), (int)(points.size() / 3), true, PATHED_TNEAR,
                                           reinterpret_cast<float *>(scene->hybridItems.data), &ordered);
-    std::vector<float4> records(ordered.size() / 4);
-    std::memcpy(records.data(), ordered.data(), ordered.size() * sizeof(float));
-    return scene->hybridItemTris.upload(records);
+    return scene->hybridItemTris.upload(asQuads(ordered));
 }
 
 // [r5] The wavefront's local rays: a sphere-free BVH scene with at most kMaxLocalTris LARGE triangles (each at least 1 / 256 of
@@ -1371,52 +1364,21 @@ static void buildLocalSet(PathedScene *scene, const PathedSceneDesc *desc)
     scene->localCount = 0;
     const uint32_t n = desc->n_triangles;
     if (n == 0 || desc->n_spheres != 0) { return; }
-    std::vector<double> area(n);
-    double total = 0.0;
+    const TriangleAreas areas = triangleAreas(desc);
+    std::vector<uint32_t> large, rest;   // triangles; vertex indices
     for (uint32_t i = 0; i < n; i++) {
-        const float *a = desc->positions + 3 * (size_t)desc->indices[3 * i], *b = desc->positions + 3 * (size_t)desc->indices[3 * i + 1], *c = desc->positions + 3 * (size_t)desc->indices[3 * i + 2];
-        const double e1[3] = { (double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2] }, e2[3] = { (double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2] };
-        const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-        area[i] = 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz);
-        total += area[i];
-    }
-    std::vector<uint32_t> large;
-    for (uint32_t i = 0; i < n; i++) {
-        if (area[i] * 256.0 >= total) {
+        if (areas.large(i)) {
             large.push_back(i);
             if (large.size() > (size_t)kMaxLocalTris) { return; }   // a scene of many large faces: no "rest" worth culling against
+        } else {
+            rest.insert(rest.end(), desc->indices + 3 * (size_t)i, desc->indices + 3 * (size_t)i + 3);
         }
     }
     if (large.empty() || large.size() == n) { return; }
-    std::vector<char> isLarge(n, 0);
-    for (uint32_t i : large) { isLarge[i] = 1; }
-    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
-    for (uint32_t i = 0; i < n; i++) {
-        if (isLarge[i]) { continue; }
-        for (int k = 0; k < 3; k++) {
-            const float *v = desc->positions + 3 * (size_t)desc->indices[3 * i + k];
-            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], (double)v[a]); hi[a] = std::max(hi[a], (double)v[a]); }
-        }
-    }
-    double extent = 0.0, centre[3], radius2 = 0.0;
-    for (int a = 0; a < 3; a++) { extent = std::max(extent, std::max(hi[a] - lo[a], std::max(std::fabs(lo[a]), std::fabs(hi[a])))); }
-    for (int a = 0; a < 3; a++) { centre[a] = (double)(float)(0.5 * (lo[a] + hi[a])); }
-    for (uint32_t i = 0; i < n; i++) {
-        if (isLarge[i]) { continue; }
-        for (int k = 0; k < 3; k++) {
-            const float *v = desc->positions + 3 * (size_t)desc->indices[3 * i + k];
-            double d2 = 0.0;
-            for (int a = 0; a < 3; a++) { const double d = (double)v[a] - centre[a]; d2 += d * d; }
-            radius2 = std::max(radius2, d2);
-        }
-    }
-    const double radius = std::sqrt(radius2) * 1.0001 + 1e-4 * extent + 1e-30;
-    for (int a = 0; a < 3; a++) {
-        scene->localLo[a] = (float)(lo[a] - 1e-4 * extent - 1e-30);
-        scene->localHi[a] = (float)(hi[a] + 1e-4 * extent + 1e-30);
-        scene->localSphere[a] = (float)centre[a];
-    }
-    scene->localSphere[3] = (float)(radius * radius * 1.00001);
+    const RestProxy proxy = restProxy(desc->positions, rest);
+    std::memcpy(scene->localLo, proxy.lo, sizeof proxy.lo);
+    std::memcpy(scene->localHi, proxy.hi, sizeof proxy.hi);
+    std::memcpy(scene->localSphere, proxy.sphere, sizeof proxy.sphere);
     for (size_t k = 0; k < large.size(); k++) {
         const uint32_t i = large[k];
         const float *v0 = desc->positions + 3 * (size_t)desc->indices[3 * i], *v1 = desc->positions + 3 * (size_t)desc->indices[3 * i + 1], *v2 = desc->positions + 3 * (size_t)desc->indices[3 * i + 2];
@@ -1437,24 +1399,19 @@ static void buildLocalSet(PathedScene *scene, const PathedSceneDesc *desc)
 static hipError_t buildHybrid(PathedScene *scene, const PathedSceneDesc *desc)
 {
     const uint32_t n = desc->n_triangles;
-    std::vector<double> area(n);
-    double total = 0.0;
-    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
-    for (uint32_t i = 0; i < n; i++) {
-        const float *a = desc->positions + 3 * (size_t)desc->indices[3 * i], *b = desc->positions + 3 * (size_t)desc->indices[3 * i + 1], *c = desc->positions + 3 * (size_t)desc->indices[3 * i + 2];
-        const double e1[3] = { (double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2] }, e2[3] = { (double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2] };
-        const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-        area[i] = 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz);
-        total += area[i];
-        for (const float *v : { a, b, c }) { for (int x = 0; x < 3; x++) { lo[x] = std::min(lo[x], (double)v[x]); hi[x] = std::max(hi[x], (double)v[x]); } }
+    const TriangleAreas areas = triangleAreas(desc);
+    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };   // the box of every triangle's corners
+    for (size_t k = 0; k < (size_t)3 * n; k++) {
+        const float *v = desc->positions + 3 * (size_t)desc->indices[k];
+        for (int x = 0; x < 3; x++) { lo[x] = std::min(lo[x], (double)v[x]); hi[x] = std::max(hi[x], (double)v[x]); }
     }
     std::vector<uint32_t> order(n);
     for (uint32_t i = 0; i < n; i++) { order[i] = i; }
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return area[x] > area[y]; });
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return areas.area[x] > areas.area[y]; });
     std::vector<char> isDirect(n, 0);
     int nDirect = 0;
     for (uint32_t k = 0; k < n && nDirect < kBruteForceMaxTris; k++) {
-        if (!(area[order[k]] * 256.0 >= total)) { break; }
+        if (!areas.large(order[k])) { break; }
         isDirect[order[k]] = 1;
         nDirect++;
     }
@@ -1491,34 +1448,14 @@ static hipError_t buildHybrid(PathedScene *scene, const PathedSceneDesc *desc)
             std::memcpy(&sub, &tree.leafTris[12 * k + 3], 4);
             bvh_detail::putInt(&tree.leafTris[12 * k + 3], (int)treePrim[(size_t)sub]);
         }
-        std::vector<float4> nodes(tree.nodes.size() / 4), tris(tree.leafTris.size() / 4);
-        std::memcpy(nodes.data(), tree.nodes.data(), tree.nodes.size() * sizeof(float));
-        std::memcpy(tris.data(), tree.leafTris.data(), tree.leafTris.size() * sizeof(float));
-        if ((status = scene->hybridNodes.upload(nodes)) != hipSuccess) { return status; }
-        if ((status = scene->hybridTris.upload(tris)) != hipSuccess) { return status; }
+        if ((status = scene->hybridNodes.upload(asQuads(tree.nodes))) != hipSuccess) { return status; }
+        if ((status = scene->hybridTris.upload(asQuads(tree.leafTris))) != hipSuccess) { return status; }
         scene->hybridNodeCount = tree.nodeCount;
         scene->hybridMaxStack = 3 * tree.maxDepth + 1;
-        double tlo[3] = { 1e300, 1e300, 1e300 }, thi[3] = { -1e300, -1e300, -1e300 };
-        for (uint32_t index : treeIndices) {
-            for (int a = 0; a < 3; a++) { tlo[a] = std::min(tlo[a], (double)desc->positions[3 * (size_t)index + a]); thi[a] = std::max(thi[a], (double)desc->positions[3 * (size_t)index + a]); }
-        }
-        double extent = 0.0;
-        for (int a = 0; a < 3; a++) { extent = std::max(extent, std::max(thi[a] - tlo[a], std::max(std::fabs(tlo[a]), std::fabs(thi[a])))); }
-        for (int a = 0; a < 3; a++) {   // padded: the proxy test is a cull, the walk's own slab tests decide
-            scene->hybridLo[a] = (float)(tlo[a] - 1e-4 * extent - 1e-30);
-            scene->hybridHi[a] = (float)(thi[a] + 1e-4 * extent + 1e-30);
-        }
-        // a bounding sphere about the box's centre (not the smallest one: the vertex farthest from that centre decides)
-        double centre[3], radius2 = 0.0;
-        for (int a = 0; a < 3; a++) { centre[a] = (double)(float)(0.5 * (tlo[a] + thi[a])); }
-        for (uint32_t index : treeIndices) {
-            double d2 = 0.0;
-            for (int a = 0; a < 3; a++) { const double d = (double)desc->positions[3 * (size_t)index + a] - centre[a]; d2 += d * d; }
-            radius2 = std::max(radius2, d2);
-        }
-        const double radius = std::sqrt(radius2) * 1.0001 + 1e-4 * extent + 1e-30;
-        for (int a = 0; a < 3; a++) { scene->hybridSphere[a] = (float)centre[a]; }
-        scene->hybridSphere[3] = (float)(radius * radius * 1.00001);
+        const RestProxy proxy = restProxy(desc->positions, treeIndices);   // (padded: the proxy test is a cull, the walk's own slab tests decide)
+        std::memcpy(scene->hybridLo, proxy.lo, sizeof proxy.lo);
+        std::memcpy(scene->hybridHi, proxy.hi, sizeof proxy.hi);
+        std::memcpy(scene->hybridSphere, proxy.sphere, sizeof proxy.sphere);
     }
     scene->hybridAvailable = true;
     return rebuildHybridItems(scene);
@@ -1746,51 +1683,53 @@ static FlatBvh buildInstancedBvh(const PathedSceneDesc *desc, const PathedInstan
     return out;
 }
 
-static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *optionsIn, const PathedInstanceDesc *instanceDesc, PathedScene **out)
+// ---- scene creation.  createScene, at the end, is the sequence of the stages below; the arithmetic
+// that needs no device is scene_tables.h.  A stage that fails has called fail() and returns its code: the scene's one owner
+// in createScene frees whatever had been allocated by then.
+
+static int deviceFail(hipError_t status, const char *what)
 {
-    if (!out) { return fail(PATHED_E_INVALID, "out pointer is null"); }
-    *out = nullptr;
-    int code = validate(desc);
-    if (code != PATHED_OK) { return code; }
-    PathedSceneOptions options;
-    std::memset(&options, 0, sizeof options);
-    options.device = PATHED_DEVICE_CURRENT;
-    if (optionsIn) {
-        if (optionsIn->struct_size != sizeof(PathedSceneOptions)) { return fail(PATHED_E_INVALID, "PathedSceneOptions.struct_size mismatch"); }
-        options = *optionsIn;
-        if (options.generic_kernels != 0 && options.generic_kernels != 1) { return fail(PATHED_E_INVALID, "generic_kernels must be 0 or 1"); }
-        if (options.node_format < 0 || options.node_format > 3) { return fail(PATHED_E_INVALID, "node_format must be 0 (automatic), 1 (128-byte float nodes), 2 (compressed 64-byte nodes) or 3 (compressed 8-wide nodes)"); }
-        if (options.build_threads < 0 || options.build_threads > 4096) { return fail(PATHED_E_INVALID, "build_threads must be 0..4096"); }
-        if (options.unit_order < 0 || options.unit_order > 3) { return fail(PATHED_E_INVALID, "unit_order must be 0..3"); }
-        if (options.bvh_builder < 0 || options.bvh_builder > PATHED_BVH_PLOC_DEVICE + 1) { return fail(PATHED_E_INVALID, "unknown BVH builder"); }
-        if (options.pools < 0 || options.pools > kMaxPools) { return fail(PATHED_E_INVALID, "pools must be 0..4"); }
-        if (options.stack_rows != 0 && options.stack_rows != 8 && options.stack_rows != 16 && options.stack_rows != 22) {
-            return fail(PATHED_E_INVALID, "stack_rows must be 0, 8, 16 or 22");
-        }
-        if (options.max_slots < 0 || (options.max_slots != 0 && options.max_slots < kBlock)) { return fail(PATHED_E_INVALID, "max_slots must be 0 or >= 256"); }
-        if (options.shade_kernel < 0 || options.shade_kernel > 6) { return fail(PATHED_E_INVALID, "shade_kernel must be 0..6"); }
-        if (options.stage_slots != 0 && options.stage_slots != 512 && options.stage_slots != 1024) { return fail(PATHED_E_INVALID, "stage_slots must be 0, 512 or 1024"); }
-        if (options.refittable != 0 && options.refittable != 1) { return fail(PATHED_E_INVALID, "refittable must be 0 or 1"); }
-        if (options.small_phase1 < 0 || options.small_phase1 > 2) { return fail(PATHED_E_INVALID, "small_phase1 must be 0 (automatic), 1 (VALU) or 2 (matrix pipe)"); }
-        if (options.wave_max_ksamples < 0) { return fail(PATHED_E_INVALID, "wave_max_ksamples must be >= 0"); }
-        if (options.wave_stragglers < -1 || options.wave_stragglers > 64) { return fail(PATHED_E_INVALID, "wave_stragglers must be -1 (none), 0 (default) or 1..64"); }
-        if (options.wave_refill < 0 || options.wave_refill > 64) { return fail(PATHED_E_INVALID, "wave_refill must be 0 (default) or 1..64"); }
-        if (options.chunks_per_pass < 0 || options.chunks_per_pass > 4096) { return fail(PATHED_E_INVALID, "chunks_per_pass must be 0 (default) or 1..4096"); }
-        if (options.shade_chain != 0 && options.shade_chain != 1) { return fail(PATHED_E_INVALID, "shade_chain must be 0 (automatic) or 1 (off)"); }
-        if (options.shade_launches < 0 || options.shade_launches > 16) { return fail(PATHED_E_INVALID, "shade_launches must be 0 (automatic) or 1..16"); }
-        if (options.local_rays != 0 && options.local_rays != 1) { return fail(PATHED_E_INVALID, "local_rays must be 0 (automatic) or 1 (off)"); }
-        if (options.hybrid_batch < 0 || options.hybrid_batch > 128) { return fail(PATHED_E_INVALID, "hybrid_batch must be 0 (default) or 1..128"); }
-        if (options.hybrid_ready < -1 || options.hybrid_ready > 64) { return fail(PATHED_E_INVALID, "hybrid_ready must be -1 (never), 0 (default) or 1..64"); }
-    }
-    InstancedLayout instancedLayout;
-    if (instanceDesc) {
-        code = planInstances(desc, options, instanceDesc, &instancedLayout);
-        if (code != PATHED_OK) { return code; }
-    }
+    return fail(PATHED_E_DEVICE, std::string(what) + ": " + hipGetErrorString(status));
+}
+
+// THE TINY-SCENE PREDICATE.  fewTriangles: no more triangles than the all-triangles kernels test per ray.  tinyScene: such
+// a scene whose spheres fit as well and that was not told to walk a tree.  The three places that ask:
+//   chooseBuilder       fewTriangles alone: the host builder, whose host copy of the records the all-triangles kernels
+//                       read.  It omits the other conditions, so a scene of 64 triangles and 17 spheres, or one with
+//                       intersector = 1, is built on the host as well although a tree is walked: kept, the choice of the
+//                       builder never changes an image and PathedStats.bvh_builder reports it.
+//   buildTreeOnHost     tinyScene: the spheres stay out of the tree and are tested one by one.  It omits `instanced`, which
+//                       cannot matter here: planInstances refuses a scene with instances that has a sphere.
+//   chooseShadeKernel   tinyScene && !instanced = PathedScene::bruteForce.  A scene with instances of at most 64 stored
+//                       triangles (world triangles and prototypes together: desc->n_triangles counts both) does occur; it
+//                       takes the host builder by the first rule, has no spheres by planInstances, and walks its two-level
+//                       tree by this one.  With 17 spheres the second and third rule are false together: the spheres are
+//                       in the tree that is walked.
+static bool fewTriangles(const PathedSceneDesc *desc) { return desc->n_triangles <= (uint32_t)kBruteForceMaxTris; }
+
+static bool tinyScene(const PathedSceneDesc *desc, const PathedSceneOptions &options)
+{
+    return fewTriangles(desc) && desc->n_spheres <= (uint32_t)kBruteForceMaxSpheres && options.intersector != 1 && !tuningEnv("PATHED_NO_BRUTE_FORCE");
+}
+
+static int resolveOptions(const PathedSceneOptions *optionsIn, PathedSceneOptions *options)
+{
+    std::memset(options, 0, sizeof *options);
+    options->device = PATHED_DEVICE_CURRENT;
+    if (!optionsIn) { return PATHED_OK; }
+    std::string message;
+    const int code = checkSceneOptions(*optionsIn, &message);   // (struct_size first: nothing past it is read of a struct of another size)
+    if (code != PATHED_OK) { return fail(code, message); }
+    *options = *optionsIn;
+    return PATHED_OK;
+}
+
+static int resolveDevice(const PathedSceneOptions &options, int *resolved)
+{
     int deviceId = options.device;
     if (deviceId == PATHED_DEVICE_CURRENT) {
         if (g_device < 0) {
-            code = pathed_hip_init(0);
+            const int code = pathed_hip_init(0);
             if (code != PATHED_OK) { return code; }
         }
         deviceId = g_device;
@@ -1801,172 +1740,59 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
         if (deviceId < 0 || deviceId >= count) { return fail(PATHED_E_INVALID, "device id out of range"); }
     }
     HIP_TRY(hipSetDevice(deviceId));
+    *resolved = deviceId;
+    return PATHED_OK;
+}
 
-    PathedScene *scene = new PathedScene();
-    std::memset(&scene->device, 0, sizeof scene->device);
-    scene->deviceId = deviceId;
-    scene->options = options;
-    scene->width = desc->camera.width;
-    scene->height = desc->camera.height;
-    scene->instanced = instanceDesc != nullptr;
+// image textures: one float4 array for all of them (scene_tables.h: gammaTexels)
+static int uploadTextures(PathedScene *scene, const PathedSceneDesc *desc, std::vector<size_t> *textureOffset)
+{
+    std::vector<float> texels;
+    gammaTexels(desc, &texels, textureOffset);
+    const hipError_t uploaded = scene->texels.upload(asQuads(texels));
+    return uploaded == hipSuccess ? PATHED_OK : deviceFail(uploaded, "upload textures");
+}
 
-    hipDeviceProp_t properties;
-    if (hipGetDeviceProperties(&properties, deviceId) == hipSuccess) {
-        scene->computeUnits = properties.multiProcessorCount > 0 ? properties.multiProcessorCount : 256;
-    }
+// What the host derives from the description for the shading side, once the texels have their device address.
+struct ShadingTables {
+    std::vector<DMaterial> materials;
+    std::vector<DSphere> spheres;
+    std::vector<LightEntry> lightList;   // emissive surfaces in model order, the environment light last
+    std::vector<DLight> lights;          // ... as the device reads them
+    EnvTables env;                       // empty without an environment light
+};
 
-    DScene &d = scene->device;
-    buildCamera(desc->camera, &d.camera);
-
-    // image textures: one float4 array, texels already through Texture::lookup's
-    // powf(x / 255.f, 2.2f) (reference src/texture.cpp:44-48; 256 possible values per channel)
-    std::vector<size_t> textureOffset(desc->n_textures);
-    {
-        float gammaTable[256];
-        for (int value = 0; value < 256; value++) { gammaTable[value] = powf((unsigned char)value / 255.f, 2.2f); }
-        std::vector<float4> texels;
-        for (uint32_t t = 0; t < desc->n_textures; t++) {
-            const PathedTexture &texture = desc->textures[t];
-            textureOffset[t] = texels.size();
-            const size_t count = (size_t)texture.width * texture.height;
-            for (size_t k = 0; k < count; k++) {
-                texels.push_back(make_float4(gammaTable[texture.rgb[3 * k + 0]], gammaTable[texture.rgb[3 * k + 1]], gammaTable[texture.rgb[3 * k + 2]], 0.f));
-            }
-        }
-        const hipError_t uploaded = scene->texels.upload(texels);
-        if (uploaded != hipSuccess) {
-            delete scene;
-            return fail(PATHED_E_DEVICE, std::string("upload textures: ") + hipGetErrorString(uploaded));
-        }
-    }
-
-    // materials
-    std::vector<DMaterial> materials(desc->n_materials);
+static void buildShadingTables(const PathedSceneDesc *desc, const float4 *texels, const std::vector<size_t> &textureOffset, ShadingTables *tables)
+{
+    tables->materials.resize(desc->n_materials);
+    std::vector<unsigned char> materialEmits(desc->n_materials);
     for (uint32_t i = 0; i < desc->n_materials; i++) {
-        materials[i] = buildMaterial(desc->materials[i]);
+        DMaterial &material = tables->materials[i];
+        material = buildMaterial(desc->materials[i]);
         if (desc->materials[i].albedo_type == PATHED_ALBEDO_TEXTURE) {
             const PathedTexture &texture = desc->textures[desc->materials[i].texture];
-            materials[i].texSize = texture.width | (texture.height << 16);
-            materials[i].texels = scene->texels.ptr + textureOffset[(size_t)desc->materials[i].texture];
+            material.texSize = texture.width | (texture.height << 16);
+            material.texels = texels + textureOffset[(size_t)desc->materials[i].texture];
         }
+        materialEmits[i] = emits(material);
     }
-
-    std::vector<DSphere> spheres(desc->n_spheres);
+    tables->spheres.resize(desc->n_spheres);
     for (uint32_t i = 0; i < desc->n_spheres; i++) {
         const PathedSphere &s = desc->spheres[i];
         for (int k = 0; k < 3; k++) {
-            spheres[i].centerWorld[k] = s.center_world[k];
-            spheres[i].centerSample[k] = s.center_sample[k];
+            tables->spheres[i].centerWorld[k] = s.center_world[k];
+            tables->spheres[i].centerSample[k] = s.center_sample[k];
         }
-        spheres[i].radius = s.radius;
-        spheres[i].material = s.material;
+        tables->spheres[i].radius = s.radius;
+        tables->spheres[i].material = s.material;
     }
-    std::memset(scene->spherePairs, 0, sizeof scene->spherePairs);
-    for (int pair = 0; pair < 8; pair++) { scene->spherePairs[pair][3][0] = -1.f; scene->spherePairs[pair][3][1] = -1.f; }   // radius^2 < 0: nothing touches it
-    for (uint32_t i = 0; i < desc->n_spheres && i < 16u; i++) {
-        for (int k = 0; k < 3; k++) { scene->spherePairs[i / 2][k][i % 2] = spheres[i].centerWorld[k]; }
-        scene->spherePairs[i / 2][3][i % 2] = spheres[i].radius * spheres[i].radius;
-    }
+    tables->lightList = listLights(desc, materialEmits);
+    for (const LightEntry &light : tables->lightList) { tables->lights.push_back({ light.kind, light.index }); }
+    if (desc->env) { buildEnvTables(*desc->env, &tables->env); }
+}
 
-    // lights: emissive surfaces in model order, environment light last
-    // (reference src/scene_parser.cpp:173-190)
-    std::vector<DLight> lights;
-    for (uint32_t g = 0; g < desc->n_geoms; g++) {
-        const PathedGeom &geom = desc->geoms[g];
-        if (geom.type == PATHED_GEOM_MESH) {
-            for (int i = 0; i < geom.count; i++) {
-                const int tri = geom.first + i;
-                if (emits(materials[(size_t)desc->tri_material[tri]])) { lights.push_back({ 0, tri }); }
-            }
-        } else if (emits(materials[(size_t)desc->spheres[geom.first].material])) {
-            lights.push_back({ 1, geom.first });
-        }
-    }
-
-    // environment light: EnvironmentLight ctor, reference src/environment_light.cpp:14-53
-    std::vector<float4> envRgba;
-    std::vector<float> thetaCdf, phiCdf;
-    std::vector<int> phiEmpty, thetaGuide, phiGuide;
-    std::vector<float4> thetaRecords, phiRecords;
-    if (desc->env) {
-        const PathedEnvLight &env = *desc->env;
-        const size_t texels = (size_t)env.width * env.height;
-        envRgba.resize(texels);
-        std::vector<float> luminance(texels, 0.f);
-        for (size_t i = 0; i < texels; i++) {
-            envRgba[i] = make_float4(env.rgba[4 * i], env.rgba[4 * i + 1], env.rgba[4 * i + 2], env.rgba[4 * i + 3]);
-            luminance[i] += env.rgba[4 * i + 0];
-            luminance[i] += env.rgba[4 * i + 1];
-            luminance[i] += env.rgba[4 * i + 2];
-        }
-        thetaCdf.resize((size_t)env.height);
-        phiCdf.resize(texels);
-        phiEmpty.resize((size_t)env.height);
-        std::vector<float> thetaData((size_t)env.height, 0.f);
-        for (int row = 0; row < env.height; row++) {
-            float thetaSum = 0.f;
-            for (int col = 0; col < env.width; col++) { thetaSum += luminance[(size_t)row * env.width + col]; }
-            phiEmpty[(size_t)row] = buildCdf(&luminance[(size_t)row * env.width], (size_t)env.width, &phiCdf[(size_t)row * env.width]) ? 1 : 0;
-            thetaData[(size_t)row] = thetaSum;
-        }
-        d.env.thetaEmpty = buildCdf(thetaData.data(), (size_t)env.height, thetaCdf.data()) ? 1 : 0;
-        // guide[j] = first i with cdf[i] >= j / size (the last entry when there is none)
-        auto buildGuide = [](const float *cdf, size_t size, int *guide) {
-            size_t i = 0;
-            for (size_t j = 0; j <= size; j++) {
-                const float threshold = (float)j / (float)size;
-                while (i + 1 < size && !(cdf[i] >= threshold)) { i++; }
-                guide[j] = (int)i;
-            }
-        };
-        thetaGuide.resize((size_t)env.height + 1);
-        buildGuide(thetaCdf.data(), (size_t)env.height, thetaGuide.data());
-        phiGuide.resize((size_t)env.height * ((size_t)env.width + 1));
-        for (int row = 0; row < env.height; row++) {
-            buildGuide(&phiCdf[(size_t)row * env.width], (size_t)env.width, &phiGuide[(size_t)row * (env.width + 1)]);
-        }
-        // sampling records (device_scene.h): for the guide cell `bucket` the search window of cdfSample is
-        // [guide[bucket - 1], guide[bucket + 2]]; the record carries its start, its end and the CDF around the start
-        auto buildRecords = [](const float *cdf, const int *guide, size_t size, bool empty, float4 *records) {
-            for (size_t bucket = 0; bucket <= size; bucket++) {
-                const size_t below = bucket == 0 ? 0 : bucket - 1;
-                const size_t above = bucket + 2 > size ? size : bucket + 2;
-                const int lo = guide[below], hi = guide[above];
-                auto at = [&](int index) { return cdf[(size_t)(index < 0 ? 0 : (index > (int)size - 1 ? (int)size - 1 : index))]; };
-                int loBits = empty ? -1 : lo;
-                float loAsFloat, hiAsFloat;
-                std::memcpy(&loAsFloat, &loBits, 4);
-                std::memcpy(&hiAsFloat, &hi, 4);
-                records[2 * bucket + 0] = make_float4(loAsFloat, hiAsFloat, lo > 0 ? at(lo - 1) : 0.f, at(lo));
-                records[2 * bucket + 1] = make_float4(at(lo + 1), at(lo + 2), 0.f, 0.f);
-            }
-        };
-        thetaRecords.resize(2 * ((size_t)env.height + 1));
-        buildRecords(thetaCdf.data(), thetaGuide.data(), (size_t)env.height, d.env.thetaEmpty != 0, thetaRecords.data());
-        phiRecords.resize(2 * (size_t)env.height * ((size_t)env.width + 1));
-        for (int row = 0; row < env.height; row++) {
-            buildRecords(&phiCdf[(size_t)row * env.width], &phiGuide[(size_t)row * (env.width + 1)], (size_t)env.width,
-                         phiEmpty[(size_t)row] != 0, &phiRecords[2 * (size_t)row * ((size_t)env.width + 1)]);
-        }
-        d.env.width = env.width;
-        d.env.height = env.height;
-        d.env.scale = env.scale;
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) {
-                d.env.mapToWorld[3 * r + c] = env.map_to_world[4 * r + c];
-                d.env.worldToMap[3 * r + c] = env.world_to_map[4 * r + c];
-            }
-        }
-        d.hasEnv = 1;
-        lights.push_back({ 2, 0 });
-    }
-
-    auto fail_cleanup = [&](hipError_t status, const char *what) {
-        delete scene;
-        return fail(PATHED_E_DEVICE, std::string(what) + ": " + hipGetErrorString(status));
-    };
-
-    hipError_t status;
+static int chooseBuilder(const PathedSceneDesc *desc, const PathedSceneOptions &options)
+{
     int builder = options.bvh_builder > 0 ? options.bvh_builder - 1 : PATHED_BVH_SAH_HOST;
     if (const char *text = tuningEnv("PATHED_BVH_BUILDER")) {
         if (!strcmp(text, "lbvh")) { builder = PATHED_BVH_LBVH_DEVICE; }
@@ -1974,150 +1800,173 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
         else if (!strcmp(text, "sah")) { builder = PATHED_BVH_SAH_HOST; }
     }
     // tiny meshes take the all-triangles kernel, which wants the host copy of the records
-    if (desc->n_triangles <= (uint32_t)kBruteForceMaxTris) { builder = PATHED_BVH_SAH_HOST; }
-    scene->bvhBuilder = builder;
-    // the triangle soup on the device: input of the device builders and of the shading-record gather
-    DeviceBuffer<float> devicePositions, deviceNormals, deviceUvs;
-    DeviceBuffer<uint32_t> deviceIndices;
-    DeviceBuffer<int> deviceTriMaterial;
-    auto releaseSoup = [&]() {
-        devicePositions.release(); deviceNormals.release(); deviceUvs.release(); deviceIndices.release(); deviceTriMaterial.release();
-    };
-    if (desc->n_triangles > 0) {
-        const size_t nv = desc->n_vertices, nt = desc->n_triangles;
-        status = devicePositions.allocate(3 * nv);
-        if (status == hipSuccess) { status = deviceNormals.allocate(3 * nv); }
-        if (status == hipSuccess) { status = deviceUvs.allocate(2 * nv); }
-        if (status == hipSuccess) { status = deviceIndices.allocate(3 * nt); }
-        if (status == hipSuccess) { status = deviceTriMaterial.allocate(nt); }
-        if (status == hipSuccess) { status = scene->triShade.allocate((size_t)kTriShadeQuads * nt); }
-        if (status == hipSuccess) { status = scene->triCompact.allocate((size_t)kTriCompactQuads * nt); }
-        if (status == hipSuccess) { status = hipMemcpy(devicePositions.ptr, desc->positions, 3 * nv * sizeof(float), hipMemcpyHostToDevice); }
-        if (status == hipSuccess) { status = hipMemcpy(deviceNormals.ptr, desc->normals, 3 * nv * sizeof(float), hipMemcpyHostToDevice); }
-        if (status == hipSuccess) { status = hipMemcpy(deviceUvs.ptr, desc->uvs, 2 * nv * sizeof(float), hipMemcpyHostToDevice); }
-        if (status == hipSuccess) { status = hipMemcpy(deviceIndices.ptr, desc->indices, 3 * nt * sizeof(uint32_t), hipMemcpyHostToDevice); }
-        if (status == hipSuccess) { status = hipMemcpy(deviceTriMaterial.ptr, desc->tri_material, nt * sizeof(int), hipMemcpyHostToDevice); }
-        if (status == hipSuccess) {
-            hipLaunchKernelGGL(k_build_tri_shade, dim3((unsigned)((8 * nt + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
-                               devicePositions.ptr, deviceNormals.ptr, deviceUvs.ptr, deviceIndices.ptr, deviceTriMaterial.ptr,
-                               (uint32_t)nt, scene->triShade.ptr, scene->triCompact.ptr);
-            status = hipGetLastError();
-        }
-        if (status != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload triangle soup"); }
-    }
+    if (fewTriangles(desc)) { builder = PATHED_BVH_SAH_HOST; }
+    return builder;
+}
 
-    if (builder == PATHED_BVH_LBVH_DEVICE || builder == PATHED_BVH_PLOC_DEVICE) {
-        // rtcCommitScene's stand-in on the device (lbvh.h): build, keep the result in place
-        DeviceBvh built;
-        std::string message;
-        // spheres join the tree as one-sphere leaves, as on the host (reference src/sphere.cpp:16-48: each is a geometry of its own)
-        DeviceBuffer<float4> sphereBounds;
-        if (desc->n_spheres > 0) {
-            std::vector<float4> bounds(desc->n_spheres);
-            for (uint32_t i = 0; i < desc->n_spheres; i++) {
-                bounds[i] = make_float4(desc->spheres[i].center_world[0], desc->spheres[i].center_world[1], desc->spheres[i].center_world[2], desc->spheres[i].radius);
-            }
-            if ((status = sphereBounds.upload(bounds)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload sphere bounds"); }
-            scene->spheresInTree = true;
+// The triangle soup on the device: input of the device builders and of the shading-record gather.  Freed with the scope
+// that holds it, unless the scene adopts it.
+struct TriangleSoup {
+    DeviceBuffer<float> positions, normals, uvs;
+    DeviceBuffer<uint32_t> indices;
+    DeviceBuffer<int> triMaterial;
+
+    void release() { positions.release(); normals.release(); uvs.release(); indices.release(); triMaterial.release(); }
+
+    // pathed_hip_scene_refit moves the vertices later: the soup stays (the buffers change owner, nothing is copied)
+    void adoptInto(PathedScene &scene)
+    {
+        auto adopt = [](auto &to, auto &from) { to.ptr = from.ptr; to.count = from.count; from.ptr = nullptr; from.count = 0; };
+        adopt(scene.soupPositions, positions); adopt(scene.soupNormals, normals); adopt(scene.soupUvs, uvs);
+        adopt(scene.soupIndices, indices); adopt(scene.soupTriMaterial, triMaterial);
+    }
+};
+
+// ... uploaded, and the shading records gathered from it (k_build_tri_shade, not waited for here)
+static int uploadSoup(PathedScene *scene, const PathedSceneDesc *desc, TriangleSoup *soup)
+{
+    if (desc->n_triangles == 0) { return PATHED_OK; }
+    const size_t nv = desc->n_vertices, nt = desc->n_triangles;
+    hipError_t status = soup->positions.allocate(3 * nv);
+    if (status == hipSuccess) { status = soup->normals.allocate(3 * nv); }
+    if (status == hipSuccess) { status = soup->uvs.allocate(2 * nv); }
+    if (status == hipSuccess) { status = soup->indices.allocate(3 * nt); }
+    if (status == hipSuccess) { status = soup->triMaterial.allocate(nt); }
+    if (status == hipSuccess) { status = scene->triShade.allocate((size_t)kTriShadeQuads * nt); }
+    if (status == hipSuccess) { status = scene->triCompact.allocate((size_t)kTriCompactQuads * nt); }
+    if (status == hipSuccess) { status = hipMemcpy(soup->positions.ptr, desc->positions, 3 * nv * sizeof(float), hipMemcpyHostToDevice); }
+    if (status == hipSuccess) { status = hipMemcpy(soup->normals.ptr, desc->normals, 3 * nv * sizeof(float), hipMemcpyHostToDevice); }
+    if (status == hipSuccess) { status = hipMemcpy(soup->uvs.ptr, desc->uvs, 2 * nv * sizeof(float), hipMemcpyHostToDevice); }
+    if (status == hipSuccess) { status = hipMemcpy(soup->indices.ptr, desc->indices, 3 * nt * sizeof(uint32_t), hipMemcpyHostToDevice); }
+    if (status == hipSuccess) { status = hipMemcpy(soup->triMaterial.ptr, desc->tri_material, nt * sizeof(int), hipMemcpyHostToDevice); }
+    if (status == hipSuccess) {
+        hipLaunchKernelGGL(k_build_tri_shade, dim3((unsigned)((8 * nt + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                           soup->positions.ptr, soup->normals.ptr, soup->uvs.ptr, soup->indices.ptr, soup->triMaterial.ptr,
+                           (uint32_t)nt, scene->triShade.ptr, scene->triCompact.ptr);
+        status = hipGetLastError();
+    }
+    return status == hipSuccess ? PATHED_OK : deviceFail(status, "upload triangle soup");
+}
+
+// rtcCommitScene's stand-in on the device (lbvh.h): build, keep the result in place
+static int buildTreeOnDevice(PathedScene *scene, const PathedSceneDesc *desc, int builder, const TriangleSoup &soup)
+{
+    DeviceBvh built;
+    std::string message;
+    hipError_t status;
+    // spheres join the tree as one-sphere leaves, as on the host (reference src/sphere.cpp:16-48: each is a geometry of its own)
+    DeviceBuffer<float4> sphereBounds;
+    if (desc->n_spheres > 0) {
+        std::vector<float4> bounds(desc->n_spheres);
+        for (uint32_t i = 0; i < desc->n_spheres; i++) {
+            bounds[i] = make_float4(desc->spheres[i].center_world[0], desc->spheres[i].center_world[1], desc->spheres[i].center_world[2], desc->spheres[i].radius);
         }
-        status = buildBvhOnDevice(builder == PATHED_BVH_PLOC_DEVICE ? kDeviceBuilderPloc : kDeviceBuilderLbvh,
-                                  devicePositions.ptr, deviceIndices.ptr, desc->n_triangles, sphereBounds.ptr, desc->n_spheres, nullptr, &built, &message);
-        if (status != hipSuccess) { releaseSoup(); return fail_cleanup(status, message.empty() ? "device BVH build" : message.c_str()); }
-        scene->nodes.ptr = built.nodes;
-        scene->nodes.count = built.nodeCapacity * 8;
-        scene->leafTris.ptr = built.leafTris;
-        scene->leafTris.count = (size_t)desc->n_triangles * 3;
-        scene->bvh.nodeCount = built.nodeCount;
-        scene->bvh.maxDepth = built.maxDepth;
-        scene->bvhOnHost = false;
-        scene->bvhBuildMs = built.buildMs;
-    } else {
-        const auto buildStart = std::chrono::steady_clock::now();
-        // Spheres join the tree as one-sphere leaves (the reference gives each one to Embree as a geometry of its own,
-        // src/sphere.cpp:16-48) unless the scene is small enough for the all-triangles kernel, which tests them one by one.
-        std::vector<float> sphereBounds;
-        const bool tiny = desc->n_triangles <= (uint32_t)kBruteForceMaxTris && desc->n_spheres <= (uint32_t)kBruteForceMaxSpheres
-            && scene->options.intersector != 1 && !tuningEnv("PATHED_NO_BRUTE_FORCE");
-        if (!tiny) {
-            for (uint32_t i = 0; i < desc->n_spheres; i++) {
-                for (int a = 0; a < 3; a++) { sphereBounds.push_back(desc->spheres[i].center_world[a]); }
-                sphereBounds.push_back(desc->spheres[i].radius);
-            }
-        }
-        scene->spheresInTree = !sphereBounds.empty();
-        std::vector<float4> instanceRecords, protoBoxes;
-        if (instanceDesc) {
-            scene->bvh = buildInstancedBvh(desc, instanceDesc, instancedLayout, scene->options.build_threads, &instanceRecords, &scene->instancedMaxStack,
-                                           &protoBoxes, &scene->topNodes, &scene->topDepth);
-        } else {
-            scene->bvh = buildBvh(desc->positions, desc->indices, desc->n_triangles, sphereBounds.data(), (uint32_t)(sphereBounds.size() / 4),
-                                  scene->options.build_threads);
-        }
-        scene->bvhBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - buildStart).count();
-        std::vector<float4> nodes(scene->bvh.nodes.size() / 4), tris(scene->bvh.leafTris.size() / 4);
-        std::memcpy(nodes.data(), scene->bvh.nodes.data(), scene->bvh.nodes.size() * sizeof(float));
-        std::memcpy(tris.data(), scene->bvh.leafTris.data(), scene->bvh.leafTris.size() * sizeof(float));
-        if ((status = scene->nodes.upload(nodes)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload nodes"); }
-        if ((status = scene->leafTris.upload(tris)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload triangles"); }
-        if (instanceDesc) {
-            if ((status = scene->instanceRecords.upload(instanceRecords)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload instance records"); }
-            if ((status = scene->instanceBases.upload(instancedLayout.bases)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload instance bases"); }
-            if ((status = scene->protoBoxes.upload(protoBoxes)) != hipSuccess) { releaseSoup(); return fail_cleanup(status, "upload prototype boxes"); }
-            scene->instanceSet.records = scene->instanceRecords.ptr;
-            scene->instanceSet.bases = scene->instanceBases.ptr;
-            scene->instanceSet.nInstances = (int)instanceDesc->n_instances;
-            scene->instanceSet.worldTris = instancedLayout.worldTris;
+        if ((status = sphereBounds.upload(bounds)) != hipSuccess) { return deviceFail(status, "upload sphere bounds"); }
+        scene->spheresInTree = true;
+    }
+    status = buildBvhOnDevice(builder == PATHED_BVH_PLOC_DEVICE ? kDeviceBuilderPloc : kDeviceBuilderLbvh,
+                              soup.positions.ptr, soup.indices.ptr, desc->n_triangles, sphereBounds.ptr, desc->n_spheres, nullptr, &built, &message);
+    if (status != hipSuccess) { return deviceFail(status, message.empty() ? "device BVH build" : message.c_str()); }
+    scene->nodes.ptr = built.nodes;
+    scene->nodes.count = built.nodeCapacity * 8;
+    scene->leafTris.ptr = built.leafTris;
+    scene->leafTris.count = (size_t)desc->n_triangles * 3;
+    scene->bvh.nodeCount = built.nodeCount;
+    scene->bvh.maxDepth = built.maxDepth;
+    scene->bvhOnHost = false;
+    scene->bvhBuildMs = built.buildMs;
+    return PATHED_OK;
+}
+
+// The binned-SAH builder on the host cores (bvh_build.h), or the two-level tree of a scene with instances; uploaded.
+static int buildTreeOnHost(PathedScene *scene, const PathedSceneDesc *desc, const PathedInstanceDesc *instanceDesc, const InstancedLayout &instancedLayout)
+{
+    const auto buildStart = std::chrono::steady_clock::now();
+    // Spheres join the tree as one-sphere leaves (the reference gives each one to Embree as a geometry of its own,
+    // src/sphere.cpp:16-48) unless the scene is small enough for the all-triangles kernel, which tests them one by one.
+    std::vector<float> sphereBounds;
+    if (!tinyScene(desc, scene->options)) {
+        for (uint32_t i = 0; i < desc->n_spheres; i++) {
+            for (int a = 0; a < 3; a++) { sphereBounds.push_back(desc->spheres[i].center_world[a]); }
+            sphereBounds.push_back(desc->spheres[i].radius);
         }
     }
-    status = hipDeviceSynchronize();   // the shading-record gather reads the soup
-    if (status == hipSuccess && options.refittable && desc->n_triangles > 0) {
-        // pathed_hip_scene_refit moves the vertices later: the soup stays (the buffers change owner, nothing is copied)
-        auto adopt = [](auto &to, auto &from) { to.ptr = from.ptr; to.count = from.count; from.ptr = nullptr; from.count = 0; };
-        adopt(scene->soupPositions, devicePositions); adopt(scene->soupNormals, deviceNormals); adopt(scene->soupUvs, deviceUvs);
-        adopt(scene->soupIndices, deviceIndices); adopt(scene->soupTriMaterial, deviceTriMaterial);
+    scene->spheresInTree = !sphereBounds.empty();
+    std::vector<float4> instanceRecords, protoBoxes;
+    if (instanceDesc) {
+        scene->bvh = buildInstancedBvh(desc, instanceDesc, instancedLayout, scene->options.build_threads, &instanceRecords, &scene->instancedMaxStack,
+                                       &protoBoxes, &scene->topNodes, &scene->topDepth);
+    } else {
+        scene->bvh = buildBvh(desc->positions, desc->indices, desc->n_triangles, sphereBounds.data(), (uint32_t)(sphereBounds.size() / 4),
+                              scene->options.build_threads);
+    }
+    scene->bvhBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - buildStart).count();
+    hipError_t status;
+    if ((status = scene->nodes.upload(asQuads(scene->bvh.nodes))) != hipSuccess) { return deviceFail(status, "upload nodes"); }
+    if ((status = scene->leafTris.upload(asQuads(scene->bvh.leafTris))) != hipSuccess) { return deviceFail(status, "upload triangles"); }
+    if (instanceDesc) {
+        if ((status = scene->instanceRecords.upload(instanceRecords)) != hipSuccess) { return deviceFail(status, "upload instance records"); }
+        if ((status = scene->instanceBases.upload(instancedLayout.bases)) != hipSuccess) { return deviceFail(status, "upload instance bases"); }
+        if ((status = scene->protoBoxes.upload(protoBoxes)) != hipSuccess) { return deviceFail(status, "upload prototype boxes"); }
+        scene->instanceSet.records = scene->instanceRecords.ptr;
+        scene->instanceSet.bases = scene->instanceBases.ptr;
+        scene->instanceSet.nInstances = (int)instanceDesc->n_instances;
+        scene->instanceSet.worldTris = instancedLayout.worldTris;
+    }
+    return PATHED_OK;
+}
+
+// Waits for the builders and the shading-record gather, then lets the soup go or, for a refittable scene, keeps it.
+static int settleSoup(PathedScene *scene, const PathedSceneDesc *desc, TriangleSoup *soup)
+{
+    const hipError_t status = hipDeviceSynchronize();   // the shading-record gather reads the soup
+    if (status == hipSuccess && scene->options.refittable && desc->n_triangles > 0) {
+        soup->adoptInto(*scene);
         scene->soupVertices = desc->n_vertices;
         scene->refittable = true;
     }
-    releaseSoup();
-    if (status != hipSuccess) { return fail_cleanup(status, "build shading records"); }
-    if ((status = scene->spheres.upload(spheres)) != hipSuccess) { return fail_cleanup(status, "upload spheres"); }
-    if ((status = scene->materials.upload(materials)) != hipSuccess) { return fail_cleanup(status, "upload materials"); }
-    if ((status = scene->lights.upload(lights)) != hipSuccess) { return fail_cleanup(status, "upload lights"); }
-    if ((status = scene->lightRecords.allocate((size_t)kLightRecordQuads * lights.size())) != hipSuccess) { return fail_cleanup(status, "allocate light records"); }
-    if ((status = buildLightRecords(scene, (int)lights.size())) != hipSuccess) { return fail_cleanup(status, "build light records"); }
-    {
-        // participating media and every primitive's internal medium (Surface::getInternalMedium), triangles then spheres
-        std::vector<DMedium> media(desc->n_media);
-        for (uint32_t i = 0; i < desc->n_media; i++) {
-            std::memset(&media[i], 0, sizeof(DMedium));
-            for (int k = 0; k < 3; k++) { media[i].sigmaT[k] = desc->media[i].sigma_t[k]; media[i].sigmaS[k] = desc->media[i].sigma_s[k]; }
-        }
-        std::vector<int> primMedium((size_t)desc->n_triangles + desc->n_spheres, -1);
-        for (uint32_t g = 0; g < desc->n_geoms; g++) {
-            const PathedGeom &geom = desc->geoms[g];
-            // (a medium with sigma_t = 0 stays a medium: its surface is still a container the volumetric queries skip; its
-            // distance sample -log(1 - xi) / 0 is +inf, "no event", as in the reference)
-            const int medium = geom.medium;
-            if (geom.type == PATHED_GEOM_MESH) {
-                for (int i = 0; i < geom.count; i++) { primMedium[(size_t)(geom.first + i)] = medium; }
-            } else {
-                primMedium[(size_t)desc->n_triangles + (size_t)geom.first] = medium;
-            }
-        }
-        for (uint32_t i = 0; i < desc->n_materials; i++) { scene->hasContainers = scene->hasContainers || desc->materials[i].type == PATHED_MAT_PASSTHROUGH; }
-        if ((status = scene->media.upload(media)) != hipSuccess) { return fail_cleanup(status, "upload media"); }
-        scene->mediaHost = media;
-        if ((status = scene->primMedium.upload(primMedium)) != hipSuccess) { return fail_cleanup(status, "upload media"); }
-    }
-    if ((status = scene->envRgba.upload(envRgba)) != hipSuccess) { return fail_cleanup(status, "upload env map"); }
-    if ((status = scene->thetaCdf.upload(thetaCdf)) != hipSuccess) { return fail_cleanup(status, "upload env cdf"); }
-    if ((status = scene->phiCdf.upload(phiCdf)) != hipSuccess) { return fail_cleanup(status, "upload env cdf"); }
-    if ((status = scene->phiEmpty.upload(phiEmpty)) != hipSuccess) { return fail_cleanup(status, "upload env cdf"); }
-    if ((status = scene->thetaGuide.upload(thetaGuide)) != hipSuccess) { return fail_cleanup(status, "upload env cdf"); }
-    if ((status = scene->phiGuide.upload(phiGuide)) != hipSuccess) { return fail_cleanup(status, "upload env cdf"); }
-    if ((status = scene->thetaRecords.upload(thetaRecords)) != hipSuccess) { return fail_cleanup(status, "upload env cdf"); }
-    if ((status = scene->phiRecords.upload(phiRecords)) != hipSuccess) { return fail_cleanup(status, "upload env cdf"); }
+    // (its destructor would do; released here for the footprint: 44 bytes per triangle or so that the uploads, the hybrid
+    // split and the render state allocated from here on need not sit beside)
+    soup->release();
+    return status == hipSuccess ? PATHED_OK : deviceFail(status, "build shading records");
+}
 
+// spheres, materials, lights and their records, media, the environment's tables
+static int uploadShadingTables(PathedScene *scene, const PathedSceneDesc *desc, const ShadingTables &tables)
+{
+    hipError_t status;
+    if ((status = scene->spheres.upload(tables.spheres)) != hipSuccess) { return deviceFail(status, "upload spheres"); }
+    if ((status = scene->materials.upload(tables.materials)) != hipSuccess) { return deviceFail(status, "upload materials"); }
+    if ((status = scene->lights.upload(tables.lights)) != hipSuccess) { return deviceFail(status, "upload lights"); }
+    if ((status = scene->lightRecords.allocate((size_t)kLightRecordQuads * tables.lights.size())) != hipSuccess) { return deviceFail(status, "allocate light records"); }
+    if ((status = buildLightRecords(scene, (int)tables.lights.size())) != hipSuccess) { return deviceFail(status, "build light records"); }
+    // participating media and every primitive's internal medium (scene_tables.h: buildMediaTables)
+    const MediaTables mediaTables = buildMediaTables(desc);
+    std::vector<DMedium> media(desc->n_media);
+    for (uint32_t i = 0; i < desc->n_media; i++) {
+        std::memset(&media[i], 0, sizeof(DMedium));
+        for (int k = 0; k < 3; k++) { media[i].sigmaT[k] = mediaTables.sigma[6 * i + k]; media[i].sigmaS[k] = mediaTables.sigma[6 * i + 3 + k]; }
+    }
+    scene->hasContainers = scene->hasContainers || mediaTables.hasContainers;
+    if ((status = scene->media.upload(media)) != hipSuccess) { return deviceFail(status, "upload media"); }
+    scene->mediaHost = media;
+    if ((status = scene->primMedium.upload(mediaTables.primMedium)) != hipSuccess) { return deviceFail(status, "upload media"); }
+    const EnvTables &env = tables.env;
+    if ((status = scene->envRgba.upload(asQuads(env.rgba))) != hipSuccess) { return deviceFail(status, "upload env map"); }
+    if ((status = scene->thetaCdf.upload(env.thetaCdf)) != hipSuccess) { return deviceFail(status, "upload env cdf"); }
+    if ((status = scene->phiCdf.upload(env.phiCdf)) != hipSuccess) { return deviceFail(status, "upload env cdf"); }
+    if ((status = scene->phiEmpty.upload(env.phiEmpty)) != hipSuccess) { return deviceFail(status, "upload env cdf"); }
+    if ((status = scene->thetaGuide.upload(env.thetaGuide)) != hipSuccess) { return deviceFail(status, "upload env cdf"); }
+    if ((status = scene->phiGuide.upload(env.phiGuide)) != hipSuccess) { return deviceFail(status, "upload env cdf"); }
+    if ((status = scene->thetaRecords.upload(asQuads(env.thetaRecords))) != hipSuccess) { return deviceFail(status, "upload env cdf"); }
+    if ((status = scene->phiRecords.upload(asQuads(env.phiRecords))) != hipSuccess) { return deviceFail(status, "upload env cdf"); }
+    return PATHED_OK;
+}
+
+// DScene: what the kernels read of the scene, now that every table has its address; and the scene's traits
+static void fillDeviceScene(PathedScene *scene, const PathedSceneDesc *desc, const ShadingTables &tables)
+{
+    DScene &d = scene->device;
     d.nodes = scene->nodes.ptr;
     d.nodesQ = nullptr;
     d.leafTris = scene->leafTris.ptr;
@@ -2128,39 +1977,26 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
     d.nLinearSpheres = scene->spheresInTree ? 0 : (int)desc->n_spheres;
     d.triShade = scene->triShade.ptr;
     d.triCompact = scene->triCompact.ptr;
-    {
-        // plain ranges (device_scene.h): meshes all of whose vertices carry zero normals and zero uvs, e.g. an OBJ without
-        // vn / vt or a PLY of positions
-        d.nPlainRanges = 0;
-        for (uint32_t g = 0; g < desc->n_geoms; g++) {
-            const PathedGeom &geom = desc->geoms[g];
-            if (geom.type != PATHED_GEOM_MESH || geom.count <= 0) { continue; }
-            bool plain = true;
-            for (int i = 0; i < geom.count && plain; i++) {
-                for (int k = 0; k < 3 && plain; k++) {
-                    const size_t v = desc->indices[3 * (size_t)(geom.first + i) + k];
-                    plain = desc->normals[3 * v] == 0.f && desc->normals[3 * v + 1] == 0.f && desc->normals[3 * v + 2] == 0.f
-                        && desc->uvs[2 * v] == 0.f && desc->uvs[2 * v + 1] == 0.f;
-                }
-            }
-            if (!plain) { continue; }
-            if (d.nPlainRanges > 0 && d.plainEnd[d.nPlainRanges - 1] == geom.first) { d.plainEnd[d.nPlainRanges - 1] = geom.first + geom.count; }
-            else if (d.nPlainRanges < kMaxPlainRanges) {
-                d.plainBegin[d.nPlainRanges] = geom.first;
-                d.plainEnd[d.nPlainRanges] = geom.first + geom.count;
-                d.nPlainRanges++;
-            }
-        }
-    }
+    d.nPlainRanges = plainRanges(desc, kMaxPlainRanges, d.plainBegin, d.plainEnd);
     d.materials = scene->materials.ptr;
     d.nMaterials = (int)desc->n_materials;
     d.lights = scene->lights.ptr;
     d.lightRecords = scene->lightRecords.ptr;
-    d.nLights = (int)lights.size();
-    scene->traits = sceneTraits(desc, materials, lights, options);
+    d.nLights = (int)tables.lights.size();
+    scene->traits = sceneTraits(desc, tables.materials, tables.lights, scene->options);
     d.media = scene->media.ptr;
     d.primMedium = scene->primMedium.ptr;
     d.nMedia = (int)desc->n_media;
+    if (desc->env) {
+        const EnvTables &env = tables.env;
+        d.env.thetaEmpty = env.thetaEmpty;
+        d.env.width = env.width;
+        d.env.height = env.height;
+        d.env.scale = env.scale;
+        std::memcpy(d.env.mapToWorld, env.mapToWorld, sizeof env.mapToWorld);
+        std::memcpy(d.env.worldToMap, env.worldToMap, sizeof env.worldToMap);
+        d.hasEnv = 1;
+    }
     d.env.rgba = scene->envRgba.ptr;
     d.env.thetaCdf = scene->thetaCdf.ptr;
     d.env.phiCdf = scene->phiCdf.ptr;
@@ -2169,14 +2005,19 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
     d.env.phiGuide = scene->phiGuide.ptr;
     d.env.thetaRecords = scene->thetaRecords.ptr;
     d.env.phiRecords = scene->phiRecords.ptr;
+}
 
+// Which kernels carry the radiance loop, part one: pools, the all-triangles intersector, the slot policy's defaults, the
+// shade kernel (returned through *chosen: 0 automatic .. 6, as PathedSceneOptions.shade_kernel) and the trace configuration.
+static int chooseShadeKernel(PathedScene *scene, const PathedSceneDesc *desc, int *chosen)
+{
+    const PathedSceneOptions &options = scene->options;
     if (options.pools > 0) { scene->pools = options.pools; }
     if (const char *poolCount = tuningEnv("PATHED_POOLS")) {
         const int value = atoi(poolCount);
         scene->pools = value < 1 ? 1 : value > kMaxPools ? kMaxPools : value;
     }
-    scene->bruteForce = scene->device.nTris <= kBruteForceMaxTris && scene->device.nSpheres <= kBruteForceMaxSpheres
-        && options.intersector != 1 && !tuningEnv("PATHED_NO_BRUTE_FORCE") && !scene->instanced;
+    scene->bruteForce = tinyScene(desc, options) && !scene->instanced;
     // BVH scenes: more slots = more rays per persistent wave to refill finished lanes from (ray cost is heavy-tailed) and
     // fewer, longer launches: 8 Mi slots (1.3 GB of path state) against 4 Mi: +3.6 % on the teapot, +6.1 % on the 5.2 M-
     // triangle mesh at >= 256 spp per call, 16 Mi +1 % / +7.6 %, 32 Mi less again (tools/slots_sweep.py); short calls want
@@ -2198,47 +2039,55 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
         else if (!strcmp(text, "wave")) { shadeKernel = 5; }
     }
     if (shadeKernel == 3 && !scene->bruteForce) {
-        delete scene;
         return fail(PATHED_E_INVALID, "the fused path kernel serves scenes of at most 64 triangles that take the all-triangles intersector");
     }
 #if !PATHED_EXPERIMENTS
     if (shadeKernel == 2 || shadeKernel == 4 || requestedNodeFormat(options) >= 2 || options.small_phase1 == 2) {
-        delete scene;
         return fail(PATHED_E_UNSUPPORTED, "the staged and split shade stages, the compressed node formats and the matrix-pipe phase 1 are measured-and-rejected "
                                           "experiments: build libpathed_hip_experiments.so (`make experiments`) and load it instead");
     }
 #endif
     if (shadeKernel == 4 && scene->bruteForce) {
-        delete scene;
         return fail(PATHED_E_INVALID, "the split shade stage follows the BVH trace kernel: scenes of at most 64 triangles take the fused, per-slot or staged kernels");
     }
     scene->splitShade = shadeKernel == 4;
     configureTrace(scene);
-    {
-        // the compressed tree: sphere-free scenes whose tree stays in HBM, walked by the per-slot pipeline's trace kernel
-        const int nodeFormat = requestedNodeFormat(options);
-        const bool eligible = !scene->bruteForce && !scene->sceneInLds && !scene->splitShade && scene->device.nSpheres == 0
-            && scene->device.nNodes > 0 && options.generic_kernels == 0 && !scene->instanced;
-        if (nodeFormat >= 2 && !eligible) {
-            delete scene;
-            return fail(PATHED_E_INVALID, "compressed nodes serve sphere-free scenes whose tree is walked in HBM by the per-slot pipeline (not generic_kernels, not the split stage)");
-        }
-        const int chosen = !eligible || nodeFormat == 1 ? 0 : nodeFormat == 0 ? PATHED_DEFAULT_NODE_FORMAT : nodeFormat - 1;
-#if PATHED_EXPERIMENTS
-        if (chosen != 0) {
-            const size_t nNodes = (size_t)scene->device.nNodes;
-            const unsigned blocks = (unsigned)((nNodes + kBlock - 1) / kBlock);
-            if ((status = scene->nodesQ.allocate((chosen == 2 ? 8 : 4) * nNodes)) != hipSuccess) { return fail_cleanup(status, "allocate compressed nodes"); }
-            if (chosen == 2) { hipLaunchKernelGGL(k_widen_nodes, dim3(blocks), dim3(kBlock), 0, nullptr, scene->nodes.ptr, (int)nNodes, scene->nodesQ.ptr); }
-            else { hipLaunchKernelGGL(k_compress_nodes, dim3(blocks), dim3(kBlock), 0, nullptr, scene->nodes.ptr, (int)nNodes, scene->nodesQ.ptr); }
-            if ((status = hipDeviceSynchronize()) != hipSuccess) { return fail_cleanup(status, "compress nodes"); }
-            scene->device.nodesQ = scene->nodesQ.ptr;
-            scene->nodeFormat = chosen;
-        }
-#else
-        (void)chosen;
-#endif
+    *chosen = shadeKernel;
+    return PATHED_OK;
+}
+
+// the compressed tree: sphere-free scenes whose tree stays in HBM, walked by the per-slot pipeline's trace kernel
+static int chooseNodeFormat(PathedScene *scene)
+{
+    const PathedSceneOptions &options = scene->options;
+    const int nodeFormat = requestedNodeFormat(options);
+    const bool eligible = !scene->bruteForce && !scene->sceneInLds && !scene->splitShade && scene->device.nSpheres == 0
+        && scene->device.nNodes > 0 && options.generic_kernels == 0 && !scene->instanced;
+    if (nodeFormat >= 2 && !eligible) {
+        return fail(PATHED_E_INVALID, "compressed nodes serve sphere-free scenes whose tree is walked in HBM by the per-slot pipeline (not generic_kernels, not the split stage)");
     }
+    const int chosen = !eligible || nodeFormat == 1 ? 0 : nodeFormat == 0 ? PATHED_DEFAULT_NODE_FORMAT : nodeFormat - 1;
+#if PATHED_EXPERIMENTS
+    if (chosen != 0) {
+        hipError_t status;
+        const size_t nNodes = (size_t)scene->device.nNodes;
+        const unsigned blocks = (unsigned)((nNodes + kBlock - 1) / kBlock);
+        if ((status = scene->nodesQ.allocate((chosen == 2 ? 8 : 4) * nNodes)) != hipSuccess) { return deviceFail(status, "allocate compressed nodes"); }
+        if (chosen == 2) { hipLaunchKernelGGL(k_widen_nodes, dim3(blocks), dim3(kBlock), 0, nullptr, scene->nodes.ptr, (int)nNodes, scene->nodesQ.ptr); }
+        else { hipLaunchKernelGGL(k_compress_nodes, dim3(blocks), dim3(kBlock), 0, nullptr, scene->nodes.ptr, (int)nNodes, scene->nodesQ.ptr); }
+        if ((status = hipDeviceSynchronize()) != hipSuccess) { return deviceFail(status, "compress nodes"); }
+        scene->device.nodesQ = scene->nodesQ.ptr;
+        scene->nodeFormat = chosen;
+    }
+#else
+    (void)chosen;
+#endif
+    return PATHED_OK;
+}
+
+// ... part two: the split stage's grids, and which in-register path kernels serve the scene
+static void choosePathKernels(PathedScene *scene, int shadeKernel)
+{
     // persistent grids of the split stage: k_vertex at PATHED_VERTEX_WAVES blocks per CU, k_regen at PATHED_REGEN_WAVES
 #if PATHED_EXPERIMENTS
     scene->vertexGrid = scene->computeUnits * PATHED_VERTEX_WAVES;
@@ -2249,26 +2098,36 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
     scene->fusedPath = scene->bruteForce && (shadeKernel == 0 || shadeKernel == 3);
     scene->waveMode = shadeKernel == 5 ? 2 : (shadeKernel == 0 || shadeKernel == 6) ? 0 : 1;
     scene->waveAvailable = !scene->bruteForce && scene->device.nMaterials <= kMaxLdsMaterials && scene->nodeFormat == 0 && !scene->instanced;
-    {
-        // [r5] k_path_hybrid: BVH scenes small enough that a handful of large triangles carry most of the hits (path_hybrid.h)
-        // (shade_kernel 6 asks for it on a larger mesh as well: the walk is the same, the tree just stops being cache-resident)
-        const bool eligible = !scene->bruteForce && desc->n_spheres == 0
-            && scene->device.nMaterials <= kMaxLdsMaterials && scene->nodeFormat == 0 && options.intersector != 1 && !scene->hasContainers
-            && !options.refittable    // (a refittable scene keeps ONE tree, the one pathed_hip_scene_refit moves)
-            && !scene->instanced;
-        if (shadeKernel == 6 && !eligible) {
-            delete scene;
-            return fail(PATHED_E_INVALID, "the hybrid path kernel serves sphere-free scenes of more than 64 triangles and at most 96 materials (intersector 0, not refittable)");
-        }
-        if (eligible && ((shadeKernel == 0 && desc->n_triangles <= (uint32_t)kHybridMaxTris) || shadeKernel == 6)) {
-            if ((status = buildHybrid(scene, desc)) != hipSuccess) { return fail_cleanup(status, "build the hybrid kernel's scene split"); }
-            scene->hybridPath = true;
-        }
+}
+
+// [r5] k_path_hybrid's split of the scene and the wavefront's local set, where they apply
+static int buildSplits(PathedScene *scene, const PathedSceneDesc *desc, int shadeKernel)
+{
+    const PathedSceneOptions &options = scene->options;
+    // k_path_hybrid: BVH scenes small enough that a handful of large triangles carry most of the hits (path_hybrid.h)
+    // (shade_kernel 6 asks for it on a larger mesh as well: the walk is the same, the tree just stops being cache-resident)
+    const bool eligible = !scene->bruteForce && desc->n_spheres == 0
+        && scene->device.nMaterials <= kMaxLdsMaterials && scene->nodeFormat == 0 && options.intersector != 1 && !scene->hasContainers
+        && !options.refittable    // (a refittable scene keeps ONE tree, the one pathed_hip_scene_refit moves)
+        && !scene->instanced;
+    if (shadeKernel == 6 && !eligible) {
+        return fail(PATHED_E_INVALID, "the hybrid path kernel serves sphere-free scenes of more than 64 triangles and at most 96 materials (intersector 0, not refittable)");
+    }
+    if (eligible && ((shadeKernel == 0 && desc->n_triangles <= (uint32_t)kHybridMaxTris) || shadeKernel == 6)) {
+        const hipError_t status = buildHybrid(scene, desc);
+        if (status != hipSuccess) { return deviceFail(status, "build the hybrid kernel's scene split"); }
+        scene->hybridPath = true;
     }
     // (not for refittable scenes: their vertices move, the large triangles' records and the bounds of the rest would go stale)
     if (!scene->bruteForce && options.local_rays != 1 && scene->nodeFormat == 0 && !options.refittable && !scene->instanced) { buildLocalSet(scene, desc); }
+    return PATHED_OK;
+}
+
+// ... part three: the wave kernel's and the staged kernel's settings
+static int tuneWaveAndStages(PathedScene *scene, int shadeKernel)
+{
+    const PathedSceneOptions &options = scene->options;
     if (shadeKernel == 5 && !scene->waveAvailable) {
-        delete scene;
         return fail(PATHED_E_INVALID, "the wave path kernel serves BVH scenes (more than 64 triangles or intersector 1) of at most 96 materials over the float nodes");
     }
     if (options.wave_max_ksamples > 0) { scene->waveMaxSamples = (unsigned long long)options.wave_max_ksamples << 10; }
@@ -2288,40 +2147,23 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
         const int value = atoi(text);
         if (value == 512 || value == 1024) { scene->stageRounds = value / kBlock; }
     }
+    return PATHED_OK;
+}
+
+// The all-triangles kernels' records: the packed pairs, the inputs of the never-occluder rule, the fused kernel's phase-1
+// records (rebuildSmallItems) and, in the experiments build, the matrix-pipe rows.
+static int buildSmallScene(PathedScene *scene, const PathedSceneDesc *desc, const std::vector<LightEntry> &lightList)
+{
+    const PathedSceneOptions &options = scene->options;
+    hipError_t status;
     std::memset(&scene->smallTris, 0, sizeof scene->smallTris);
-    if (scene->bruteForce) {
-        // pairs of leaf-ordered triangles, component-interleaved (kernels.h: SmallTris); the odd
-        // one out is paired with an all-zero triangle, masked off in the kernel
-        const float *tris = scene->bvh.leafTris.data();
-        for (int k = 0; k < scene->device.nTris; k++) {
-            const float *tri = tris + (size_t)12 * k;  // (v0, prim) (e1, -) (e2, -)
-            f2 *record = scene->smallTris.data + (size_t)kSmallPairWords * (k / 2);
-            for (int row = 0; row < 3; row++) {
-                for (int axis = 0; axis < 3; axis++) { record[3 * row + axis][k & 1] = tri[4 * row + axis]; }
-            }
-        }
-    }
+    if (scene->bruteForce) { packSmallTris(scene->bvh.leafTris.data(), scene->device.nTris, kSmallPairWords, reinterpret_cast<float *>(scene->smallTris.data)); }
     std::memset(&scene->smallItems, 0, sizeof scene->smallItems);
-    scene->smallExtraPoints.clear();
-    for (uint32_t i = 0; i < desc->n_spheres; i++) {
-        for (int sign = -1; sign <= 1; sign += 2) {
-            for (int a = 0; a < 3; a++) { scene->smallExtraPoints.push_back(desc->spheres[i].center_world[a] + sign * std::fabs(desc->spheres[i].radius) * 1.001f); }
-        }
-    }
-    scene->smallEmitterPrims.assign((size_t)desc->n_triangles, 0);
-    scene->smallSphereLights.clear();
-    for (const DLight &light : lights) {
-        if (light.kind == 0 && light.index >= 0 && (size_t)light.index < scene->smallEmitterPrims.size()) { scene->smallEmitterPrims[(size_t)light.index] = 1; }
-        if (light.kind == 1) {
-            // sampleLightsTerm samples the light about DSphere::centerSample, the intersector meets it about center_world: the
-            // rule is given both, so neither has to be told from the other
-            for (int a = 0; a < 3; a++) { scene->smallSphereLights.push_back(desc->spheres[light.index].center_sample[a]); }
-            scene->smallSphereLights.push_back(desc->spheres[light.index].radius);
-            for (int a = 0; a < 3; a++) { scene->smallSphereLights.push_back(desc->spheres[light.index].center_world[a]); }
-            scene->smallSphereLights.push_back(desc->spheres[light.index].radius);
-        }
-    }
-    if ((status = rebuildSmallItems(scene)) != hipSuccess) { return fail_cleanup(status, "upload the phase-1 records"); }
+    SmallLightInputs inputs = smallLightInputs(desc, lightList);
+    scene->smallExtraPoints.swap(inputs.extraPoints);
+    scene->smallEmitterPrims.swap(inputs.emitterPrims);
+    scene->smallSphereLights.swap(inputs.sphereLights);
+    if ((status = rebuildSmallItems(scene)) != hipSuccess) { return deviceFail(status, "upload the phase-1 records"); }
     scene->mfmaPhase1 = false;
     std::memset(&scene->mfmaFrame, 0, sizeof scene->mfmaFrame);
     if (scene->bruteForce && scene->fusedPath) {
@@ -2331,21 +2173,93 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
         }
         if (phase1 == 0) { phase1 = kDefaultSmallPhase1; }
         if (phase1 == 2 && scene->device.nTris > 0) {
+            // (rebuildSmallItems builds the same table, but only once mfmaPhase1 is set -- a new camera; at its call above
+            // the flag was still false, so this is the table's first build and stays)
             std::vector<float> table;
             // rows in ITEM order: phase 2 of the fused kernel indexes the item-ordered triangle records
             buildMfmaTable(scene->itemTrisHost.data(), scene->device.nTris, scene->device.camera.origin, 1, &table, &scene->mfmaFrame);
-            if ((status = scene->mfmaTable.upload(table)) != hipSuccess) { return fail_cleanup(status, "upload the matrix-pipe rows"); }
+            if ((status = scene->mfmaTable.upload(table)) != hipSuccess) { return deviceFail(status, "upload the matrix-pipe rows"); }
             scene->mfmaPhase1 = true;
         }
     }
-    if ((status = rebuildCameraMasks(scene)) != hipSuccess) { return fail_cleanup(status, "build the camera-ray candidate masks"); }
+    return PATHED_OK;
+}
+
+// the unit order, and the caller's word on the slot count (chooseShadeKernel set the defaults)
+static void applySlotOptions(PathedScene *scene)
+{
+    const PathedSceneOptions &options = scene->options;
     scene->unitOrder = unitOrderFromEnvironment(options.unit_order == 2 ? kOrderStripesTiled : options.unit_order == 3 ? kOrderTiles : kOrderStripes);
     if (options.max_slots >= kBlock) { scene->maxSlots = options.max_slots; scene->adaptiveSlots = false; }
     if (const char *slots = tuningEnv("PATHED_MAX_SLOTS")) {
         const long value = atol(slots);
         if (value >= kBlock) { scene->maxSlots = (int)value; scene->adaptiveSlots = false; }
     }
-    *out = scene;
+}
+
+static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *optionsIn, const PathedInstanceDesc *instanceDesc, PathedScene **out)
+{
+    if (!out) { return fail(PATHED_E_INVALID, "out pointer is null"); }
+    *out = nullptr;
+    int code = validate(desc);
+    if (code != PATHED_OK) { return code; }
+    PathedSceneOptions options;
+    if ((code = resolveOptions(optionsIn, &options)) != PATHED_OK) { return code; }
+    InstancedLayout instancedLayout;
+    if (instanceDesc && (code = planInstances(desc, options, instanceDesc, &instancedLayout)) != PATHED_OK) { return code; }
+    int deviceId = 0;
+    if ((code = resolveDevice(options, &deviceId)) != PATHED_OK) { return code; }
+
+    // the one owner: every return below frees what the scene holds by then
+    std::unique_ptr<PathedScene> owner(new PathedScene());
+    PathedScene *scene = owner.get();
+    std::memset(&scene->device, 0, sizeof scene->device);
+    scene->deviceId = deviceId;
+    scene->options = options;
+    scene->width = desc->camera.width;
+    scene->height = desc->camera.height;
+    scene->instanced = instanceDesc != nullptr;
+    hipDeviceProp_t properties;
+    if (hipGetDeviceProperties(&properties, deviceId) == hipSuccess) {
+        scene->computeUnits = properties.multiProcessorCount > 0 ? properties.multiProcessorCount : 256;
+    }
+    buildCamera(desc->camera, &scene->device.camera);
+
+    // the tables
+    std::vector<size_t> textureOffset;
+    if ((code = uploadTextures(scene, desc, &textureOffset)) != PATHED_OK) { return code; }
+    ShadingTables tables;
+    buildShadingTables(desc, scene->texels.ptr, textureOffset, &tables);
+    packSpherePairs(desc, scene->spherePairs);
+
+    // the soup and the shading records, the tree
+    const int builder = scene->bvhBuilder = chooseBuilder(desc, options);
+    TriangleSoup soup;
+    if ((code = uploadSoup(scene, desc, &soup)) != PATHED_OK) { return code; }
+    const bool onDevice = builder == PATHED_BVH_LBVH_DEVICE || builder == PATHED_BVH_PLOC_DEVICE;
+    code = onDevice ? buildTreeOnDevice(scene, desc, builder, soup) : buildTreeOnHost(scene, desc, instanceDesc, instancedLayout);
+    if (code != PATHED_OK) { return code; }
+    if ((code = settleSoup(scene, desc, &soup)) != PATHED_OK) { return code; }
+
+    // the uploads, the DScene pointers
+    if ((code = uploadShadingTables(scene, desc, tables)) != PATHED_OK) { return code; }
+    fillDeviceScene(scene, desc, tables);
+
+    // the kernel choice, with the hybrid and the local set in its middle (they need the node format, the wave kernel's
+    // refusal comes after them)
+    int shadeKernel = 0;
+    if ((code = chooseShadeKernel(scene, desc, &shadeKernel)) != PATHED_OK) { return code; }
+    if ((code = chooseNodeFormat(scene)) != PATHED_OK) { return code; }
+    choosePathKernels(scene, shadeKernel);
+    if ((code = buildSplits(scene, desc, shadeKernel)) != PATHED_OK) { return code; }
+    if ((code = tuneWaveAndStages(scene, shadeKernel)) != PATHED_OK) { return code; }
+
+    // the phase-1 records, the camera masks
+    if ((code = buildSmallScene(scene, desc, tables.lightList)) != PATHED_OK) { return code; }
+    const hipError_t status = rebuildCameraMasks(scene);
+    if (status != hipSuccess) { return deviceFail(status, "build the camera-ray candidate masks"); }
+    applySlotOptions(scene);
+    *out = owner.release();
     return PATHED_OK;
 }
 
