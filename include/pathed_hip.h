@@ -401,7 +401,8 @@ int pathed_hip_scene_create_instanced(const PathedSceneDesc *desc, const PathedS
  * host's -- into a second record buffer, and k_refit_top_pass refits the TOP tree bottom-up around the new world boxes (the
  * box rule of scene creation, pathed_amd.instances.placement_box in numpy).  The tree keeps its SHAPE: hits, ids and shading
  * are those of a scene created with the new transforms, but placements scattered far from where the tree was built make it
- * slower to walk (boxes of siblings overlap) -- a caller who moves them that far creates the scene again.  No prototype
+ * slower to walk (boxes of siblings overlap) -- a caller who moves them that far follows up with
+ * pathed_hip_scene_rebuild_top below.  No prototype
  * node and no leaf triangle is written; the traversal stack's bound is unchanged.
  *
  * Order: the call first waits for ALL work on the scene's device (hipDeviceSynchronize), so render calls still running --
@@ -415,6 +416,24 @@ int pathed_hip_scene_create_instanced(const PathedSceneDesc *desc, const PathedS
  * names the lowest such instance index).  On every error the scene is exactly as it was before the call. */
 int pathed_hip_scene_set_instance_transforms(PathedScene *scene, const float *transforms, uint32_t n_instances, float *device_ms);
 int pathed_hip_scene_set_instance_transforms_device(PathedScene *scene, const float *d_transforms, uint32_t n_instances, float *device_ms);
+/* Rebuilding the top tree: a NEW top tree over the scene's world triangles and its placements' CURRENT world boxes, built on
+ * the device, in place of the one the scene was created with -- the other half of what the reference repeats rtcCommitScene
+ * for.  Meant to follow pathed_hip_scene_set_instance_transforms when the placements were scattered far (a refitted tree keeps
+ * its shape and gets slow to walk); valid on a scene that was never moved as well.  builder: PATHED_BVH_LBVH_DEVICE or
+ * PATHED_BVH_PLOC_DEVICE.  The prototypes' trees, shading records and the render state stay; hits, ids and shading are those
+ * of a scene created with the current transforms (hits do not depend on the tree).  A later set_instance_transforms refits
+ * the new tree.  PathedStats.bvh_nodes / bvh_bytes / bvh_max_depth report the new tree, bvh_builder keeps saying what the
+ * scene was created with.  With fewer than two primitives (world triangles + placements) there is nothing to arrange: the
+ * call returns PATHED_OK and leaves the tree alone.
+ *
+ * Order: as pathed_hip_scene_set_instance_transforms -- the call first waits for all work on the scene's device and returns
+ * synchronised; it must not run concurrently with another call on the same scene.  device_ms (may be NULL): HIP-event time
+ * of the device work (the builder's, which includes its waits for a few counters, and the kernels around it).
+ *
+ * PATHED_E_INVALID: a null scene.  PATHED_E_UNSUPPORTED: a scene without instances; PATHED_BVH_SAH_HOST or an unknown
+ * builder (the host builder needs the scene created again).  PATHED_E_DEVICE: an allocation or a kernel failed.  The new
+ * arrays are built beside the live ones and adopted at the end: on every error the scene is exactly as it was. */
+int pathed_hip_scene_rebuild_top(PathedScene *scene, int32_t builder, float *device_ms);
 /* Another view of the same scene: replaces the camera (reference Camera, src/camera.cpp:13-30) without rebuilding or
  * re-uploading anything; the resolution must stay (the caller's radiance sums are per pixel). */
 int pathed_hip_scene_set_camera(PathedScene *scene, const PathedCamera *camera);

@@ -238,6 +238,7 @@ HIP_SYMBOLS = [
     "pathed_hip_scene_create_instanced",
     "pathed_hip_scene_set_instance_transforms",
     "pathed_hip_scene_set_instance_transforms_device",
+    "pathed_hip_scene_rebuild_top",
     "pathed_hip_debug_instance_records",
     "pathed_hip_scene_device",
     "pathed_hip_scene_set_camera",
@@ -332,6 +333,9 @@ def load_hip():
         lib.pathed_hip_scene_set_instance_transforms_device.restype = C.c_int
         lib.pathed_hip_debug_instance_records.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t]
         lib.pathed_hip_debug_instance_records.restype = C.c_int
+    if hasattr(lib, "pathed_hip_scene_rebuild_top"):   # (an older build of the same ABI, as above)
+        lib.pathed_hip_scene_rebuild_top.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
+        lib.pathed_hip_scene_rebuild_top.restype = C.c_int
     lib.pathed_hip_scene_device.argtypes = [vp]
     lib.pathed_hip_scene_device.restype = C.c_int
     lib.pathed_hip_scene_set_camera.argtypes = [vp, C.POINTER(PathedCamera)]

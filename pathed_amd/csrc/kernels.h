@@ -4675,4 +4675,69 @@ __global__ __launch_bounds__(kBlock) void k_accum_add(float *dst, const float *s
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) { dst[i] += src[i]; }
 }
 
+// ------------------------------------------------------------------------- rebuilding the top tree
+// pathed_hip_scene_rebuild_top: a NEW top tree over the world triangles and the placements' current world boxes (lbvh.hip:
+// buildTopBvhOnDevice), the prototypes' trees copied behind it.
+//
+// One thread per placement: its world box, (lo, hi) as two float4.  THE THIRD COPY of the rule -- buildInstancedBvh
+// (pathed_hip.hip) on the host, k_refit_top_pass above, and here; numpy states it as pathed_amd.instances.placement_box --
+// statement for statement: the eight corners of the prototype's padded box through flattenPoint with the live record's rows,
+// std::min / std::max, the pad 1e-5 max(1, |lo|, |hi|) + 1e-5 (hi - lo).  (Restated, not shared: k_refit_top_pass keeps its
+// 73 VGPRs and no scratch as it stands.)  A prototype index outside the table -- no record of the library holds one -- gives
+// an empty box at the origin instead of a read out of bounds.
+__global__ __launch_bounds__(kBlock) void k_placement_boxes(const float4 *records, int nInstances, const float4 *protoBoxes, int nPrototypes, float4 *boxes)
+{
+    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (i >= nInstances) { return; }
+    const float4 *record = records + (size_t)kInstanceQuads * i;
+    const float4 r0 = record[0], r1 = record[1], r2 = record[2];
+    const int prototype = floatAsInt(record[6].y);
+    float low[3] = { 0.f, 0.f, 0.f }, high[3] = { 0.f, 0.f, 0.f };
+    if (prototype >= 0 && prototype < nPrototypes) {
+        const float inf = __builtin_huge_valf();
+        const float m[12] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w };
+        const float4 protoLo = protoBoxes[2 * prototype], protoHi = protoBoxes[2 * prototype + 1];
+        float boxLo[3] = { inf, inf, inf }, boxHi[3] = { -inf, -inf, -inf };
+        for (int corner = 0; corner < 8; corner++) {
+            const V3 world = flattenPoint(m, v3((corner & 1) ? protoHi.x : protoLo.x, (corner & 2) ? protoHi.y : protoLo.y, (corner & 4) ? protoHi.z : protoLo.z));
+            const float point[3] = { world.x, world.y, world.z };
+            for (int a = 0; a < 3; a++) { boxLo[a] = hostMin(boxLo[a], point[a]); boxHi[a] = hostMax(boxHi[a], point[a]); }
+        }
+        for (int a = 0; a < 3; a++) {
+            const float pad = 1e-5f * hostMax(1.f, hostMax(fabsf(boxLo[a]), fabsf(boxHi[a]))) + 1e-5f * (boxHi[a] - boxLo[a]);
+            low[a] = boxLo[a] - pad;
+            high[a] = boxHi[a] + pad;
+        }
+    }
+    boxes[2 * (size_t)i] = make_float4(low[0], low[1], low[2], 0.f);
+    boxes[2 * (size_t)i + 1] = make_float4(high[0], high[1], high[2], 0.f);
+}
+
+// The prototypes' trees, nodes [oldTop, oldCount) of the old array, copied behind the new top tree: one thread per float4.
+// Their inner references (>= 0) move by delta = newTop - oldTop; leaf references are absolute into the leaf triangles, whose
+// layout [world | prototypes] keeps its size, and stay, as do the boxes.
+__global__ __launch_bounds__(kBlock) void k_rebase_prototype_nodes(const float4 *oldNodes, int oldTop, int oldCount, float4 *newNodes, int newTop)
+{
+    const size_t quad = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (quad >= (size_t)8 * (size_t)(oldCount - oldTop)) { return; }
+    float4 value = oldNodes[(size_t)8 * oldTop + quad];
+    if ((quad & 7) == 6) {
+        const int delta = newTop - oldTop;
+        int refs[4] = { floatAsInt(value.x), floatAsInt(value.y), floatAsInt(value.z), floatAsInt(value.w) };
+        for (int k = 0; k < 4; k++) { if (refs[k] >= 0) { refs[k] += delta; } }
+        value = make_float4(__int_as_float(refs[0]), __int_as_float(refs[1]), __int_as_float(refs[2]), __int_as_float(refs[3]));
+    }
+    newNodes[(size_t)8 * newTop + quad] = value;
+}
+
+// ... and every placement's record into the staged buffer with its protoRoot (word 2 of quad 6) moved by the same delta
+__global__ __launch_bounds__(kBlock) void k_rebase_instance_roots(const float4 *live, float4 *staged, int nInstances, int delta)
+{
+    const size_t quad = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (quad >= (size_t)kInstanceQuads * (size_t)nInstances) { return; }
+    float4 value = live[quad];
+    if (quad % kInstanceQuads == 6) { value.z = __int_as_float(floatAsInt(value.z) + delta); }
+    staged[quad] = value;
+}
+
 }  // namespace pathed

@@ -38,4 +38,15 @@ static const int kDeviceBuilderPloc = 2;   // PATHED_BVH_PLOC_DEVICE
 hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t *indices, uint32_t triangleCount,
                             const float4 *spheres, uint32_t sphereCount, hipStream_t stream, DeviceBvh *out, std::string *error);
 
+// The TOP tree of a scene with instances (pathed_hip_scene_rebuild_top), by the same kernels.  Its triangles are read from
+// leaf-triangle records -- 3 float4 each, (v0, prim) (e1, -) (e2, -), DEVICE pointer, the scene's only copy of its world
+// triangles -- bounded with directed rounding (the box holds the real-valued corners v0 + e1, v0 + e2) and copied, prim word
+// unchanged, in leaf order into the NEW buffer out->leafTris.  boxes: DEVICE pointer, (lo, hi) as two float4 per box; box i
+// becomes a leaf of its own as a sphere does, with trace.h's instance-leaf reference -(kInstanceLeafBit | i) - 1 and the
+// child box the collapse's pad gives every child.  Any triangleCount >= 0 builds as long as triangleCount + boxCount >= 2
+// (and < 2^28).  out->nodes has room for extraNodes nodes behind the nodeCount the build wrote, out->leafTris for extraTris
+// triangles behind the triangleCount it wrote: the caller's prototype trees.
+hipError_t buildTopBvhOnDevice(int builder, const float4 *records, uint32_t triangleCount, const float4 *boxes, uint32_t boxCount,
+                               size_t extraNodes, size_t extraTris, hipStream_t stream, DeviceBvh *out, std::string *error);
+
 }  // namespace pathed

@@ -15,6 +15,9 @@
 //                       frontier entry carries its subtree's first position in leaf order; subtrees
 //                       of at most four triangles become leaves and write their (v0, prim) (e1) (e2)
 //                       records there.
+// The top tree of a scene with instances (buildTopBvhOnDevice) takes the same steps with two other step-1 kernels --
+// k_lbvh_record_prims (triangles read from leaf-triangle records) and k_lbvh_box_prims (the placements' world boxes, leaves
+// of their own as spheres are) -- and k_lbvh_wide_emit<true>, which copies those records and emits instance leaves.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +37,7 @@ constexpr unsigned int kLeafFlag = 0x80000000u;   // child reference: a single s
 constexpr unsigned int kNoChild = 0xFFFFFFFFu;
 constexpr int kLbvhMaxLeaf = 4;                   // as the host builder's default leaf size
 constexpr int kEmptyRef = (int)0x80000000u;       // trace.h kEmptyChild
+constexpr int kInstanceLeaf = 1 << 30;            // trace.h kInstanceLeafBit: leaf code of placement i is kInstanceLeaf | i
 // "count" of a subtree: the triangles below it, and in the top bit whether a SPHERE is below it.  A sphere gets a leaf of
 // its own (bvh_build.h; reference src/sphere.cpp:16-48 hands each one to Embree as a geometry): a subtree with the bit set
 // never becomes a triangle leaf, and as an unsigned number it is "more than kLbvhMaxLeaf" wherever that is the question.
@@ -60,30 +64,10 @@ __host__ __device__ inline float fromOrderedBits(unsigned int u)
 // MI355X, and one set per wave made this kernel 5.6 ms for 5.2 M triangles (now ~0.3 ms).
 constexpr unsigned int kReduceBlocks = 1024;
 
-__global__ __launch_bounds__(kLbvhBlock) void k_lbvh_prims(
-    const float *positions, const uint32_t *indices, uint32_t n,
-    float4 *boxLo, float4 *boxHi, unsigned int *centroidBounds)
+// a block's centroid bounds joined into the build's: wave min / max, then one atomic pair per axis and block
+__device__ __forceinline__ void joinCentroidBounds(const float (&cmin)[3], const float (&cmax)[3], unsigned int *centroidBounds)
 {
     __shared__ float partial[kLbvhBlock / 64][6];
-    const float inf = __builtin_huge_valf();
-    float cmin[3] = { inf, inf, inf }, cmax[3] = { -inf, -inf, -inf };
-    for (size_t i = (size_t)blockIdx.x * kLbvhBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kLbvhBlock) {
-        const uint32_t i0 = indices[3 * i + 0], i1 = indices[3 * i + 1], i2 = indices[3 * i + 2];
-        float lo[3], hi[3];
-        #pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const float c0 = positions[3 * (size_t)i0 + a];
-            const float c1 = positions[3 * (size_t)i1 + a];
-            const float c2 = positions[3 * (size_t)i2 + a];
-            lo[a] = fminf(c0, fminf(c1, c2));
-            hi[a] = fmaxf(c0, fmaxf(c1, c2));
-            const float centre = 0.5f * (lo[a] + hi[a]);   // bvh_build.h: the box centre is the "centroid"
-            cmin[a] = fminf(cmin[a], centre);
-            cmax[a] = fmaxf(cmax[a], centre);
-        }
-        boxLo[i] = make_float4(lo[0], lo[1], lo[2], 0.f);
-        boxHi[i] = make_float4(hi[0], hi[1], hi[2], 0.f);
-    }
     #pragma unroll
     for (int a = 0; a < 3; a++) {
         float low = cmin[a], high = cmax[a];
@@ -110,6 +94,95 @@ __global__ __launch_bounds__(kLbvhBlock) void k_lbvh_prims(
             atomicMax(&centroidBounds[3 + threadIdx.x], orderedBits(high));
         }
     }
+}
+
+__global__ __launch_bounds__(kLbvhBlock) void k_lbvh_prims(
+    const float *positions, const uint32_t *indices, uint32_t n,
+    float4 *boxLo, float4 *boxHi, unsigned int *centroidBounds)
+{
+    const float inf = __builtin_huge_valf();
+    float cmin[3] = { inf, inf, inf }, cmax[3] = { -inf, -inf, -inf };
+    for (size_t i = (size_t)blockIdx.x * kLbvhBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kLbvhBlock) {
+        const uint32_t i0 = indices[3 * i + 0], i1 = indices[3 * i + 1], i2 = indices[3 * i + 2];
+        float lo[3], hi[3];
+        #pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const float c0 = positions[3 * (size_t)i0 + a];
+            const float c1 = positions[3 * (size_t)i1 + a];
+            const float c2 = positions[3 * (size_t)i2 + a];
+            lo[a] = fminf(c0, fminf(c1, c2));
+            hi[a] = fmaxf(c0, fmaxf(c1, c2));
+            const float centre = 0.5f * (lo[a] + hi[a]);   // bvh_build.h: the box centre is the "centroid"
+            cmin[a] = fminf(cmin[a], centre);
+            cmax[a] = fmaxf(cmax[a], centre);
+        }
+        boxLo[i] = make_float4(lo[0], lo[1], lo[2], 0.f);
+        boxHi[i] = make_float4(hi[0], hi[1], hi[2], 0.f);
+    }
+    joinCentroidBounds(cmin, cmax, centroidBounds);
+}
+
+// a + b rounded towards -inf and towards +inf (what __fadd_rd / __fadd_ru give; this toolchain's headers define them only
+// with OCML's rounded operations).  Knuth's two-sum yields the rounding error of the fp32 sum exactly -- this file is
+// compiled with -ffp-contract=off and without fast-math -- and its sign says on which side of the sum the real value lies.
+__device__ inline void addDirected(float a, float b, float *down, float *up)
+{
+    const float sum = a + b;
+    const float bPart = sum - a;
+    const float error = (a - (sum - bPart)) + (b - bPart);
+    *down = error < 0.f ? fromOrderedBits(orderedBits(sum) - 1u) : sum;
+    *up = error > 0.f ? fromOrderedBits(orderedBits(sum) + 1u) : sum;
+}
+
+// The triangles of a tree that is built over LEAF-TRIANGLE RECORDS, (v0, prim) (e1, -) (e2, -), the only copy a scene with
+// instances keeps of its world triangles and what the intersector tests.  The corners v0 + e1 and v0 + e2 are no stored
+// numbers: each sum is rounded down for the low side and up for the high side, so the box holds the real-valued corners.
+__global__ __launch_bounds__(kLbvhBlock) void k_lbvh_record_prims(
+    const float4 *records, uint32_t n, float4 *boxLo, float4 *boxHi, unsigned int *centroidBounds)
+{
+    const float inf = __builtin_huge_valf();
+    float cmin[3] = { inf, inf, inf }, cmax[3] = { -inf, -inf, -inf };
+    for (size_t i = (size_t)blockIdx.x * kLbvhBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kLbvhBlock) {
+        const float4 q0 = records[3 * i + 0], q1 = records[3 * i + 1], q2 = records[3 * i + 2];
+        const float v0[3] = { q0.x, q0.y, q0.z }, e1[3] = { q1.x, q1.y, q1.z }, e2[3] = { q2.x, q2.y, q2.z };
+        float lo[3], hi[3];
+        #pragma unroll
+        for (int a = 0; a < 3; a++) {
+            float down1, up1, down2, up2;
+            addDirected(v0[a], e1[a], &down1, &up1);
+            addDirected(v0[a], e2[a], &down2, &up2);
+            lo[a] = fminf(v0[a], fminf(down1, down2));
+            hi[a] = fmaxf(v0[a], fmaxf(up1, up2));
+            const float centre = 0.5f * (lo[a] + hi[a]);
+            cmin[a] = fminf(cmin[a], centre);
+            cmax[a] = fmaxf(cmax[a], centre);
+        }
+        boxLo[i] = make_float4(lo[0], lo[1], lo[2], 0.f);
+        boxHi[i] = make_float4(hi[0], hi[1], hi[2], 0.f);
+    }
+    joinCentroidBounds(cmin, cmax, centroidBounds);
+}
+
+// Boxes join the primitives behind the triangles, as spheres do, and like them each becomes a leaf of its own: primitive
+// triangleCount + b, bounds as given (lo, hi per box; a NaN box keeps out of the centroid bounds and sorts to code 0).
+__global__ __launch_bounds__(kLbvhBlock) void k_lbvh_box_prims(
+    const float4 *boxes, uint32_t boxCount, uint32_t triangleCount, float4 *boxLo, float4 *boxHi, unsigned int *centroidBounds)
+{
+    const float inf = __builtin_huge_valf();
+    float cmin[3] = { inf, inf, inf }, cmax[3] = { -inf, -inf, -inf };
+    for (size_t b = (size_t)blockIdx.x * kLbvhBlock + threadIdx.x; b < boxCount; b += (size_t)gridDim.x * kLbvhBlock) {
+        const float4 lo = boxes[2 * b], hi = boxes[2 * b + 1];
+        const float low[3] = { lo.x, lo.y, lo.z }, high[3] = { hi.x, hi.y, hi.z };
+        #pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const float centre = 0.5f * (low[a] + high[a]);
+            cmin[a] = fminf(cmin[a], centre);
+            cmax[a] = fmaxf(cmax[a], centre);
+        }
+        boxLo[triangleCount + b] = make_float4(lo.x, lo.y, lo.z, 0.f);
+        boxHi[triangleCount + b] = make_float4(hi.x, hi.y, hi.z, 0.f);
+    }
+    joinCentroidBounds(cmin, cmax, centroidBounds);
 }
 
 // spheres join the primitives behind the triangles: primitive triangleCount + s, bounds as bvh_build.h gives them
@@ -399,9 +472,9 @@ struct WideInputs {
     const float4 *nodeLo, *nodeHi;
     const float4 *boxLo, *boxHi;
     const unsigned int *sorted;
-    const float *positions;
-    const uint32_t *indices;
-    uint32_t triangleCount;          // primitives at or beyond it are spheres
+    const float *positions;          // (over records, the top tree of a scene with instances: the leaf-triangle records, 12 floats
+    const uint32_t *indices;         //  per triangle, and no indices -- one field for both keeps this kernel argument's size)
+    uint32_t triangleCount;          // primitives at or beyond it are spheres (over records: boxes, the placements)
 };
 
 // the packed count of a child reference (triangles below | kHasSphere)
@@ -451,7 +524,9 @@ __global__ __launch_bounds__(kLbvhBlock) void k_lbvh_wide_children(
         + (isInnerRef(in, c[2]) ? 1u : 0u) + (isInnerRef(in, c[3]) ? 1u : 0u);
 }
 
-// the (v0, prim) (e1) (e2) records of a leaf's triangles, left to right, starting at `first`
+// the (v0, prim) (e1) (e2) records of a leaf's triangles, left to right, starting at `first`.  RECORDS: copied from the
+// records the tree was built over, prim word and all (buildTopBvhOnDevice), into the new buffer.
+template <bool RECORDS>
 __device__ inline void writeLeafTriangles(const WideInputs &in, unsigned int ref, unsigned int first, float4 *leafTris)
 {
     unsigned int stack[kLbvhMaxLeaf];
@@ -462,6 +537,14 @@ __device__ inline void writeLeafTriangles(const WideInputs &in, unsigned int ref
         const unsigned int r = stack[--sp];
         if (r & kLeafFlag) {
             const unsigned int prim = in.sorted[r & ~kLeafFlag];
+            if (RECORDS) {
+                const float4 *records = reinterpret_cast<const float4 *>(in.positions);
+                leafTris[3 * (size_t)at + 0] = records[3 * (size_t)prim + 0];
+                leafTris[3 * (size_t)at + 1] = records[3 * (size_t)prim + 1];
+                leafTris[3 * (size_t)at + 2] = records[3 * (size_t)prim + 2];
+                at++;
+                continue;
+            }
             const float *v0 = in.positions + 3 * (size_t)in.indices[3 * (size_t)prim + 0];
             const float *v1 = in.positions + 3 * (size_t)in.indices[3 * (size_t)prim + 1];
             const float *v2 = in.positions + 3 * (size_t)in.indices[3 * (size_t)prim + 2];
@@ -480,6 +563,9 @@ __device__ inline void writeLeafTriangles(const WideInputs &in, unsigned int ref
     }
 }
 
+// RECORDS (the top tree of a scene with instances) differs in where a leaf's triangles come from and in what a one-primitive
+// leaf is: not a sphere but a placement, trace.h's instance leaf.  <false> is the kernel as it was before there were two.
+template <bool RECORDS>
 __global__ __launch_bounds__(kLbvhBlock) void k_lbvh_wide_emit(
     WideInputs in, const uint2 *frontier, unsigned int m, unsigned int levelBase,
     const uint4 *adopted, const unsigned int *innerCount, const unsigned int *childBase,
@@ -513,10 +599,10 @@ __global__ __launch_bounds__(kLbvhBlock) void k_lbvh_wide_emit(
             if ((ref & kLeafFlag) && (packed & kHasSphere)) {
                 // a sphere: a leaf of its own, count 0, first = sphere + 1 (bvh_build.h; trace.h tests it); no place in leaf order
                 const unsigned int sphere = in.sorted[ref & ~kLeafFlag] - in.triangleCount;
-                refs[k] = -(int)(((sphere + 1u) << 3) | 0u) - 1;
+                refs[k] = RECORDS ? -(int)((unsigned int)kInstanceLeaf | sphere) - 1 : -(int)(((sphere + 1u) << 3) | 0u) - 1;
             } else if (packed <= (unsigned int)kLbvhMaxLeaf) {
                 refs[k] = -(int)((first << 3) | triangles) - 1;   // trace.h encodeLeaf
-                writeLeafTriangles(in, ref, first, leafTris);
+                writeLeafTriangles<RECORDS>(in, ref, first, leafTris);
             } else {
                 refs[k] = (int)(levelBase + m + base + rank);     // next level's ids follow this level's
                 nextFrontier[base + rank] = make_uint2(ref, first);
@@ -674,10 +760,13 @@ struct Scratch {
 
 inline unsigned int blocksFor(size_t n) { return (unsigned int)((n + kLbvhBlock - 1) / kLbvhBlock); }
 
-}  // namespace
-
-hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t *indices, uint32_t triangleCount,
-                            const float4 *spheres, uint32_t sphereCount, hipStream_t stream, DeviceBvh *out, std::string *error)
+// The one build behind both entries.  records == nullptr: buildBvhOnDevice, triangles from positions / indices, the
+// one-primitive leaves are spheres.  Otherwise buildTopBvhOnDevice: triangles from leaf-triangle records, sphereCount BOXES
+// (lo, hi pairs in `boxes`) that become instance leaves, any triangle count as long as there are two primitives, and room
+// for extraNodes nodes / extraTris triangles behind what the build itself writes.
+hipError_t buildOnDevice(int builder, const float *positions, const uint32_t *indices, const float4 *records, uint32_t triangleCount,
+                         const float4 *spheres, const float4 *boxes, uint32_t sphereCount, size_t extraNodes, size_t extraTris,
+                         hipStream_t stream, DeviceBvh *out, std::string *error)
 {
     auto failed = [&](hipError_t status, const char *what) {
         if (error) { *error = std::string("device bvh: ") + what + ": " + hipGetErrorString(status); }
@@ -688,9 +777,10 @@ hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t 
     *out = DeviceBvh();
     const uint32_t n = triangleCount + sphereCount;   // primitives: triangles, then spheres
     if (builder != kDeviceBuilderLbvh && builder != kDeviceBuilderPloc) { return failed(hipErrorInvalidValue, "unknown builder"); }
-    if (triangleCount <= (uint32_t)kLbvhMaxLeaf) { return failed(hipErrorInvalidValue, "fewer than five triangles"); }
+    if (!records && triangleCount <= (uint32_t)kLbvhMaxLeaf) { return failed(hipErrorInvalidValue, "fewer than five triangles"); }
     if (n >= (1u << 28) || n < triangleCount) { return failed(hipErrorInvalidValue, "more than 2^28 primitives"); }
-    if (sphereCount > 0 && !spheres) { return failed(hipErrorInvalidValue, "null sphere array"); }
+    if (records && n < 2u) { return failed(hipErrorInvalidValue, "fewer than two primitives"); }
+    if (sphereCount > 0 && !(records ? boxes : spheres)) { return failed(hipErrorInvalidValue, records ? "null box array" : "null sphere array"); }
 
     hipEvent_t started = nullptr, finished = nullptr;
     hipError_t status;
@@ -724,8 +814,14 @@ hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t 
     }
     const unsigned int reduceGrid = blocksFor(n) < kReduceBlocks ? blocksFor(n) : kReduceBlocks;
     const unsigned int triangleGrid = blocksFor(triangleCount) < kReduceBlocks ? blocksFor(triangleCount) : kReduceBlocks;
-    hipLaunchKernelGGL(k_lbvh_prims, dim3(triangleGrid), dim3(kLbvhBlock), 0, stream, positions, indices, triangleCount, boxLo, boxHi, words);
-    if (sphereCount > 0) {
+    if (records) {
+        const unsigned int boxGrid = blocksFor(sphereCount) < kReduceBlocks ? blocksFor(sphereCount) : kReduceBlocks;
+        if (triangleCount > 0) { hipLaunchKernelGGL(k_lbvh_record_prims, dim3(triangleGrid), dim3(kLbvhBlock), 0, stream, records, triangleCount, boxLo, boxHi, words); }
+        if (sphereCount > 0) { hipLaunchKernelGGL(k_lbvh_box_prims, dim3(boxGrid), dim3(kLbvhBlock), 0, stream, boxes, sphereCount, triangleCount, boxLo, boxHi, words); }
+    } else {
+        hipLaunchKernelGGL(k_lbvh_prims, dim3(triangleGrid), dim3(kLbvhBlock), 0, stream, positions, indices, triangleCount, boxLo, boxHi, words);
+    }
+    if (!records && sphereCount > 0) {
         hipLaunchKernelGGL(k_lbvh_sphere_prims, dim3(blocksFor(sphereCount)), dim3(kLbvhBlock), 0, stream, spheres, sphereCount, triangleCount, boxLo, boxHi, words);
     }
     hipLaunchKernelGGL(k_lbvh_morton, dim3(blocksFor(n)), dim3(kLbvhBlock), 0, stream, boxLo, boxHi, n, words, keysIn, valuesIn);
@@ -879,11 +975,13 @@ hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t 
     unsigned int capacity = 0;
     if ((status = hipMemcpyAsync(&capacity, words + 6, sizeof capacity, hipMemcpyDeviceToHost, stream)) != hipSuccess) { return failed(status, "count"); }
     if ((status = hipStreamSynchronize(stream)) != hipSuccess) { return failed(status, "hierarchy kernels"); }
+    if (capacity == 0 && records) { capacity = 1; }   // two to four triangles and no box: the root's binary node is no "inner" one, the root itself still is
     if (capacity == 0) { return failed(hipErrorInvalidValue, "empty hierarchy"); }
 
-    if ((status = hipMalloc((void **)&out->nodes, (size_t)capacity * 8 * sizeof(float4))) != hipSuccess) { return failed(status, "node allocation"); }
-    if ((status = hipMalloc((void **)&out->leafTris, (size_t)triangleCount * 3 * sizeof(float4))) != hipSuccess) { return failed(status, "triangle allocation"); }
-    out->nodeCapacity = capacity;
+    const size_t storedTris = (size_t)triangleCount + extraTris;
+    if ((status = hipMalloc((void **)&out->nodes, ((size_t)capacity + extraNodes) * 8 * sizeof(float4))) != hipSuccess) { return failed(status, "node allocation"); }
+    if ((status = hipMalloc((void **)&out->leafTris, (storedTris ? storedTris : 1) * 3 * sizeof(float4))) != hipSuccess) { return failed(status, "triangle allocation"); }
+    out->nodeCapacity = (size_t)capacity + extraNodes;
 
     uint2 *frontierA = scratch.get<uint2>(capacity);
     uint2 *frontierB = scratch.get<uint2>(capacity);
@@ -906,7 +1004,7 @@ hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t 
     inputs.boxLo = boxLo;
     inputs.boxHi = boxHi;
     inputs.sorted = sorted;
-    inputs.positions = positions;
+    inputs.positions = records ? reinterpret_cast<const float *>(records) : positions;
     inputs.indices = indices;
     inputs.triangleCount = triangleCount;
 
@@ -926,8 +1024,13 @@ hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t 
         if ((status = rocprim::exclusive_scan(scanTemporary, bytes, innerCount, childBase, 0u, (size_t)m, rocprim::plus<unsigned int>(), stream)) != hipSuccess) {
             return failed(status, "scan");
         }
-        hipLaunchKernelGGL(k_lbvh_wide_emit, dim3(blocksFor(m)), dim3(kLbvhBlock), 0, stream,
-                           inputs, frontier, m, levelBase, adopted, innerCount, childBase, nextFrontier, words + 7, out->nodes, out->leafTris);
+        if (records) {
+            hipLaunchKernelGGL(k_lbvh_wide_emit<true>, dim3(blocksFor(m)), dim3(kLbvhBlock), 0, stream,
+                               inputs, frontier, m, levelBase, adopted, innerCount, childBase, nextFrontier, words + 7, out->nodes, out->leafTris);
+        } else {
+            hipLaunchKernelGGL(k_lbvh_wide_emit<false>, dim3(blocksFor(m)), dim3(kLbvhBlock), 0, stream,
+                               inputs, frontier, m, levelBase, adopted, innerCount, childBase, nextFrontier, words + 7, out->nodes, out->leafTris);
+        }
         unsigned int next = 0;
         if ((status = hipMemcpyAsync(&next, words + 7, sizeof next, hipMemcpyDeviceToHost, stream)) != hipSuccess) { return failed(status, "frontier size"); }
         if ((status = hipStreamSynchronize(stream)) != hipSuccess) { return failed(status, "collapse kernels"); }
@@ -946,6 +1049,28 @@ hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t 
     if ((status = hipGetLastError()) != hipSuccess) { return failed(status, "kernel launch"); }
     (void)hipEventElapsedTime(&out->buildMs, started, finished);
     return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t buildBvhOnDevice(int builder, const float *positions, const uint32_t *indices, uint32_t triangleCount,
+                            const float4 *spheres, uint32_t sphereCount, hipStream_t stream, DeviceBvh *out, std::string *error)
+{
+    return buildOnDevice(builder, positions, indices, nullptr, triangleCount, spheres, nullptr, sphereCount, 0, 0, stream, out, error);
+}
+
+hipError_t buildTopBvhOnDevice(int builder, const float4 *records, uint32_t triangleCount, const float4 *boxes, uint32_t boxCount,
+                               size_t extraNodes, size_t extraTris, hipStream_t stream, DeviceBvh *out, std::string *error)
+{
+    if (!records) {   // (no triangle: still "over records"; the pointer is only the mode's mark then and is never read)
+        if (triangleCount > 0) {
+            if (error) { *error = "device bvh: null triangle records"; }
+            *out = DeviceBvh();
+            return hipErrorInvalidValue;
+        }
+        records = boxes;
+    }
+    return buildOnDevice(builder, nullptr, nullptr, records, triangleCount, nullptr, boxes, boxCount, extraNodes, extraTris, stream, out, error);
 }
 
 }  // namespace pathed

@@ -3954,6 +3954,117 @@ int pathed_hip_scene_set_instance_transforms(PathedScene *scene, const float *tr
     return setInstanceTransforms(scene, scene->instanceTransforms.ptr, device_ms);
 }
 
+// ---- rebuilding the top tree (include/pathed_hip.h; lbvh.hip: buildTopBvhOnDevice; kernels.h: k_placement_boxes,
+// k_rebase_prototype_nodes, k_rebase_instance_roots).  Everything new is built beside the live arrays -- node array
+// [new top | prototypes' trees], leaf triangles [world in the new leaf order | prototypes], records with their protoRoot
+// moved -- and adopted at the end by swapping pointers: an error before that leaves the scene untouched.
+int pathed_hip_scene_rebuild_top(PathedScene *scene, int32_t builder, float *device_ms)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (!scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "rebuild_top: the scene has no instances (pathed_hip_scene_create_instanced makes one that has)"); }
+    if (builder != PATHED_BVH_LBVH_DEVICE && builder != PATHED_BVH_PLOC_DEVICE) {
+        return fail(PATHED_E_UNSUPPORTED, "rebuild_top builds on the device, with the LBVH or the PLOC builder: the host builder needs the scene created again");
+    }
+    SELECT_DEVICE(scene);
+    const int nInstances = scene->instanceSet.nInstances, worldTris = scene->instanceSet.worldTris;
+    const int oldTop = scene->topNodes, oldCount = scene->bvh.nodeCount, deepest = scene->bvh.maxDepth - scene->topDepth;
+    if (oldTop <= 0 || oldCount < oldTop || (size_t)oldCount > scene->nodes.count / 8 || worldTris < 0 || worldTris > scene->device.nTris || deepest < 0) {
+        return fail(PATHED_E_INVALID, "the scene has no top tree");
+    }
+    // render calls on a caller's stream may still walk the tree
+    HIP_TRY(hipDeviceSynchronize());
+    if (device_ms) { *device_ms = 0.f; }
+    if ((long long)worldTris + nInstances < 2) { return PATHED_OK; }   // nothing to arrange: the tree stays (an empty world keeps its empty root)
+    const size_t protoNodes = (size_t)(oldCount - oldTop), protoTris = (size_t)(scene->device.nTris - worldTris);
+    if (scene->instanceRecordsStaged.count != scene->instanceRecords.count) { HIP_TRY(scene->instanceRecordsStaged.allocate(scene->instanceRecords.count)); }
+    DeviceBuffer<float4> boxes;
+    HIP_TRY(boxes.allocate(2 * (size_t)nInstances));
+    hipEvent_t start = nullptr, stop = nullptr;
+    HIP_TRY(hipEventCreate(&start));
+    hipError_t status = hipEventCreate(&stop);
+    float ms = 0.f;
+    auto timed = [&](auto &&launches) {
+        float part = 0.f;
+        if (status == hipSuccess) { status = hipEventRecord(start, nullptr); }
+        if (status == hipSuccess) { launches(); status = hipGetLastError(); }
+        if (status == hipSuccess) { status = hipEventRecord(stop, nullptr); }
+        if (status == hipSuccess) { status = hipEventSynchronize(stop); }
+        if (status == hipSuccess) { status = hipEventElapsedTime(&part, start, stop); }
+        ms += part;
+    };
+    DeviceBvh built;
+    auto giveUp = [&](const std::string &what) {
+        (void)hipEventDestroy(start);
+        if (stop) { (void)hipEventDestroy(stop); }
+        if (built.nodes) { (void)hipFree(built.nodes); }
+        if (built.leafTris) { (void)hipFree(built.leafTris); }
+        return fail(PATHED_E_DEVICE, "rebuild_top: " + what);
+    };
+    if (nInstances > 0) {
+        timed([&]() {
+            hipLaunchKernelGGL(k_placement_boxes, dim3((unsigned)((nInstances + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                               scene->instanceRecords.ptr, nInstances, scene->protoBoxes.ptr, (int)(scene->protoBoxes.count / 2), boxes.ptr);
+        });
+    }
+    if (status != hipSuccess) { return giveUp(hipGetErrorString(status)); }
+    std::string message;
+    status = buildTopBvhOnDevice(builder == PATHED_BVH_PLOC_DEVICE ? kDeviceBuilderPloc : kDeviceBuilderLbvh, scene->leafTris.ptr, (uint32_t)worldTris,
+                                 boxes.ptr, (uint32_t)nInstances, protoNodes, protoTris, nullptr, &built, &message);
+    if (status != hipSuccess) { return giveUp(message.empty() ? hipGetErrorString(status) : message); }
+    ms += built.buildMs;
+    const int newTop = built.nodeCount;
+    if (newTop <= 0 || (size_t)newTop + protoNodes > built.nodeCapacity) { return giveUp("the builder made a wrong node count"); }
+    timed([&]() {
+        if (protoNodes > 0) {
+            hipLaunchKernelGGL(k_rebase_prototype_nodes, dim3((unsigned)((8 * protoNodes + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                               scene->nodes.ptr, oldTop, oldCount, built.nodes, newTop);
+        }
+        if (nInstances > 0) {
+            hipLaunchKernelGGL(k_rebase_instance_roots, dim3((unsigned)(((size_t)kInstanceQuads * nInstances + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                               scene->instanceRecords.ptr, scene->instanceRecordsStaged.ptr, nInstances, newTop - oldTop);
+        }
+        if (protoTris > 0) {
+            (void)hipMemcpyAsync(built.leafTris + 3 * (size_t)worldTris, scene->leafTris.ptr + 3 * (size_t)worldTris, protoTris * 3 * sizeof(float4), hipMemcpyDeviceToDevice, nullptr);
+        }
+    });
+    if (status == hipSuccess) { status = hipDeviceSynchronize(); }
+    if (status != hipSuccess) { return giveUp(hipGetErrorString(status)); }
+    (void)hipEventDestroy(start);
+    (void)hipEventDestroy(stop);
+
+    // adoption: nothing below can fail
+    scene->nodes.release();
+    scene->nodes.ptr = built.nodes;
+    scene->nodes.count = built.nodeCapacity * 8;
+    scene->leafTris.release();
+    scene->leafTris.ptr = built.leafTris;
+    scene->leafTris.count = ((size_t)worldTris + protoTris) * 3;
+    std::swap(scene->instanceRecords.ptr, scene->instanceRecordsStaged.ptr);
+    scene->instanceSet.records = scene->instanceRecords.ptr;
+    scene->topNodes = newTop;
+    scene->topDepth = built.maxDepth;
+    scene->bvh.nodeCount = newTop + (int)protoNodes;
+    scene->bvh.maxDepth = built.maxDepth + deepest;
+    scene->bvhOnHost = false;   // exports download the new tree
+    scene->instancedMaxStack = (3 * built.maxDepth + 1) + (3 * deepest + 1) + 1;
+    scene->device.nodes = scene->nodes.ptr;
+    scene->device.leafTris = scene->leafTris.ptr;
+    scene->device.nNodes = scene->bvh.nodeCount;
+    // the stack's bound and what hangs on it: configureTrace restates maxStack, stackRows, the LDS bytes and the grid; the
+    // buffers ensureRenderState sized by them (suspended waves' stacks, the HBM overflow rows) are allocated again on the
+    // next render call, as are the refit's side arrays (topNodes entries each) on the next set_instance_transforms
+    configureTrace(scene);
+    scene->suspendMask.release();
+    scene->suspendData.release();
+    scene->stackOverflow.release();
+    scene->volumeOverflow.release();
+    scene->topLo.release();
+    scene->topHi.release();
+    scene->topReady.release();
+    if (device_ms) { *device_ms = ms; }
+    return PATHED_OK;
+}
+
 int pathed_hip_debug_instance_records(PathedScene *scene, float *records, size_t n_instances)
 {
     if (!scene || !records) { return fail(PATHED_E_INVALID, "null scene or records"); }

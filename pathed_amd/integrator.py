@@ -470,6 +470,16 @@ class HipScene:
             self.instance_set.set_transforms(transforms)
         return float(ms.value)
 
+    def rebuild_top(self, builder="ploc"):
+        """A new top tree over the world triangles and the placements' current world boxes, built on the device
+        (pathed_hip_scene_rebuild_top): what follows set_instance_transforms when the placements were scattered far, since a
+        refit keeps the tree's shape.  `builder` is "lbvh", "ploc" or the PATHED_BVH_* constant (1, 2); the host builder ("sah")
+        is refused by the library: it needs the scene created again.  Returns the device time in milliseconds."""
+        kind = self.BVH_BUILDERS[builder] if isinstance(builder, str) else int(builder)
+        ms = C.c_float(0.0)
+        _check(self._lib, self._lib.pathed_hip_scene_rebuild_top(self._handle, kind, C.byref(ms)), "pathed_hip_scene_rebuild_top")
+        return float(ms.value)
+
     def instance_records(self):
         """The placements' records as the device holds them (pathed_hip_debug_instance_records): (transforms (n, 12) float32,
         inverses (n, 12) float32, ids (n, 4) int32: virtual id base, prototype, its root node, its first shading record)."""

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""Moving placements (pathed_hip_scene_set_instance_transforms), two measurements in one process:
+"""Moving placements (pathed_hip_scene_set_instance_transforms, pathed_hip_scene_rebuild_top), two
+measurements in one process, three arms each -- move (refit), move + rebuild (per device builder), destroy + create:
 
   (1) update time: set_instance_transforms (wall time of the call, which returns synchronised, and the device time of its
-      kernels) against the only other way to move a placement, destroying the scene and creating it again with the same
-      placements (wall time) -- at the 400 placements of jobs/instances-field.json, at 4 096 and at 262 144 placements of a
+      kernels), the same followed by rebuild_top, and destroying the scene and creating it again with the same placements
+      (wall time) -- at the 400 placements of jobs/instances-field.json, at 4 096 and at 262 144 placements of a
       5 120-triangle stand-in on a grid
-  (2) render rate on the REFITTED tree against a FRESH build of the same placements, the two scenes alternating: a small
-      rigid motion (every placement turned a few degrees and shifted by a tenth of the spacing) and a full shuffle of the
-      positions, on the field scene and on the 4 096-placement grid; the image sums must agree
+  (2) render rate on the REFITTED tree, on the REBUILT trees and on a FRESH build of the same placements, the scenes
+      alternating: a small rigid motion (every placement turned a few degrees and shifted by a tenth of the spacing) and a
+      full shuffle of the positions, on the field scene and on the 4 096-placement grid; the image sums must agree
+
+The lines of a run are appended to the log.
 
     tools/instances_motion.py [--spp 64] [--repeats 3] [--counts 4096,262144] [--log profiles/instances_motion.log]
 """
@@ -111,6 +114,16 @@ def move(gpu, transforms):
     return wall, float(ms.value)
 
 
+BUILDERS = ("lbvh", "ploc")
+
+
+def rebuild(gpu, builder):
+    """(wall ms, device ms) of one rebuild_top (the call returns synchronised)"""
+    start = time.perf_counter()
+    device = gpu.rebuild_top(builder)
+    return (time.perf_counter() - start) * 1e3, device
+
+
 def update_times(name, pointer, prototypes, which, transforms, shift, repeats):
     rng = np.random.default_rng(5)
     gpu = create(pointer, prototypes, which, transforms)
@@ -123,6 +136,16 @@ def update_times(name, pointer, prototypes, which, transforms, shift, repeats):
             walls.append(wall)
             devices.append(device)
     stats = gpu.stats()
+    rebuilt = {}
+    for builder in BUILDERS:   # move + rebuild: both calls' wall time, both calls' device time
+        pairs = []
+        for k in range(repeats + 1):   # (the first rebuild after a refit frees the refit's side arrays; the move allocates them again)
+            moved = rigid(transforms, shift, rng)
+            wall, device = move(gpu, moved)
+            more_wall, more_device = rebuild(gpu, builder)
+            if k > 0:
+                pairs.append((wall + more_wall, device + more_device))
+        rebuilt[builder] = (pairs, gpu.stats())
     recreates = []
     for _ in range(max(2, repeats // 3)):
         placements = instance_set(prototypes, which, moved)   # (made outside the timed stretch: the caller has it anyway)
@@ -134,6 +157,12 @@ def update_times(name, pointer, prototypes, which, transforms, shift, repeats):
     say("update %-8s %7d placements, %d nodes, depth %d: set_instance_transforms wall median %.3f ms (%s), device %.3f ms; destroy + create_instanced %.1f ms (%s): x%.0f"
         % (name, len(which), stats["bvh_nodes"], stats["bvh_max_depth"], float(np.median(walls)), " ".join("%.3f" % v for v in walls), float(np.median(devices)),
            float(np.median(recreates)), " ".join("%.1f" % v for v in recreates), float(np.median(recreates)) / float(np.median(walls))))
+    for builder in BUILDERS:
+        pairs, after = rebuilt[builder]
+        wall = float(np.median([w for w, _ in pairs]))
+        say("update %-8s %7d placements, move + rebuild_top(%s): %d nodes, depth %d; wall median %.3f ms (%s), device %.3f ms; destroy + create is x%.2f of it"
+            % (name, len(which), builder, after["bvh_nodes"], after["bvh_max_depth"], wall, " ".join("%.3f" % w for w, _ in pairs),
+               float(np.median([d for _, d in pairs])), float(np.median(recreates)) / wall))
 
 
 def rate(gpu, spp, last_bounce, accum):
@@ -145,23 +174,30 @@ def rate(gpu, spp, last_bounce, accum):
 
 
 def render_rates(name, pointer, prototypes, which, transforms, moved, spp, bounces, repeats, shape):
-    refitted = create(pointer, prototypes, which, transforms)
-    move(refitted, moved)
-    fresh = create(pointer, prototypes, which, moved)
+    arms = {"refitted": create(pointer, prototypes, which, transforms)}
+    move(arms["refitted"], moved)
+    for builder in BUILDERS:
+        arms["rebuilt " + builder] = create(pointer, prototypes, which, transforms)
+        move(arms["rebuilt " + builder], moved)
+        rebuild(arms["rebuilt " + builder], builder)
+    arms["fresh"] = create(pointer, prototypes, which, moved)
     accum = np.zeros(shape + (3,), dtype=np.float32)
-    for gpu in (refitted, fresh):
+    for gpu in arms.values():
         gpu.render(1, 0, 1, 0, 2, accum)
-    rates, sums = {"refitted": [], "fresh": []}, {}
+    rates, sums = {label: [] for label in arms}, {}
     for _ in range(repeats):
-        for label, gpu in (("refitted", refitted), ("fresh", fresh)):
+        for label, gpu in arms.items():
             value, sums[label] = rate(gpu, spp, bounces, accum)
             rates[label].append(value)
-    a, b = float(np.median(rates["refitted"])), float(np.median(rates["fresh"]))
-    say("render %-22s refitted %.1f Msamples/s (%s), fresh %.1f (%s): %.3f of fresh; image sums %s"
-        % (name, a, " ".join("%.1f" % v for v in rates["refitted"]), b, " ".join("%.1f" % v for v in rates["fresh"]), a / b,
-           "equal" if sums["refitted"] == sums["fresh"] else "DIFFER %r %r" % (sums["refitted"], sums["fresh"])))
-    refitted.close()
-    fresh.close()
+    medians = {label: float(np.median(values)) for label, values in rates.items()}
+    equal = all(value == sums["fresh"] for value in sums.values())
+    say("render %-22s %s; image sums %s" % (name, "; ".join(
+        "%s %.1f Msamples/s (%s: spread %.1f %%, %.3f of fresh)" % (label, medians[label], " ".join("%.1f" % v for v in rates[label]),
+                                                                  100.0 * (max(rates[label]) - min(rates[label])) / medians[label], medians[label] / medians["fresh"])
+        for label in arms), "equal" if equal else "DIFFER %r" % sums))
+    for gpu in arms.values():
+        gpu.close()
+    return equal
 
 
 def main():
@@ -187,17 +223,19 @@ def main():
 
     shape = (job["height"], job["width"])
     rng = np.random.default_rng(9)
-    render_rates("field, rigid motion", field.desc, field.prototypes, field_which, field_transforms, rigid(field_transforms, 0.34, rng),
-                 args.spp, job["lastBounce"], args.repeats, shape)
-    render_rates("field, shuffle", field.desc, field.prototypes, field_which, field_transforms, shuffled(field_transforms, rng),
-                 args.spp, job["lastBounce"], args.repeats, shape)
+    same = []
+    same.append(render_rates("field, rigid motion", field.desc, field.prototypes, field_which, field_transforms, rigid(field_transforms, 0.34, rng),
+                 args.spp, job["lastBounce"], args.repeats, shape))
+    same.append(render_rates("field, shuffle", field.desc, field.prototypes, field_which, field_transforms, shuffled(field_transforms, rng),
+                 args.spp, job["lastBounce"], args.repeats, shape))
     if counts:
         built, pointer, prototypes, which, transforms, spacing = grids[counts[0]]
-        render_rates("grid %d, rigid motion" % counts[0], pointer, prototypes, which, transforms, rigid(transforms, 0.1 * spacing, rng), args.spp, 4, args.repeats, (768, 1024))
-        render_rates("grid %d, shuffle" % counts[0], pointer, prototypes, which, transforms, shuffled(transforms, rng), args.spp, 4, args.repeats, (768, 1024))
+        same.append(render_rates("grid %d, rigid motion" % counts[0], pointer, prototypes, which, transforms, rigid(transforms, 0.1 * spacing, rng), args.spp, 4, args.repeats, (768, 1024)))
+        same.append(render_rates("grid %d, shuffle" % counts[0], pointer, prototypes, which, transforms, shuffled(transforms, rng), args.spp, 4, args.repeats, (768, 1024)))
     os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
-    with open(args.log, "w") as handle:
+    with open(args.log, "a") as handle:
         handle.write("\n".join(LINES) + "\n")
+    assert all(same), "the arms' image sums differ"
 
 
 if __name__ == "__main__":
