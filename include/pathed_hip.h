@@ -698,6 +698,21 @@ int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, siz
  * never_occluders: one uint64, bit p = primitive p is a never-occluder.  Both are written even when n is 0. */
 int pathed_hip_debug_shadow_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out, int32_t *layout, uint64_t *never_occluders);
 
+/* Test hook onto the PASS LIST of the fused kernel (pathed_amd/csrc/small_items.h: NEVER-HIT): the item list without the
+ * triangles that are bit-for-bit copies of a triangle with a lower primitive id, as the non-counting parallelogram
+ * instantiations walk it for a vertex's two rays -- its own records and counts, the shadow ray's turns pruned.  The hook
+ * ALWAYS prunes the shadow ray; of the instantiations that take the list only the Cornell-like one does (kernels.h:
+ * kSmallPrunes), the others run every turn for both rays: for those the hook's shadow word is a subset of the kernel's,
+ * so a test that finds every accepted hit among the hook's candidates holds for the kernel all the more.
+ * rays: n * 10 floats as pathed_hip_debug_small_candidates takes them.
+ * out:  n * 2 x uint64, bit p = ORIGINAL primitive id p: the pass's candidates of the path ray, of the shadow ray.
+ * primitives: n_triangles (the scene's triangle count) x int32: the primitive ids in pass order, -1 beyond the pass list.
+ * layout: 5 x int32: parallelograms, lone triangles, the shadow ray's turns over parallelogram pairs and over lone pairs,
+ *       triangles -- all of the pass list.
+ * never_hit: one uint64, bit p = primitive p is left out of the pass.  The last three are written even when n is 0. */
+int pathed_hip_debug_pass_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out, int32_t *primitives, size_t n_triangles,
+                                     int32_t *layout, uint64_t *never_hit);
+
 /* Test hook onto the per-pixel candidate masks of the camera rays (scenes on the fused path kernel only; built at scene
  * creation and again by pathed_hip_scene_set_camera, pathed_amd/csrc/camera_masks.h).
  * out: n_pixels x uint64, row-major pixels, host memory; n_pixels must be width * height.  Bit 63 - k = triangle k of the

@@ -259,6 +259,7 @@ HIP_SYMBOLS = [
     "pathed_hip_trace",
     "pathed_hip_debug_small_candidates",
     "pathed_hip_debug_shadow_candidates",
+    "pathed_hip_debug_pass_candidates",
     "pathed_hip_debug_camera_masks",
     "pathed_hip_debug_item_order",
     "pathed_hip_debug_light_records",
@@ -398,6 +399,10 @@ def load_hip():
     lib.pathed_hip_debug_small_candidates.restype = C.c_int
     lib.pathed_hip_debug_shadow_candidates.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
     lib.pathed_hip_debug_shadow_candidates.restype = C.c_int
+    if hasattr(lib, "pathed_hip_debug_pass_candidates"):   # (an older build of the same ABI, as below)
+        lib.pathed_hip_debug_pass_candidates.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_size_t,
+                                                         C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+        lib.pathed_hip_debug_pass_candidates.restype = C.c_int
     lib.pathed_hip_debug_light_records.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int)]
     lib.pathed_hip_debug_light_records.restype = C.c_int
     if hasattr(lib, "pathed_hip_debug_camera_masks"):   # (an older build of the same ABI, as above)

@@ -212,7 +212,8 @@ struct RenderParams {
     uint32_t sppBegin, sppEnd;
     int startBounce, lastBounce;
     int smallQuads;           // k_path_small: parallelograms among the phase-1 records (small_items.h), item-order triangles 2 q, 2 q + 1
-                              // (on the launch of a pruning instantiation of k_path_small: | shadowQuadPairs << 16 | shadowLonePairs << 24)
+                              // (on the launch of a pruning instantiation of k_path_small: | shadowQuadPairs << 16 | shadowLonePairs << 24;
+                              // of a kSmallPassList one: the pass list's counts, and | its triangle count << 8)
     // k_path_small<QUADS>: the scene's spheres, two per packed record (centre x, y, z, radius^2; the odd one out paired with a
     // sphere of radius -1 that no ray touches): phase 1 of the sphere queries (smallSphereCandidates)
     float spherePairs[8][4][2];   // [pair][component][half], kBruteForceMaxSpheres / 2 pairs
@@ -1079,6 +1080,18 @@ __device__ __forceinline__ void smallCandidatesItems(const f2 *records, int nQua
 // RenderParams::smallQuads by it: one definition for both.
 template <bool COUNT, typename TRAITS>
 constexpr bool kSmallPrunes = !COUNT && std::is_same<TRAITS, TraitsLambertianTriangles>::value;
+// The parallelogram instantiations of k_path_small whose pass over all items walks the PASS LIST (small_items.h: NEVER-HIT --
+// the item list without exact copies of a triangle with a lower id).  Their launch hands the kernel the pass list's records
+// as SmallTris and RenderParams::smallQuads = quads | triangles << 8 | shadowQuadPairs << 16 | shadowLonePairs << 24, all of
+// the PASS list; the pass list's item-ordered triangles follow the scene's own in the allocation scene.leafTris points into
+// (pathed_hip.hip: rebuildSmallItems).  One definition for the kernel and the launch, as above.  The counting instantiations
+// keep the full list: the library's own reference.  Of the seven non-counting parallelogram instantiations every one takes it
+// for which tests/test_kernel_resources.py still holds (profiles/duplicate_items_profile.log has their scratch before and
+// after, and the rates): all but the one for any BSDF under triangle lights, whose scratch would fall from 112 to 80 bytes
+// per lane while that test holds the ladder's rungs to no more than it and the two rough rungs keep 104 and 108.  It compiles
+// to what it was.
+template <bool COUNT, bool MFMA, typename TRAITS>
+constexpr bool kSmallPassList = !COUNT && !MFMA && !std::is_same<TRAITS, TraitsTriangleLit>::value;
 template <typename TRAITS> struct TraitsTag { typedef TRAITS type; };
 
 // Phase 2 (a wave-level loop: call it from wave-uniform control flow, lanes without a ray pass empty masks):
@@ -3238,6 +3251,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
     const int lane = threadIdx.x & 63;
     const unsigned int waveId = blockIdx.x * kWavesPerBlock + (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (wave-uniform, and known to be)
     const int nTris = p.scene.nTris;
+    // kSmallPassList: phase 2 of the pass over all items indexes the pass list's triangles, which follow the scene's nTris
+    // item-ordered ones; the refill's candidates come from the camera masks, in the FULL item order, and keep `geometry`
+    // (a second wave-uniform pointer: scalar registers only)
+    constexpr bool kPassList = QUADS && kSmallPassList<COUNT, MFMA, TRAITS>;
+    TraceGeometry passGeometry = geometry;
+    if (kPassList) { passGeometry.tris = geometry.tris + 3 * nTris; }
     const uint64_t seed = ((uint64_t)p.seedHi << 32) | p.seedLo;
     UnitTaker units(p, waveId);
 
@@ -3376,9 +3395,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                     // profiles/shadow_prune_profile.log).  The ladder's rungs and the any-BSDF instantiation: pruned, the latter's
                     // scratch fell from 112 to 84 / 64 bytes per lane while a rung kept 104, and tests/test_kernel_resources.py
                     // holds the rungs to no more than the instantiation they stand in for.
+                    // The same instantiation walks the PASS LIST (kSmallPassList; small_items.h: NEVER-HIT): smallTris holds its
+                    // records and the low half of smallQuads its two counts.  The count the bits are shifted by is the pass
+                    // list's; nTris, the scene's, still numbers the sphere primitives (geometry.nTris + k).
                     constexpr bool kPrune = kSmallPrunes<COUNT, TRAITS>;
-                    const int smallQuads = kPrune ? (p.smallQuads & 0xFFFF) : p.smallQuads;
-                    smallCandidatesItems<true, true, true, kPrune>(smallTris.data, smallQuads, nTris, p.smallKappaT, path.o, path.d, shadowDirection,
+                    const int smallQuads = kPassList ? (p.smallQuads & 0xFF) : kPrune ? (p.smallQuads & 0xFFFF) : p.smallQuads;
+                    const int passTris = kPassList ? ((p.smallQuads >> 8) & 0xFF) : nTris;
+                    smallCandidatesItems<true, true, true, kPrune>(smallTris.data, smallQuads, passTris, p.smallKappaT, path.o, path.d, shadowDirection,
                                                                    &candidatesLow, &candidatesHigh, &shadowLow, &shadowHigh,
                                                                    candidateNear(PATHED_TNEAR), candidateFar(shadowTfar),
                                                                    (p.smallQuads >> 16) & 0xFF, (p.smallQuads >> 24) & 0xFF);
@@ -3416,10 +3439,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_F
                     if (!traceShadow) { shadowSphereCandidates = 0u; }
                 }
                 spheresDone = smallResolveShared<kResolveCapacity, PATHED_RESOLVE_SHARED != 2, TRAITS::spheres>(
-                    geometry, ray, shadowRay, candidatesLow, candidatesHigh, shadowLow, shadowHigh, sphereCandidates, shadowSphereCandidates, scratch);
+                    passGeometry, ray, shadowRay, candidatesLow, candidatesHigh, shadowLow, shadowHigh, sphereCandidates, shadowSphereCandidates, scratch);
             } else {
-                smallResolve(geometry, ray, candidatesLow, candidatesHigh);
-                smallResolve(geometry, shadowRay, shadowLow, shadowHigh);
+                smallResolve(passGeometry, ray, candidatesLow, candidatesHigh);
+                smallResolve(passGeometry, shadowRay, shadowLow, shadowHigh);
             }
             if (tracing && !spheresDone) { finishRay(geometry, ray); }
             if (traceShadow) {
@@ -3608,6 +3631,29 @@ __global__ __launch_bounds__(kBlock) void k_debug_shadow_candidates(DScene scene
         if (intersectTriangle(o, dB, v3(t0.x, t0.y, t0.z), v3(t1.x, t1.y, t1.z), v3(t2.x, t2.y, t2.z), &t, &u, &v) && t > PATHED_TNEAR && t <= tfarB) { accepted |= bit; }
     }
     if (index < n) { out[(size_t)2 * index] = candidates; out[(size_t)2 * index + 1] = accepted; }
+}
+
+// Test hook behind pathed_hip_debug_pass_candidates: both rays' candidates over the PASS LIST (small_items.h: NEVER-HIT) as the
+// kSmallPassList instantiations of k_path_small compute them -- the pass list's records and counts, the shadow ray's turns
+// pruned --, one bit per ORIGINAL primitive id.  passTris: the pass list's item-ordered triangles, nPass of them.  Rays as
+// k_debug_small_candidates takes them; two words per ray (path ray, shadow ray).
+__global__ __launch_bounds__(kBlock) void k_debug_pass_candidates(SmallTris passItems, int nQuads, int nPass, float kappaT, int shadowQuadPairs, int shadowLonePairs,
+                                                                  const float4 *passTris, const float *rays, int n, unsigned long long *out)
+{
+    const int index = blockIdx.x * kBlock + threadIdx.x;
+    const float *r = rays + (size_t)10 * index;
+    const V3 o = v3(r[0], r[1], r[2]), dA = v3(r[3], r[4], r[5]), dB = v3(r[6], r[7], r[8]);
+    const float tfarB = r[9];
+    unsigned int aLow, aHigh, bLow, bHigh;
+    smallCandidatesItems<true, true, true, true>(passItems.data, nQuads, nPass, kappaT, o, dA, dB, &aLow, &aHigh, &bLow, &bHigh,
+                                                 candidateNear(PATHED_TNEAR), candidateFar(tfarB), shadowQuadPairs, shadowLonePairs);
+    unsigned long long candidatesA = 0, candidatesB = 0;
+    for (int k = 0; k < nPass; k++) {
+        const unsigned long long bit = 1ull << (floatAsInt(passTris[3 * k].w) & 63);
+        if (((k < 32 ? aLow : aHigh) >> (31 - (k & 31))) & 1u) { candidatesA |= bit; }
+        if (((k < 32 ? bLow : bHigh) >> (31 - (k & 31))) & 1u) { candidatesB |= bit; }
+    }
+    if (index < n) { out[(size_t)2 * index] = candidatesA; out[(size_t)2 * index + 1] = candidatesB; }
 }
 
 // ------------------------------------------------------------------------- volume path kernel

@@ -286,7 +286,15 @@ struct PathedScene {
     SmallItemsLayout smallLayout;
     DeviceBuffer<float4> itemTris;
     std::vector<float> itemTrisHost;       // host copy of itemTris (12 floats per triangle)
-    std::vector<float> smallExtraPoints;   // sphere bounds: where else a ray may start (the camera is added when the records are built)
+    // the PASS LIST (small_items.h: NEVER-HIT): the same without exact copies of a lower-numbered triangle, what the
+    // kSmallPassList instantiations of k_path_small walk.  Its item-ordered triangles are the SECOND device.nTris records of
+    // itemTris (passTris of them in use), so the kernel needs no pointer of its own for them
+    SmallTris passItems;
+    SmallItemsLayout passLayout;
+    int passTris = 0;
+    unsigned long long passNeverHit = 0ull;    // bit (original primitive id & 63)
+    std::vector<float> passTrisHost;
+    std::vector<float> smallExtraPoints;  // sphere bounds: where else a ray may start (the camera is added when the records are built)
     std::vector<unsigned char> smallEmitterPrims;   // per original primitive id: the triangle is a light (small_items.h: SmallLights)
     std::vector<float> smallSphereLights;           // centre.xyz, radius of every sphere light: about center_sample, where sphereSample puts
                                                     // the samples, and again about center_world (a transformed sphere has two centres)
@@ -1295,7 +1303,13 @@ static hipError_t rebuildSmallItems(PathedScene *scene)
     scene->smallLayout = buildSmallItems(scene->bvh.leafTris.data(), scene->device.nTris, points.data(), (int)(points.size() / 3), pairQuads, PATHED_TNEAR,
                                          reinterpret_cast<float *>(scene->smallItems.data), &ordered, &lights);
     scene->itemTrisHost = ordered;
-    const hipError_t status = scene->itemTris.upload(asQuads(ordered));
+    // the pass list (small_items.h: NEVER-HIT), from the same inputs; its triangles go behind the scene's own (PathedScene::passItems)
+    scene->passLayout = buildSmallPassItems(scene->bvh.leafTris.data(), scene->device.nTris, points.data(), (int)(points.size() / 3), pairQuads, PATHED_TNEAR,
+                                            reinterpret_cast<float *>(scene->passItems.data), &scene->passTrisHost, &lights, &scene->passTris, &scene->passNeverHit);
+    std::vector<float> both((size_t)24 * scene->device.nTris, 0.f);
+    std::memcpy(both.data(), ordered.data(), sizeof(float) * 12 * (size_t)scene->device.nTris);
+    std::memcpy(both.data() + (size_t)12 * scene->device.nTris, scene->passTrisHost.data(), sizeof(float) * 12 * (size_t)scene->passTris);
+    const hipError_t status = scene->itemTris.upload(asQuads(both));
     if (status == hipSuccess && scene->mfmaPhase1) {
         // (experiments build) the matrix-pipe rows are expressed in a frame centred on the camera: a new camera is a new table,
         // or phase 1 stops being conservative for rays that start far from the old one
@@ -2511,7 +2525,8 @@ static int renderPassFused(PathedScene *scene, const Pass &pass)
         // this scene's (shading.h: SceneTraits).  MFMA and QUADS exist with the materials in LDS only.
         const SceneTraitFlags &traits = scene->traits;
         const bool count = scene->countMode;
-        const auto run = [&](void (*kernel)(RenderParams, SmallTris)) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, scene->smallItems); };
+        const SmallTris *records = &scene->smallItems;   // (quadsKernel below: or the pass list's)
+        const auto run = [&](void (*kernel)(RenderParams, SmallTris)) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, *records); };
 #if PATHED_EXPERIMENTS
         if (scene->mfmaPhase1 && ldsMaterials) {
             // phase 1 on the matrix pipe
@@ -2523,12 +2538,21 @@ static int renderPassFused(PathedScene *scene, const Pass &pass)
         } else
 #endif
         if (scene->smallLayout.nQuads > 0 && ldsMaterials) {
+            // (the rung is chosen by the FULL list's parallelograms.  The pass list keeps one triangle of every class, so it
+            // normally pairs a quad wherever the full list does; nothing depends on it: with passLayout.nQuads = 0 the
+            // parallelogram loops of phase 1 run no turn and every kept triangle is a lone one)
             // (the instantiations that prune the shadow ray's phase 1 -- kernels.h kSmallPrunes<COUNT, TRAITS>, the constant the kernel
             // itself branches on -- read the turns it runs from the upper half of smallQuads; the others read the word whole, so
             // quadsKernel sets that half for exactly those and hands out the instantiation in the same breath)
+            // (... and the instantiations that walk the pass list -- kSmallPassList, small_items.h: NEVER-HIT -- get its records
+            // and its counts, the triangle count in bits 8-15; its triangles lie behind the scene's in itemTris)
             const auto quadsKernel = [&](auto COUNT, auto traitsTag) -> void (*)(RenderParams, SmallTris) {
                 using TRAITS = typename decltype(traitsTag)::type;
-                if (kSmallPrunes<decltype(COUNT)::value, TRAITS>) {
+                if (kSmallPassList<decltype(COUNT)::value, false, TRAITS>) {
+                    const SmallItemsLayout &list = scene->passLayout;
+                    params.smallQuads = list.nQuads | scene->passTris << 8 | list.shadowQuadPairs << 16 | list.shadowLonePairs << 24;
+                    records = &scene->passItems;
+                } else if (kSmallPrunes<decltype(COUNT)::value, TRAITS>) {
                     params.smallQuads = scene->smallLayout.nQuads | scene->smallLayout.shadowQuadPairs << 16 | scene->smallLayout.shadowLonePairs << 24;
                 }
                 return k_path_small<true, decltype(COUNT)::value, TRAITS, false, true>;
@@ -3711,6 +3735,48 @@ int pathed_hip_debug_shadow_candidates(PathedScene *scene, const float *rays, si
     hipLaunchKernelGGL(k_debug_shadow_candidates, dim3((unsigned)(padded / kBlock)), dim3(kBlock), 0, nullptr, scene->device, scene->smallItems,
                        scene->smallLayout.nQuads, scene->smallLayout.kappaT, scene->smallLayout.shadowQuadPairs, scene->smallLayout.shadowLonePairs,
                        scene->itemTris.ptr, deviceRays.ptr, (int)n, deviceOut.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, deviceOut.ptr, n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PATHED_OK;
+}
+
+int pathed_hip_debug_pass_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out, int32_t *primitives, size_t n_triangles,
+                                     int32_t *layout, uint64_t *never_hit)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector's hook does not serve scenes with instances"); }
+    if (!scene->bruteForce || scene->device.nTris < 1) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector serves scenes of 1..64 triangles"); }
+    if (!layout || !never_hit || !primitives) { return fail(PATHED_E_INVALID, "null layout, primitive or never-hit buffer"); }
+    const int nPass = scene->passTris;
+    if (n_triangles != (size_t)scene->device.nTris || nPass < 1 || nPass > scene->device.nTris || scene->passTrisHost.size() < (size_t)12 * nPass) {
+        return fail(PATHED_E_INVALID, "n_triangles must be the scene's triangle count");
+    }
+    layout[0] = scene->passLayout.nQuads;
+    layout[1] = scene->passLayout.nLone;
+    layout[2] = scene->passLayout.shadowQuadPairs;
+    layout[3] = scene->passLayout.shadowLonePairs;
+    layout[4] = nPass;
+    *never_hit = scene->passNeverHit;
+    for (size_t k = 0; k < n_triangles; k++) {
+        primitives[k] = -1;   // (beyond the pass list)
+        if (k < (size_t)nPass) { std::memcpy(&primitives[k], &scene->passTrisHost[12 * k + 3], sizeof(int32_t)); }
+    }
+    if (n == 0) { return PATHED_OK; }
+    if (!rays || !out) { return fail(PATHED_E_INVALID, "null ray or output buffer"); }
+    if (n > (size_t)1 << 24) { return fail(PATHED_E_INVALID, "too many rays in one call"); }
+    SELECT_DEVICE(scene);
+    const size_t padded = (n + kBlock - 1) / kBlock * kBlock;   // whole blocks: the kernel reads a ray per lane
+    std::vector<float> hostRays(padded * 10, 0.f);
+    std::memcpy(hostRays.data(), rays, n * 10 * sizeof(float));
+    for (size_t i = n; i < padded; i++) { hostRays[10 * i + 5] = 1.f; hostRays[10 * i + 8] = 1.f; }
+    DeviceBuffer<float> deviceRays;
+    DeviceBuffer<unsigned long long> deviceOut;
+    HIP_TRY(deviceRays.upload(hostRays));
+    HIP_TRY(deviceOut.allocate(n * 2));
+    hipLaunchKernelGGL(k_debug_pass_candidates, dim3((unsigned)(padded / kBlock)), dim3(kBlock), 0, nullptr, scene->passItems,
+                       scene->passLayout.nQuads, nPass, scene->passLayout.kappaT, scene->passLayout.shadowQuadPairs, scene->passLayout.shadowLonePairs,
+                       scene->itemTris.ptr + (size_t)3 * scene->device.nTris, deviceRays.ptr, (int)n, deviceOut.ptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, deviceOut.ptr, n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));

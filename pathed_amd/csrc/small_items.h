@@ -66,6 +66,25 @@
 // a caller that cannot name the emitters: the triangle is an occluder.  A quad is a never-occluder when both halves are.
 // Cornell (extent 3.49, camera 6.8 away, max k = 2.4): eta = 2.1e-5, Dmin = 0.59; the light is 1.98 / 0.82 / 0.77 / 0.78 from floor, back,
 // right and left wall, 0.01 from the ceiling: 3 of the 17 quads and the two lone triangles.
+//
+// NEVER-HIT (smallNeverHit, buildSmallPassItems below).  Triangle k is never-hit when another triangle with a LOWER primitive id
+// (the int in float 3 of the record, not the position in leafTris) has the same 36 bytes of (v0, e1, e2).  No tolerance is
+// involved: intersectTriangle (trace.h) reads only those nine floats and the ray, so two records with the same bits give the
+// same t, u, v -- or the same rejection -- on every ray.  The closest-hit rule (testLeafTriangle, smallResolveShared's `closer`)
+// is "t < best, or t == best and a lower primitive id", independent of the order of the tests: of two copies the lower id
+// wins whichever is met first.  An any-hit query is occluded by one copy exactly when it is by the other.  The higher-id copy
+// therefore changes no hit record and no radiance sum, and the pass over all items may leave it out.  Bit patterns are compared,
+// not values: +0 against -0 is not a copy (the products' signs of zero may differ), a record one ulp away is not, a rotated or
+// reversed vertex order is not (other arithmetic), and a record holding a NaN is in no class.  Each class keeps its lowest id:
+// three copies keep one.  Spheres are not considered.  CornellBox-Original.obj: each box's "Bottom Face" line names the four
+// vertices of an earlier side face instead (f -12 -11 -10 -9, f -8 -7 -6 -5), so triangles 20, 21 are 16, 17 again and 32, 33
+// are 30, 31: 2 of the 18 quads.
+// The PASS LIST is buildSmallItems run a second time on the kept triangles alone -- records, item-ordered triangle copy and
+// layout of its own, quads paired among kept triangles only -- and is what the non-counting parallelogram instantiations of
+// k_path_small walk for a path vertex's two rays (kernels.h: kSmallPassList).  The item list above stays what it was: the camera
+// masks are in ITS order (the refill resolves against it), the counting instantiations run it whole, and so does every other
+// kernel.  The never-occluder rule of the pass list takes a kept triangle for an emitter when any member of its class emits: the
+// removed copy's surface, where a light sample can land, is the kept triangle's surface.
 #pragma once
 
 #include <algorithm>
@@ -413,6 +432,76 @@ inline SmallItemsLayout buildSmallItems(const float *leafTris, int nTris, const 
         k++;
     }
     return layout;
+}
+
+// marks[k] = 1: triangle k of leafTris is NEVER-HIT (header).  keeper[k]: the triangle of leafTris that stands for k's class,
+// the member with the lowest primitive id (k itself where k has no copy, or holds a NaN).
+inline void smallNeverHit(const float *leafTris, int nTris, std::vector<unsigned char> *marks, std::vector<int> *keeper = nullptr)
+{
+    marks->assign((size_t)std::max(nTris, 0), 0);
+    std::vector<int> lowest((size_t)std::max(nTris, 0));
+    auto primitive = [&](int t) { int id; std::memcpy(&id, leafTris + (size_t)12 * t + 3, sizeof id); return id; };
+    auto sameBits = [&](int a, int b) {   // the 36 bytes of (v0, e1, e2): bit patterns, so +0 is not -0 and a NaN could equal itself...
+        for (int row = 0; row < 3; row++) {
+            if (std::memcmp(leafTris + (size_t)12 * a + 4 * row, leafTris + (size_t)12 * b + 4 * row, 3 * sizeof(float)) != 0) { return false; }
+        }
+        return true;
+    };
+    auto hasNan = [&](int t) {   // ... which is why such a record is left out of every class
+        for (int row = 0; row < 3; row++) {
+            for (int a = 0; a < 3; a++) { if (std::isnan(leafTris[(size_t)12 * t + 4 * row + a])) { return true; } }
+        }
+        return false;
+    };
+    for (int k = 0; k < nTris; k++) {
+        lowest[(size_t)k] = k;
+        if (hasNan(k)) { continue; }
+        for (int other = 0; other < nTris; other++) {
+            if (other != k && !hasNan(other) && sameBits(k, other) && primitive(other) < primitive(lowest[(size_t)k])) { lowest[(size_t)k] = other; }
+        }
+        // (two records of one primitive id cannot both be the lowest: neither is marked, both stay)
+        if (lowest[(size_t)k] != k) { (*marks)[(size_t)k] = 1; }
+    }
+    if (keeper) { *keeper = lowest; }
+}
+
+// The PASS LIST (header: NEVER-HIT): buildSmallItems over the triangles that are not never-hit, in the order leafTris has them.
+// passTris is the item-ordered copy of THOSE triangles (what phase 2 of the pass indexes); the layout counts them:
+// 2 nQuads + nLone = *nPass <= nTris.  A kept triangle counts as an emitter when any member of its class emits (a light sample
+// can land on the removed copy's surface, which is the kept one's).  neverHit: bit (original primitive id & 63) of every
+// triangle left out.  A scene without copies gets what buildSmallItems gives it, byte for byte.
+inline SmallItemsLayout buildSmallPassItems(const float *leafTris, int nTris, const float *extraPoints, int nExtra, bool pairQuads, float tnear,
+                                            float *records, std::vector<float> *passTris, const SmallLights *lights, int *nPass,
+                                            unsigned long long *neverHit = nullptr)
+{
+    std::vector<unsigned char> marks, emitter;
+    std::vector<int> keeper;
+    smallNeverHit(leafTris, nTris, &marks, &keeper);
+    std::vector<float> kept;
+    std::vector<int> place((size_t)std::max(nTris, 0), -1);   // where triangle k went in `kept`
+    unsigned long long word = 0ull;
+    for (int k = 0; k < nTris; k++) {
+        if (marks[(size_t)k]) {
+            int id;
+            std::memcpy(&id, leafTris + (size_t)12 * k + 3, sizeof id);
+            word |= 1ull << (id & 63);
+            continue;
+        }
+        place[(size_t)k] = (int)(kept.size() / 12);
+        kept.insert(kept.end(), leafTris + (size_t)12 * k, leafTris + (size_t)12 * (k + 1));
+    }
+    const int count = (int)(kept.size() / 12);
+    SmallLights passLights = lights ? *lights : SmallLights();
+    if (passLights.emitter) {
+        emitter.assign((size_t)std::max(count, 1), 0);
+        for (int k = 0; k < nTris; k++) {
+            if (passLights.emitter[k]) { emitter[(size_t)place[(size_t)keeper[(size_t)k]]] = 1; }
+        }
+        passLights.emitter = emitter.data();
+    }
+    if (nPass) { *nPass = count; }
+    if (neverHit) { *neverHit = word; }
+    return buildSmallItems(kept.data(), count, extraPoints, nExtra, pairQuads, tnear, records, passTris, lights ? &passLights : nullptr);
 }
 
 }  // namespace pathed

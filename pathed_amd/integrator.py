@@ -401,6 +401,23 @@ class HipScene:
         counts = {"quads": layout[0], "lone": layout[1], "shadow_quad_pairs": layout[2], "shadow_lone_pairs": layout[3]}
         return out, counts, int(never.value)
 
+    def pass_candidates(self, rays, n_triangles):
+        """Both rays' candidates over the fused kernel's pass list -- the item list without exact copies of a lower-numbered
+        triangle -- as the timed kernel runs it (pathed_hip_debug_pass_candidates): rays (n, 10) as small_candidates takes them
+        -> ((n, 2) uint64 (path ray, shadow ray), bit p = primitive id p; the primitive ids in pass order, (n_triangles,) int32,
+        -1 beyond the list; the pass layout's counts as a dict; the never-hit set as an int, bit p = primitive id p)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 10)
+        out = np.zeros((rays.shape[0], 2), dtype=np.uint64)
+        primitives = np.zeros(n_triangles, dtype=np.int32)
+        layout = (C.c_int32 * 5)()
+        never = C.c_uint64(0)
+        code = self._lib.pathed_hip_debug_pass_candidates(
+            self._handle, rays.ctypes.data_as(C.POINTER(C.c_float)), rays.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint64)),
+            primitives.ctypes.data_as(C.POINTER(C.c_int32)), n_triangles, layout, C.byref(never))
+        _check(self._lib, code, "pathed_hip_debug_pass_candidates")
+        counts = {"quads": layout[0], "lone": layout[1], "shadow_quad_pairs": layout[2], "shadow_lone_pairs": layout[3], "triangles": layout[4]}
+        return out, primitives, counts, int(never.value)
+
     def camera_masks(self):
         """The per-pixel candidate masks of the camera rays (pathed_hip_debug_camera_masks; scenes on the fused path kernel):
         (height, width) uint64, bit 63 - k = triangle k of the item order."""

@@ -97,9 +97,9 @@ def main():
     parser.add_argument("--loops", action="store_true")
     parser.add_argument("--json", default="")
     parser.add_argument("--bench-json", default="", help="write the trip-count-weighted mix of the Cornell instantiation of k_path_small (what bench.py times) here")
-    parser.add_argument("--quad-pairs", type=int, default=9, help="trips of the parallelogram-pair loop per pass (Cornell: 17 parallelograms)")
+    parser.add_argument("--quad-pairs", type=int, default=8, help="trips of the parallelogram-pair loop per pass (Cornell: the pass list's 15 parallelograms, 17 less the two exact copies)")
     parser.add_argument("--lone-pairs", type=int, default=1, help="trips of the lone-triangle-pair loop per pass (Cornell: 2 triangles)")
-    parser.add_argument("--shadow-quad-pairs", type=int, default=7, help="... of them run for the shadow ray as well (Cornell: 14 occluder parallelograms)")
+    parser.add_argument("--shadow-quad-pairs", type=int, default=6, help="... of them run for the shadow ray as well (Cornell: 12 occluder parallelograms)")
     parser.add_argument("--shadow-lone-pairs", type=int, default=0, help="lone-pair trips that run for the shadow ray as well (Cornell: none)")
     args = parser.parse_args()
     path = args.asm
@@ -165,7 +165,8 @@ def write_bench_mix(kernels, pretty, args):
         total = collections.Counter()
         for block in blocks.values():
             total.update(block["ops"])
-        # the phase-1 loops, in program order: innermost backward branches over at least 40 packed instructions.  With the shadow
+        # the phase-1 loops, in program order: innermost backward branches over at least 30 packed instructions that make up half of
+        # the body's VALU or more.  With the shadow
         # ray's pruning (kernels.h smallCandidatesItems<PRUNE>) there are three: parallelogram pairs for both rays, parallelogram
         # pairs for the path's ray alone, and the lone pairs, whose shadow half is a block of its own between the loop's first
         # and last block.  Without it two single-block loops, the larger one the parallelogram pairs.
@@ -176,10 +177,19 @@ def write_bench_mix(kernels, pretty, args):
             for target in blocks[label]["targets"]:
                 if target in index and index[target] <= i:
                     body = order[index[target]:i + 1]
-                    if sum(blocks[inner]["ops"]["valu_packed"] for inner in body) >= 40 and not any(set(body) & set(other) for other in loops):
+                    packed = sum(blocks[inner]["ops"]["valu_packed"] for inner in body)
+                    valu = sum(v for inner in body for k, v in blocks[inner]["ops"].items() if k.startswith("valu"))
+                    # (packed-dominated: the path-ray-only lone-pair loop has 34 packed of 43; the shading loops are far below a half)
+                    if packed >= 30 and 2 * packed >= valu and not any(set(body) & set(other) for other in loops):
                         loops.append(body)
         weights = {}
-        if len(loops) >= 3:
+        if len(loops) >= 4:
+            # the lone pairs in two loops as well (both rays, then the path's ray alone): four single-purpose loops
+            pruned = "; the shadow ray runs %d of the parallelogram-pair turns and %d of the lone-pair turns, each section in two loops" % (args.shadow_quad_pairs, args.shadow_lone_pairs)
+            for body, trips in zip(loops, (args.shadow_quad_pairs, args.quad_pairs - args.shadow_quad_pairs, args.shadow_lone_pairs, args.lone_pairs - args.shadow_lone_pairs)):
+                for inner in body:
+                    weights[inner] = trips
+        elif len(loops) >= 3:
             pruned = "; the shadow ray runs %d of the parallelogram-pair turns and %d of the lone-pair turns" % (args.shadow_quad_pairs, args.shadow_lone_pairs)
             for inner in loops[0]:
                 weights[inner] = args.shadow_quad_pairs
