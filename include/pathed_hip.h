@@ -361,7 +361,8 @@ int pathed_hip_scene_device(const PathedScene *scene);   /* the HIP device the s
  * where i is the inverse of m, formed in double from the floats of m by cofactors -- c00 = e k - f h, c01 = c h - b k,
  * c02 = b f - c e, c10 = f g - d k, c11 = a k - c g, c12 = c d - a f, c20 = d h - e g, c21 = b g - a h, c22 = a e - b d for
  * m's 3 x 3 part (a b c / d e f / g h k), det = (a c00 + b c10) + c c20, i3x3 = c / det, translation -((r0 tx + r1 ty) + r2 tz)
- * per row -- and rounded once to float.  pathed_amd.flatten_instances is this routine in numpy.
+ * per row -- and rounded once to float (pathed_amd/csrc/instances.h: instanceInverse).  pathed_amd.flatten_instances is this
+ * routine in numpy.
  *
  * Memory: per instance one 112-byte record; nodes, leaf triangles and shading records exist once per prototype.
  * Such a scene renders on the wavefront with k_trace_instanced / k_shade_instanced whatever its size (PathedStats.path_kernel

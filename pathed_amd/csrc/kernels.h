@@ -4498,141 +4498,6 @@ __global__ __launch_bounds__(kBlock) void k_refit_pass(
     readyOut[n] = 1;
 }
 
-// ------------------------------------------------------------------------- moving placements
-// New transforms for the placements of an instanced scene over an UNCHANGED top tree (pathed_hip_scene_set_instance_transforms):
-// k_instance_records restates every placement's record, k_refit_top_pass refits the top tree around the new world boxes.
-//
-// std::min / std::max as the host's Box::grow evaluates them (bvh_build.h), so that a signed zero lands where the host puts it
-__device__ inline float hostMin(float a, float b) { return b < a ? b : a; }
-__device__ inline float hostMax(float a, float b) { return a < b ? b : a; }
-
-// One thread per placement: the record of buildInstancedBvh (pathed_hip.hip) from 12 floats, the inverse statement for
-// statement as instanceInverse forms it (trace.h; -ffp-contract=off, double division and the conversions round as the host's),
-// refused by the same two tests.  Quad 6 (base, prototype, root node, first shading record) comes from the live record.
-// bad[0] counts the refused transforms, bad[1] keeps the lowest refused index; a refused placement writes no record.
-__global__ __launch_bounds__(kBlock) void k_instance_records(const float *transforms, int nInstances, const float4 *live, float4 *staged, unsigned int *bad)
-{
-    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
-    if (i >= nInstances) { return; }
-    float m[12], inverse[12];
-    bool fine = true;
-    for (int k = 0; k < 12; k++) {
-        m[k] = transforms[(size_t)12 * i + k];
-        if (!(m[k] - m[k] == 0.f)) { fine = false; }
-    }
-    const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], k = m[10];
-    const double c00 = e * k - f * h, c01 = c * h - b * k, c02 = b * f - c * e;
-    const double c10 = f * g - d * k, c11 = a * k - c * g, c12 = c * d - a * f;
-    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
-    const double det = (a * c00 + b * c10) + c * c20;
-    if (!(det != 0.0) || !(det - det == 0.0)) { fine = false; }
-    const double r[9] = { c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det };
-    const double tx = m[3], ty = m[7], tz = m[11];
-    for (int row = 0; row < 3; row++) {
-        for (int col = 0; col < 3; col++) { inverse[4 * row + col] = (float)r[3 * row + col]; }
-        inverse[4 * row + 3] = (float)(-((r[3 * row] * tx + r[3 * row + 1] * ty) + r[3 * row + 2] * tz));
-    }
-    for (int n = 0; n < 12; n++) { if (!(inverse[n] - inverse[n] == 0.f)) { fine = false; } }
-    if (!fine) {
-        atomicAdd(&bad[0], 1u);
-        atomicMin(&bad[1], (unsigned int)i);
-        return;
-    }
-    float4 *record = staged + (size_t)kInstanceQuads * i;
-    for (int row = 0; row < 3; row++) {
-        record[row] = make_float4(m[4 * row], m[4 * row + 1], m[4 * row + 2], m[4 * row + 3]);
-        record[3 + row] = make_float4(inverse[4 * row], inverse[4 * row + 1], inverse[4 * row + 2], inverse[4 * row + 3]);
-    }
-    record[6] = live[(size_t)kInstanceQuads * i + 6];
-}
-
-// One thread per node of the TOP tree, nodes [0, topNodes) and nothing behind them (the prototypes' trees follow in the same
-// array, in object space: they do not move), level-synchronous with double-buffered flags like k_refit_pass.  Per child:
-//   instance leaf   (-ref - 1) & kInstanceLeafBit: the world box of buildInstancedBvh (pathed_hip.hip), statement for statement
-//                   -- the eight corners of the prototype's padded box (protoBoxes: lo, hi per prototype) through flattenPoint
-//                   with the record's rows, min / max, the pad 1e-5 max(1, |lo|, |hi|) + 1e-5 (hi - lo) -- then padBox's rule
-//                   for the node's copy; the box BEFORE padBox joins the node's own bounds, as the builder's does
-//   triangle leaf   world triangles do not move: the stored (padded) box stays and joins the node's own bounds
-//   inner child     padBox of the unpadded bounds kept beside the nodes (boundsLo / boundsHi, topNodes entries)
-//   empty           stays
-// A reference that points outside its array (no tree of the builder holds one) leaves the stored box alone.
-__global__ __launch_bounds__(kBlock) void k_refit_top_pass(
-    float4 *nodes, int topNodes, const float4 *records, int nInstances, const float4 *protoBoxes, int nPrototypes,
-    float4 *boundsLo, float4 *boundsHi, const unsigned char *readyIn, unsigned char *readyOut)
-{
-    const int n = blockIdx.x * kBlock + threadIdx.x;
-    if (n >= topNodes) { return; }
-    if (readyIn[n]) { readyOut[n] = 1; return; }
-    float4 *node = nodes + (size_t)8 * n;
-    const float4 refWords = node[6];
-    const int refs[4] = { floatAsInt(refWords.x), floatAsInt(refWords.y), floatAsInt(refWords.z), floatAsInt(refWords.w) };
-    for (int k = 0; k < 4; k++) {
-        if (refs[k] >= 0 && refs[k] < topNodes && !readyIn[refs[k]]) { readyOut[n] = 0; return; }   // an inner child is not fitted yet
-    }
-    const float inf = __builtin_huge_valf();
-    float lo[3][4], hi[3][4];
-    for (int a = 0; a < 3; a++) {
-        const float4 low = node[a], high = node[3 + a];
-        lo[a][0] = low.x; lo[a][1] = low.y; lo[a][2] = low.z; lo[a][3] = low.w;
-        hi[a][0] = high.x; hi[a][1] = high.y; hi[a][2] = high.z; hi[a][3] = high.w;
-    }
-    float ownLo[3] = { inf, inf, inf }, ownHi[3] = { -inf, -inf, -inf };
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int ref = refs[k];
-        if (ref == kEmptyChild) { continue; }
-        float low[3] = { lo[0][k], lo[1][k], lo[2][k] }, high[3] = { hi[0][k], hi[1][k], hi[2][k] };
-        bool padded = true;   // low / high are the stored box: nothing to pad, nothing to write
-        if (ref >= 0) {
-            if (ref < topNodes) {
-                const float4 a = boundsLo[ref], b = boundsHi[ref];
-                low[0] = a.x; low[1] = a.y; low[2] = a.z; high[0] = b.x; high[1] = b.y; high[2] = b.z;
-                padded = false;
-            }
-        } else {
-            const int code = -ref - 1;
-            const int instance = code & (kInstanceLeafBit - 1);
-            if ((code & kInstanceLeafBit) && instance < nInstances) {
-                const float4 *record = records + (size_t)kInstanceQuads * instance;
-                const float4 r0 = record[0], r1 = record[1], r2 = record[2];
-                const int prototype = floatAsInt(record[6].y);
-                if (prototype >= 0 && prototype < nPrototypes) {
-                    const float m[12] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w };
-                    const float4 protoLo = protoBoxes[2 * prototype], protoHi = protoBoxes[2 * prototype + 1];
-                    float boxLo[3] = { inf, inf, inf }, boxHi[3] = { -inf, -inf, -inf };
-                    for (int corner = 0; corner < 8; corner++) {
-                        const V3 world = flattenPoint(m, v3((corner & 1) ? protoHi.x : protoLo.x, (corner & 2) ? protoHi.y : protoLo.y, (corner & 4) ? protoHi.z : protoLo.z));
-                        const float point[3] = { world.x, world.y, world.z };
-                        for (int a = 0; a < 3; a++) { boxLo[a] = hostMin(boxLo[a], point[a]); boxHi[a] = hostMax(boxHi[a], point[a]); }
-                    }
-                    for (int a = 0; a < 3; a++) {
-                        const float pad = 1e-5f * hostMax(1.f, hostMax(fabsf(boxLo[a]), fabsf(boxHi[a]))) + 1e-5f * (boxHi[a] - boxLo[a]);
-                        low[a] = boxLo[a] - pad;
-                        high[a] = boxHi[a] + pad;
-                    }
-                    padded = false;
-                }
-            }
-        }
-        for (int a = 0; a < 3; a++) {
-            ownLo[a] = hostMin(ownLo[a], low[a]);
-            ownHi[a] = hostMax(ownHi[a], high[a]);
-            if (!padded) {
-                const float pad = 1e-5f * hostMax(1.f, hostMax(fabsf(low[a]), fabsf(high[a])));   // bvh_build.h: padBox
-                lo[a][k] = low[a] - pad;
-                hi[a][k] = high[a] + pad;
-            }
-        }
-    }
-    for (int a = 0; a < 3; a++) {
-        node[a] = make_float4(lo[a][0], lo[a][1], lo[a][2], lo[a][3]);
-        node[3 + a] = make_float4(hi[a][0], hi[a][1], hi[a][2], hi[a][3]);
-    }
-    boundsLo[n] = make_float4(ownLo[0], ownLo[1], ownLo[2], 0.f);
-    boundsHi[n] = make_float4(ownHi[0], ownHi[1], ownHi[2], 0.f);
-    readyOut[n] = 1;
-}
-
 // ------------------------------------------------------------------------- bandwidth probe
 // What this box's HBM actually delivers to a plain streaming kernel: the second denominator beside
 // the 8 TB/s spec figure.  16 bytes per lane per access, grid-stride.
@@ -4721,69 +4586,6 @@ __global__ __launch_bounds__(kBlock) void k_accum_add(float *dst, const float *s
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) { dst[i] += src[i]; }
 }
 
-// ------------------------------------------------------------------------- rebuilding the top tree
-// pathed_hip_scene_rebuild_top: a NEW top tree over the world triangles and the placements' current world boxes (lbvh.hip:
-// buildTopBvhOnDevice), the prototypes' trees copied behind it.
-//
-// One thread per placement: its world box, (lo, hi) as two float4.  THE THIRD COPY of the rule -- buildInstancedBvh
-// (pathed_hip.hip) on the host, k_refit_top_pass above, and here; numpy states it as pathed_amd.instances.placement_box --
-// statement for statement: the eight corners of the prototype's padded box through flattenPoint with the live record's rows,
-// std::min / std::max, the pad 1e-5 max(1, |lo|, |hi|) + 1e-5 (hi - lo).  (Restated, not shared: k_refit_top_pass keeps its
-// 73 VGPRs and no scratch as it stands.)  A prototype index outside the table -- no record of the library holds one -- gives
-// an empty box at the origin instead of a read out of bounds.
-__global__ __launch_bounds__(kBlock) void k_placement_boxes(const float4 *records, int nInstances, const float4 *protoBoxes, int nPrototypes, float4 *boxes)
-{
-    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
-    if (i >= nInstances) { return; }
-    const float4 *record = records + (size_t)kInstanceQuads * i;
-    const float4 r0 = record[0], r1 = record[1], r2 = record[2];
-    const int prototype = floatAsInt(record[6].y);
-    float low[3] = { 0.f, 0.f, 0.f }, high[3] = { 0.f, 0.f, 0.f };
-    if (prototype >= 0 && prototype < nPrototypes) {
-        const float inf = __builtin_huge_valf();
-        const float m[12] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w };
-        const float4 protoLo = protoBoxes[2 * prototype], protoHi = protoBoxes[2 * prototype + 1];
-        float boxLo[3] = { inf, inf, inf }, boxHi[3] = { -inf, -inf, -inf };
-        for (int corner = 0; corner < 8; corner++) {
-            const V3 world = flattenPoint(m, v3((corner & 1) ? protoHi.x : protoLo.x, (corner & 2) ? protoHi.y : protoLo.y, (corner & 4) ? protoHi.z : protoLo.z));
-            const float point[3] = { world.x, world.y, world.z };
-            for (int a = 0; a < 3; a++) { boxLo[a] = hostMin(boxLo[a], point[a]); boxHi[a] = hostMax(boxHi[a], point[a]); }
-        }
-        for (int a = 0; a < 3; a++) {
-            const float pad = 1e-5f * hostMax(1.f, hostMax(fabsf(boxLo[a]), fabsf(boxHi[a]))) + 1e-5f * (boxHi[a] - boxLo[a]);
-            low[a] = boxLo[a] - pad;
-            high[a] = boxHi[a] + pad;
-        }
-    }
-    boxes[2 * (size_t)i] = make_float4(low[0], low[1], low[2], 0.f);
-    boxes[2 * (size_t)i + 1] = make_float4(high[0], high[1], high[2], 0.f);
-}
-
-// The prototypes' trees, nodes [oldTop, oldCount) of the old array, copied behind the new top tree: one thread per float4.
-// Their inner references (>= 0) move by delta = newTop - oldTop; leaf references are absolute into the leaf triangles, whose
-// layout [world | prototypes] keeps its size, and stay, as do the boxes.
-__global__ __launch_bounds__(kBlock) void k_rebase_prototype_nodes(const float4 *oldNodes, int oldTop, int oldCount, float4 *newNodes, int newTop)
-{
-    const size_t quad = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (quad >= (size_t)8 * (size_t)(oldCount - oldTop)) { return; }
-    float4 value = oldNodes[(size_t)8 * oldTop + quad];
-    if ((quad & 7) == 6) {
-        const int delta = newTop - oldTop;
-        int refs[4] = { floatAsInt(value.x), floatAsInt(value.y), floatAsInt(value.z), floatAsInt(value.w) };
-        for (int k = 0; k < 4; k++) { if (refs[k] >= 0) { refs[k] += delta; } }
-        value = make_float4(__int_as_float(refs[0]), __int_as_float(refs[1]), __int_as_float(refs[2]), __int_as_float(refs[3]));
-    }
-    newNodes[(size_t)8 * newTop + quad] = value;
-}
-
-// ... and every placement's record into the staged buffer with its protoRoot (word 2 of quad 6) moved by the same delta
-__global__ __launch_bounds__(kBlock) void k_rebase_instance_roots(const float4 *live, float4 *staged, int nInstances, int delta)
-{
-    const size_t quad = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (quad >= (size_t)kInstanceQuads * (size_t)nInstances) { return; }
-    float4 value = live[quad];
-    if (quad % kInstanceQuads == 6) { value.z = __int_as_float(floatAsInt(value.z) + delta); }
-    staged[quad] = value;
-}
-
 }  // namespace pathed
+
+#include "instance_kernels.h"   // k_instance_records, k_refit_top_pass, k_placement_boxes, k_rebase_prototype_nodes, k_rebase_instance_roots

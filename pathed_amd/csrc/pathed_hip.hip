@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -106,6 +107,20 @@ struct DeviceBuffer {
         ptr = nullptr;
         count = 0;
     }
+
+    // takes ownership of a raw hipMalloc'ed allocation of n elements (null: of nothing)
+    void adopt(T *allocation, size_t n)
+    {
+        release();
+        ptr = allocation;
+        count = allocation ? n : 0;
+    }
+
+    void swap(DeviceBuffer &other)
+    {
+        std::swap(ptr, other.ptr);
+        std::swap(count, other.count);
+    }
 };
 
 struct EventRing {
@@ -167,6 +182,74 @@ struct EventRing {
             (void)hipEventDestroy(stop[i]);
         }
         created = false;
+    }
+};
+
+// One start / stop event pair for the entry points that report a device time.  run() times one stretch of launches and adds
+// it to `ms`; `status` keeps the FIRST error, after which nothing more is recorded or launched.
+struct EventTimer {
+    hipEvent_t start = nullptr, stop = nullptr;
+    hipError_t status = hipSuccess;
+    float ms = 0.f;
+
+    EventTimer()
+    {
+        keep(hipEventCreate(&start));
+        if (ok()) { keep(hipEventCreate(&stop)); }
+    }
+    EventTimer(const EventTimer &) = delete;
+    EventTimer &operator=(const EventTimer &) = delete;
+    ~EventTimer()
+    {
+        if (start) { (void)hipEventDestroy(start); }
+        if (stop) { (void)hipEventDestroy(stop); }
+    }
+
+    bool ok() const { return status == hipSuccess; }
+    bool keep(hipError_t result)
+    {
+        if (ok()) { status = result; }
+        return ok();
+    }
+
+    // the device time of this stretch, which has finished on return (0 after an error)
+    template <typename Launches>
+    float run(Launches &&launches, hipStream_t stream = nullptr)
+    {
+        float part = 0.f;
+        if (ok() && keep(hipEventRecord(start, stream))) {
+            launches();
+            keep(hipGetLastError());
+        }
+        if (ok() && keep(hipEventRecord(stop, stream)) && keep(hipEventSynchronize(stop))) { keep(hipEventElapsedTime(&part, start, stop)); }
+        ms += part;
+        return part;
+    }
+};
+
+// The level-synchronous passes of a bottom-up refit (kernels.h: k_refit_pass; instance_kernels.h: k_refit_top_pass) over a
+// tree of nNodes nodes.  `ready` holds two flag arrays of nNodes bytes, cleared by the caller; a pass reads one and writes the
+// other, and launchPass(in, out) launches one.
+struct LevelPasses {
+    unsigned char *ready;
+    size_t nNodes;
+    std::function<void(const unsigned char *in, unsigned char *out)> launchPass;
+    int passes = 0;
+
+    void launch(int count)
+    {
+        for (int k = 0; k < count; k++, passes++) { launchPass(ready + (size_t)(passes & 1) * nNodes, ready + (size_t)((passes + 1) & 1) * nNodes); }
+    }
+    // one pass per 4-wide level, back to back (no look at the flags in between: a host round trip costs more than a pass)
+    void launchLevels(int depth) { launch(depth > 0 ? depth + 1 : 16); }
+    // After launchLevels: whether the root was reached.  A tree deeper than its recorded depth keeps going, four passes per
+    // look at the root's flag and 4096 passes at most; their device time joins the timer's.
+    bool reachRoot(EventTimer &timer)
+    {
+        unsigned char rootReady = 0;
+        const auto look = [&]() { return timer.ok() && timer.keep(hipMemcpy(&rootReady, ready + (size_t)(passes & 1) * nNodes, 1, hipMemcpyDeviceToHost)); };
+        while (look() && !rootReady && passes < 4096) { timer.run([&]() { launch(4); }); }
+        return rootReady != 0;
     }
 };
 
@@ -702,9 +785,8 @@ static void sortProbe(PathedScene *scene, const RenderParams &q, hipStream_t str
             && hipMemcpy(dO[v], orderedO[v].data(), n * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess
             && hipMemcpy(dD[v], orderedD[v].data(), n * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess;
     }
-    hipEvent_t start = nullptr, stop = nullptr;
-    ok = ok && hipEventCreate(&start) == hipSuccess && hipEventCreate(&stop) == hipSuccess;
-    if (ok) {
+    EventTimer timer;
+    if (ok && timer.ok()) {
         fprintf(stderr, "[pathed] sort probe: %zu slots, %zu rays for the trace kernel (%.3f of the slots), shadow list left out\n", n, traced.size(), (double)traced.size() / (double)n);
         for (int repeat = 0; repeat < 3; repeat++) {
             for (int v = -1; v < kOrders; v++) {
@@ -714,19 +796,12 @@ static void sortProbe(PathedScene *scene, const RenderParams &q, hipStream_t str
                 probe.counters = dCounters;
                 probe.suspendLanes = 0;   // no parking: the whole pool in one launch
                 (void)hipMemsetAsync(dCounters, 0, kCtrCount * sizeof(unsigned int), stream);
-                (void)hipEventRecord(start, stream);
-                launchTrace(scene, probe, stream);
-                (void)hipEventRecord(stop, stream);
-                (void)hipEventSynchronize(stop);
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, start, stop);
+                const float ms = timer.run([&]() { launchTrace(scene, probe, stream); }, stream);
                 fprintf(stderr, "[pathed] sort probe: k_trace over the rays %s: %.1f us (%.2f Grays/s)\n",
                         v < 0 ? "as they lie in the pool" : v == 0 ? "compacted, in slot order" : v == 1 ? "by direction octant" : "by (octant, origin cell, direction cell)", 1e3 * ms, (double)traced.size() / (1e6 * ms));
             }
         }
     }
-    if (start) { (void)hipEventDestroy(start); }
-    if (stop) { (void)hipEventDestroy(stop); }
     for (int v = 0; v < kOrders; v++) { if (dO[v]) { (void)hipFree(dO[v]); } if (dD[v]) { (void)hipFree(dD[v]); } }
     if (dHit) { (void)hipFree(dHit); }
     if (dCounters) { (void)hipFree(dCounters); }
@@ -894,41 +969,25 @@ int pathed_hip_measure_bandwidth(size_t bytes, int repeats, double *read_gbs, do
     const size_t count = bytes / sizeof(float4);
     DeviceBuffer<float4> source, target;
     DeviceBuffer<float> sink;
-    hipEvent_t start = nullptr, stop = nullptr;
-    auto cleanup = [&]() {
-        source.release(); target.release(); sink.release();
-        if (start) { (void)hipEventDestroy(start); }
-        if (stop) { (void)hipEventDestroy(stop); }
-    };
     hipError_t status = source.allocate(count);
     if (status == hipSuccess) { status = target.allocate(count); }
     if (status == hipSuccess) { status = sink.allocate(1); }
     if (status == hipSuccess) { status = hipMemset(source.ptr, 0, count * sizeof(float4)); }
     if (status == hipSuccess) { status = hipMemset(target.ptr, 0, count * sizeof(float4)); }
-    if (status == hipSuccess) { status = hipEventCreate(&start); }
-    if (status == hipSuccess) { status = hipEventCreate(&stop); }
-    if (status != hipSuccess) { cleanup(); return fail(PATHED_E_DEVICE, std::string("bandwidth probe: ") + hipGetErrorString(status)); }
+    EventTimer timer;
+    if (status == hipSuccess) { status = timer.status; }
+    if (status != hipSuccess) { return fail(PATHED_E_DEVICE, std::string("bandwidth probe: ") + hipGetErrorString(status)); }
 
     hipDeviceProp_t properties;
     int units = 256;
     if (hipGetDeviceProperties(&properties, g_device) == hipSuccess && properties.multiProcessorCount > 0) { units = properties.multiProcessorCount; }
     const dim3 grid((unsigned)(units * 16)), block(kBlock);
-    float readMs = 0.f, copyMs = 0.f;
     hipLaunchKernelGGL(k_stream_read, grid, block, 0, nullptr, source.ptr, count, sink.ptr);   // warm-up
     hipLaunchKernelGGL(k_stream_copy, grid, block, 0, nullptr, source.ptr, target.ptr, count);
-    (void)hipEventRecord(start, nullptr);
-    for (int r = 0; r < repeats; r++) { hipLaunchKernelGGL(k_stream_read, grid, block, 0, nullptr, source.ptr, count, sink.ptr); }
-    (void)hipEventRecord(stop, nullptr);
-    status = hipEventSynchronize(stop);
-    if (status == hipSuccess) { status = hipEventElapsedTime(&readMs, start, stop); }
-    (void)hipEventRecord(start, nullptr);
-    for (int r = 0; r < repeats; r++) { hipLaunchKernelGGL(k_stream_copy, grid, block, 0, nullptr, source.ptr, target.ptr, count); }
-    (void)hipEventRecord(stop, nullptr);
-    if (status == hipSuccess) { status = hipEventSynchronize(stop); }
-    if (status == hipSuccess) { status = hipEventElapsedTime(&copyMs, start, stop); }
-    cleanup();
-    if (status != hipSuccess || !(readMs > 0.f) || !(copyMs > 0.f)) {
-        return fail(PATHED_E_DEVICE, std::string("bandwidth probe: ") + hipGetErrorString(status));
+    const float readMs = timer.run([&]() { for (int r = 0; r < repeats; r++) { hipLaunchKernelGGL(k_stream_read, grid, block, 0, nullptr, source.ptr, count, sink.ptr); } });
+    const float copyMs = timer.run([&]() { for (int r = 0; r < repeats; r++) { hipLaunchKernelGGL(k_stream_copy, grid, block, 0, nullptr, source.ptr, target.ptr, count); } });
+    if (!timer.ok() || !(readMs > 0.f) || !(copyMs > 0.f)) {
+        return fail(PATHED_E_DEVICE, std::string("bandwidth probe: ") + hipGetErrorString(timer.status));
     }
     const double moved = (double)count * sizeof(float4) * repeats;
     *read_gbs = moved / (readMs * 1e-3) / 1e9;
@@ -959,11 +1018,10 @@ int pathed_hip_measure_valu_modes(int waves_per_simd, int repeats, double *rates
     hipDeviceProp_t properties;
     int units = 256;
     if (hipGetDeviceProperties(&properties, device) == hipSuccess && properties.multiProcessorCount > 0) { units = properties.multiProcessorCount; }
-    float *sink = nullptr;
-    hipEvent_t start = nullptr, stop = nullptr;
-    hipError_t status = hipMalloc((void **)&sink, sizeof(float));
-    if (status == hipSuccess) { status = hipEventCreate(&start); }
-    if (status == hipSuccess) { status = hipEventCreate(&stop); }
+    DeviceBuffer<float> sinkBuffer;
+    EventTimer timer;
+    timer.keep(sinkBuffer.allocate(1));
+    float *sink = sinkBuffer.ptr;
     // one 256-thread block = one wave on each of a CU's four SIMDs; k blocks per CU = k waves per SIMD
     const dim3 grid((unsigned)(units * waves_per_simd)), block(kBlock);
     const int iterations = 8192;   // 393 216 instructions per wave and launch
@@ -977,22 +1035,13 @@ int pathed_hip_measure_valu_modes(int waves_per_simd, int repeats, double *rates
         }
     };
     const double issued = (double)grid.x * kWavesPerBlock * (double)iterations * kValuProbeUnroll * repeats;
-    for (int mode = 0; mode < n_modes && status == hipSuccess; mode++) {
-        float ms = 0.f;
+    for (int mode = 0; mode < n_modes && timer.ok(); mode++) {
         launch(mode);   // warm-up
-        (void)hipEventRecord(start, nullptr);
-        for (int r = 0; r < repeats; r++) { launch(mode); }
-        (void)hipEventRecord(stop, nullptr);
-        status = hipEventSynchronize(stop);
-        if (status == hipSuccess) { status = hipEventElapsedTime(&ms, start, stop); }
-        if (status == hipSuccess) { status = hipGetLastError(); }
-        if (status == hipSuccess && !(ms > 0.f)) { status = hipErrorUnknown; }
-        if (status == hipSuccess) { rates[mode] = issued / (ms * 1e-3); }
+        const float ms = timer.run([&]() { for (int r = 0; r < repeats; r++) { launch(mode); } });
+        if (timer.ok() && !(ms > 0.f)) { timer.keep(hipErrorUnknown); }
+        if (timer.ok()) { rates[mode] = issued / (ms * 1e-3); }
     }
-    if (sink) { (void)hipFree(sink); }
-    if (start) { (void)hipEventDestroy(start); }
-    if (stop) { (void)hipEventDestroy(stop); }
-    if (status != hipSuccess) { return fail(PATHED_E_DEVICE, std::string("VALU probe: ") + hipGetErrorString(status)); }
+    if (!timer.ok()) { return fail(PATHED_E_DEVICE, std::string("VALU probe: ") + hipGetErrorString(timer.status)); }
     return PATHED_OK;
 }
 
@@ -1022,29 +1071,21 @@ int pathed_hip_measure_valu_clocks(int waves_per_simd, int chains, int repeats, 
     const dim3 grid((unsigned)(units * waves_per_simd)), block(kBlock);
     const size_t waves = (size_t)grid.x * kWavesPerBlock;
     const int iterations = 8192;   // 393 216 instructions per wave and launch
-    float *sink = nullptr;
-    unsigned long long *clocks = nullptr;
-    hipEvent_t start = nullptr, stop = nullptr;
-    hipError_t status = hipMalloc((void **)&sink, sizeof(float));
-    if (status == hipSuccess) { status = hipMalloc((void **)&clocks, 2 * waves * sizeof(unsigned long long)); }
-    if (status == hipSuccess) { status = hipEventCreate(&start); }
-    if (status == hipSuccess) { status = hipEventCreate(&stop); }
+    DeviceBuffer<float> sinkBuffer;
+    DeviceBuffer<unsigned long long> clockBuffer;
+    EventTimer timer;
+    if (timer.keep(sinkBuffer.allocate(1))) { timer.keep(clockBuffer.allocate(2 * waves)); }
+    float *sink = sinkBuffer.ptr;
+    unsigned long long *clocks = clockBuffer.ptr;
     auto launch = [&]() {
         if (chains == 16) { hipLaunchKernelGGL((k_valu_clock_probe<16>), grid, block, 0, nullptr, iterations, 1.f, sink, clocks); }
         else { hipLaunchKernelGGL((k_valu_clock_probe<8>), grid, block, 0, nullptr, iterations, 1.f, sink, clocks); }
     };
-    float ms = 0.f;
-    if (status == hipSuccess) {
-        launch();   // warm-up
-        (void)hipEventRecord(start, nullptr);
-        for (int r = 0; r < repeats; r++) { launch(); }
-        (void)hipEventRecord(stop, nullptr);
-        status = hipEventSynchronize(stop);
-    }
-    if (status == hipSuccess) { status = hipEventElapsedTime(&ms, start, stop); }
+    if (timer.ok()) { launch(); }   // warm-up
+    const float ms = timer.run([&]() { for (int r = 0; r < repeats; r++) { launch(); } });
     std::vector<unsigned long long> host(2 * waves);
-    if (status == hipSuccess) { status = hipMemcpy(host.data(), clocks, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost); }
-    if (status == hipSuccess && ms > 0.f) {
+    if (timer.ok()) { timer.keep(hipMemcpy(host.data(), clocks, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost)); }
+    if (timer.ok() && ms > 0.f) {
         const double perWave = (double)iterations * kValuProbeUnroll;   // instructions of the last launch's waves
         double shaderTicks = 0.0, wallTicks = 0.0;
         for (size_t w = 0; w < waves; w++) { shaderTicks += (double)host[2 * w]; wallTicks += (double)host[2 * w + 1]; }
@@ -1060,11 +1101,7 @@ int pathed_hip_measure_valu_clocks(int waves_per_simd, int chains, int repeats, 
         const double simds = (double)units * 4.0;
         out->cycles_per_instruction_events = out->shader_clock_mhz > 0.0 ? simds * out->shader_clock_mhz * 1e6 / out->rate : 0.0;
     }
-    if (sink) { (void)hipFree(sink); }
-    if (clocks) { (void)hipFree(clocks); }
-    if (start) { (void)hipEventDestroy(start); }
-    if (stop) { (void)hipEventDestroy(stop); }
-    if (status != hipSuccess) { return fail(PATHED_E_DEVICE, std::string("VALU clock probe: ") + hipGetErrorString(status)); }
+    if (!timer.ok()) { return fail(PATHED_E_DEVICE, std::string("VALU clock probe: ") + hipGetErrorString(timer.status)); }
     return PATHED_OK;
 #endif
 }
@@ -1341,19 +1378,14 @@ static hipError_t rebuildCameraMasks(PathedScene *scene)
     if (scene->cameraQueue.count < quads && (status = scene->cameraQueue.allocate(quads)) != hipSuccess) { return status; }
     const int nPixels = scene->width * scene->height;
     const size_t words = cameraMaskWords(nPixels);
-    hipEvent_t start = nullptr, stop = nullptr;
-    const bool timed = hipEventCreate(&start) == hipSuccess && hipEventCreate(&stop) == hipSuccess;
-    if (timed) { (void)hipEventRecord(start, nullptr); }
-    hipLaunchKernelGGL(k_build_camera_masks, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, nullptr, scene->device.camera,
-                       scene->itemTris.ptr, scene->device.nTris, nPixels, reinterpret_cast<unsigned long long *>(scene->cameraQueue.ptr));
-    if (timed) { (void)hipEventRecord(stop, nullptr); }
-    status = hipGetLastError();
-    if (status == hipSuccess) { status = hipDeviceSynchronize(); }
-    float ms = 0.f;
-    if (timed && status == hipSuccess && hipEventElapsedTime(&ms, start, stop) == hipSuccess) { scene->cameraMaskMs = ms; }
-    if (start) { (void)hipEventDestroy(start); }
-    if (stop) { (void)hipEventDestroy(stop); }
-    if (status != hipSuccess) { return status; }
+    EventTimer timer;
+    timer.run([&]() {
+        hipLaunchKernelGGL(k_build_camera_masks, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, nullptr, scene->device.camera,
+                           scene->itemTris.ptr, scene->device.nTris, nPixels, reinterpret_cast<unsigned long long *>(scene->cameraQueue.ptr));
+    });
+    if (timer.ok()) { timer.keep(hipDeviceSynchronize()); }
+    if (!timer.ok()) { return timer.status; }
+    scene->cameraMaskMs = timer.ms;
     scene->cameraMasksBuilt = true;
     return hipSuccess;
 }
@@ -1519,187 +1551,10 @@ static SceneTraitFlags sceneTraits(const PathedSceneDesc *desc, const std::vecto
     return t;
 }
 
-// ---- instanced scenes (include/pathed_hip.h: PathedInstanceDesc; pathed_amd/csrc/trace.h: "Instances")
-struct InstancedLayout {
-    int worldTris = 0;                        // T0
-    std::vector<int> protoFirst, protoCount;  // triangle range of each prototype in the description
-    std::vector<int> bases;                   // nInstances + 1 virtual-id bases
-    std::vector<float> inverses;              // 12 floats per instance
-};
-
-// Everything that can be refused about an instanced scene, before anything is allocated or launched.
-static int planInstances(const PathedSceneDesc *desc, const PathedSceneOptions &options, const PathedInstanceDesc *in, InstancedLayout *layout)
-{
-    if (in->struct_size != sizeof(PathedInstanceDesc)) { return fail(PATHED_E_INVALID, "PathedInstanceDesc.struct_size mismatch"); }
-    if ((in->n_prototypes && !in->prototypes) || (in->n_instances && !in->instances)) { return fail(PATHED_E_INVALID, "prototype or instance array missing"); }
-    if (in->n_instances >= (1u << 30) - 1u) { return fail(PATHED_E_INVALID, "too many instances (the limit is 2^30 - 2)"); }
-    if (desc->n_spheres > 0) { return fail(PATHED_E_UNSUPPORTED, "sphere primitives in a scene with instances are not supported"); }
-    bool containers = false;
-    for (uint32_t i = 0; i < desc->n_materials; i++) { containers = containers || desc->materials[i].type == PATHED_MAT_PASSTHROUGH; }
-    if (desc->n_media > 0 || containers) { return fail(PATHED_E_UNSUPPORTED, "media and containers (passthrough materials) in a scene with instances are not supported"); }
-    if (options.refittable) { return fail(PATHED_E_UNSUPPORTED, "refittable: a scene with instances cannot be refitted"); }
-    if (options.bvh_builder > PATHED_BVH_SAH_HOST + 1) { return fail(PATHED_E_UNSUPPORTED, "the device builders (LBVH, PLOC) do not build a scene with instances: use the host SAH builder"); }
-    if (options.shade_kernel != 0 && options.shade_kernel != 1) { return fail(PATHED_E_UNSUPPORTED, "shade_kernel: a scene with instances renders on the wavefront's per-slot pair only (0 or 1)"); }
-    if (options.node_format >= 2) { return fail(PATHED_E_UNSUPPORTED, "node_format: a scene with instances is walked over the 128-byte float nodes"); }
-    // the geoms cover the triangles in order; the prototypes' geoms are the tail of the array, prototype after prototype
-    uint32_t nextTriangle = 0;
-    for (uint32_t g = 0; g < desc->n_geoms; g++) {
-        if (desc->geoms[g].type != PATHED_GEOM_MESH || (uint32_t)desc->geoms[g].first != nextTriangle) {
-            return fail(PATHED_E_INVALID, "a scene with instances: the mesh geoms must cover the triangles in order, without gaps");
-        }
-        nextTriangle += (uint32_t)desc->geoms[g].count;
-    }
-    if (nextTriangle != desc->n_triangles) { return fail(PATHED_E_INVALID, "a scene with instances: the mesh geoms must cover all triangles"); }
-    if (desc->n_triangles >= (1u << 27)) { return fail(PATHED_E_INVALID, "a scene with instances stores fewer than 2^27 triangles (the instance leaf encoding)"); }
-    uint32_t firstProtoGeom = desc->n_geoms;
-    if (in->n_prototypes > 0) { firstProtoGeom = (uint32_t)in->prototypes[0].first_geom; }
-    uint32_t nextGeom = firstProtoGeom;
-    for (uint32_t p = 0; p < in->n_prototypes; p++) {
-        const PathedPrototype &proto = in->prototypes[p];
-        if (proto.first_geom < 0 || proto.n_geoms < 1 || (uint32_t)proto.first_geom != nextGeom || (uint64_t)nextGeom + (uint64_t)proto.n_geoms > desc->n_geoms) {
-            return fail(PATHED_E_INVALID, "prototypes must name consecutive, non-empty geom ranges that end the geom array");
-        }
-        const int first = desc->geoms[nextGeom].first;
-        int count = 0;
-        for (int g = 0; g < proto.n_geoms; g++) { count += desc->geoms[nextGeom + (uint32_t)g].count; }
-        if (count < 1) { return fail(PATHED_E_INVALID, "a prototype needs at least one triangle"); }
-        for (int i = 0; i < count; i++) {
-            const PathedMaterial &material = desc->materials[(size_t)desc->tri_material[first + i]];
-            if (!(material.emit[0] == 0.f && material.emit[1] == 0.f && material.emit[2] == 0.f)) {
-                return fail(PATHED_E_UNSUPPORTED, "an emissive material inside a prototype is not supported: bake such faces into world triangles, one copy per placement");
-            }
-        }
-        layout->protoFirst.push_back(first);
-        layout->protoCount.push_back(count);
-        nextGeom += (uint32_t)proto.n_geoms;
-    }
-    if (nextGeom != desc->n_geoms) { return fail(PATHED_E_INVALID, "prototypes must name consecutive, non-empty geom ranges that end the geom array"); }
-    layout->worldTris = firstProtoGeom < desc->n_geoms ? desc->geoms[firstProtoGeom].first : (int)desc->n_triangles;
-    uint64_t virtualTris = (uint64_t)layout->worldTris;
-    layout->inverses.resize((size_t)12 * in->n_instances);
-    for (uint32_t k = 0; k < in->n_instances; k++) {
-        const PathedInstance &instance = in->instances[k];
-        if (instance.prototype < 0 || (uint32_t)instance.prototype >= in->n_prototypes) { return fail(PATHED_E_INVALID, "instance prototype index out of range"); }
-        for (int i = 0; i < 12; i++) { if (!(instance.transform[i] - instance.transform[i] == 0.f)) { return fail(PATHED_E_INVALID, "instance transform is not finite"); } }
-        if (!instanceInverse(instance.transform, &layout->inverses[(size_t)12 * k])) { return fail(PATHED_E_INVALID, "instance transform is not invertible"); }
-        layout->bases.push_back((int)virtualTris);
-        virtualTris += (uint64_t)layout->protoCount[(size_t)instance.prototype];
-        if (virtualTris >= (1ull << 31)) { return fail(PATHED_E_INVALID, "a scene with instances: the virtual primitive ids (world triangles + every placement's) must stay below the limit of 2^31"); }
-    }
-    layout->bases.push_back((int)virtualTris);
-    return PATHED_OK;
-}
-
-// The two-level tree in one node array and one leaf-triangle array (trace.h): the top tree over the world triangles and the
-// placements' world boxes, then one object-space tree per prototype, refs and firsts made absolute.
-static FlatBvh buildInstancedBvh(const PathedSceneDesc *desc, const PathedInstanceDesc *in, const InstancedLayout &layout, int buildThreads,
-                                 std::vector<float4> *records, int *maxStack, std::vector<float4> *protoBoxes, int *topNodes, int *topDepth)
-{
-    const size_t nProto = layout.protoFirst.size();
-    std::vector<FlatBvh> trees(nProto);
-    std::vector<float> protoLo(3 * nProto), protoHi(3 * nProto);
-    int deepest = 0;
-    for (size_t p = 0; p < nProto; p++) {
-        const int first = layout.protoFirst[p], count = layout.protoCount[p];
-        trees[p] = buildBvh(desc->positions, desc->indices + (size_t)3 * first, (uint32_t)count, nullptr, 0, buildThreads);
-        deepest = std::max(deepest, trees[p].maxDepth);
-        bvh_detail::Box box;
-        box.reset();
-        for (int i = 0; i < 3 * count; i++) {
-            const float *corner = desc->positions + (size_t)3 * desc->indices[(size_t)3 * first + i];
-            box.grow(corner, corner);
-        }
-        bvh_detail::padBox(box, &protoLo[3 * p], &protoHi[3 * p]);   // what the prototype's root children span at most
-    }
-    // a placement's world box: the corners of the padded prototype box through the flatten routine, padded once more for the
-    // roundings of the object-space ray (the builder pads the node's copy a third time, as it pads every child box)
-    std::vector<float> boxes((size_t)6 * in->n_instances);
-    for (uint32_t k = 0; k < in->n_instances; k++) {
-        const PathedInstance &instance = in->instances[k];
-        const float *lo = &protoLo[(size_t)3 * instance.prototype], *hi = &protoHi[(size_t)3 * instance.prototype];
-        bvh_detail::Box box;
-        box.reset();
-        for (int corner = 0; corner < 8; corner++) {
-            const V3 world = flattenPoint(instance.transform, v3((corner & 1) ? hi[0] : lo[0], (corner & 2) ? hi[1] : lo[1], (corner & 4) ? hi[2] : lo[2]));
-            const float point[3] = { world.x, world.y, world.z };
-            box.grow(point, point);
-        }
-        for (int a = 0; a < 3; a++) {
-            const float pad = 1e-5f * std::max(1.f, std::max(std::fabs(box.lo[a]), std::fabs(box.hi[a]))) + 1e-5f * (box.hi[a] - box.lo[a]);
-            boxes[(size_t)6 * k + a] = box.lo[a] - pad;
-            boxes[(size_t)6 * k + 3 + a] = box.hi[a] + pad;
-        }
-    }
-    FlatBvh out = buildBvh(desc->positions, desc->indices, (uint32_t)layout.worldTris, boxes.data(), in->n_instances, buildThreads, 0, true);
-    // the placements' one-primitive leaves (count 0, first = index + 1) become instance leaves
-    for (int n = 0; n < out.nodeCount; n++) {
-        for (int k = 0; k < 4; k++) {
-            int ref;
-            std::memcpy(&ref, &out.nodes[(size_t)kNodeFloats * n + 24 + k], 4);
-            if (ref == kEmptyChildRef || ref >= 0) { continue; }
-            const int payload = -ref - 1;
-            if ((payload & 7) != 0) { continue; }
-            bvh_detail::putInt(&out.nodes[(size_t)kNodeFloats * n + 24 + k], -(kInstanceLeafBit | ((payload >> 3) - 1)) - 1);
-        }
-    }
-    if (out.nodeCount == 0) {
-        // nothing in the world: an empty root, so that node 0 is never a prototype's
-        out.nodes.assign((size_t)kNodeFloats, 0.f);
-        for (int k = 0; k < 4; k++) { bvh_detail::putInt(&out.nodes[24 + k], kEmptyChildRef); }
-        out.nodeCount = 1;
-        out.maxDepth = 1;
-    }
-    // what a later move of the placements needs (pathed_hip_scene_set_instance_transforms): the top tree's extent in the node
-    // array, its levels, and the padded prototype boxes the world boxes above came from
-    *topNodes = out.nodeCount;
-    *topDepth = out.maxDepth;
-    protoBoxes->resize(2 * nProto);
-    for (size_t p = 0; p < nProto; p++) {
-        (*protoBoxes)[2 * p] = make_float4(protoLo[3 * p], protoLo[3 * p + 1], protoLo[3 * p + 2], 0.f);
-        (*protoBoxes)[2 * p + 1] = make_float4(protoHi[3 * p], protoHi[3 * p + 1], protoHi[3 * p + 2], 0.f);
-    }
-    *maxStack = (3 * out.maxDepth + 1) + (3 * deepest + 1) + 1;
-    out.maxDepth += deepest;
-    std::vector<int> protoRoot(nProto);
-    int triOffset = layout.worldTris;
-    for (size_t p = 0; p < nProto; p++) {
-        const int nodeOffset = out.nodeCount;
-        protoRoot[p] = nodeOffset;
-        const size_t nodeBase = out.nodes.size();
-        out.nodes.insert(out.nodes.end(), trees[p].nodes.begin(), trees[p].nodes.end());
-        for (int n = 0; n < trees[p].nodeCount; n++) {
-            for (int k = 0; k < 4; k++) {
-                float *slot = &out.nodes[nodeBase + (size_t)kNodeFloats * n + 24 + k];
-                int ref;
-                std::memcpy(&ref, slot, 4);
-                if (ref == kEmptyChildRef) { continue; }
-                if (ref >= 0) { bvh_detail::putInt(slot, ref + nodeOffset); continue; }
-                const int payload = -ref - 1;
-                bvh_detail::putInt(slot, -((((payload >> 3) + triOffset) << 3) | (payload & 7)) - 1);
-            }
-        }
-        out.leafTris.insert(out.leafTris.end(), trees[p].leafTris.begin(), trees[p].leafTris.end());   // (prim = the index inside the prototype)
-        out.nodeCount += trees[p].nodeCount;
-        triOffset += layout.protoCount[p];
-    }
-    records->resize((size_t)kInstanceQuads * in->n_instances);
-    for (uint32_t k = 0; k < in->n_instances; k++) {
-        const float *m = in->instances[k].transform, *inverse = &layout.inverses[(size_t)12 * k];
-        const int prototype = in->instances[k].prototype;
-        float4 *record = records->data() + (size_t)kInstanceQuads * k;
-        for (int row = 0; row < 3; row++) {
-            record[row] = make_float4(m[4 * row], m[4 * row + 1], m[4 * row + 2], m[4 * row + 3]);
-            record[3 + row] = make_float4(inverse[4 * row], inverse[4 * row + 1], inverse[4 * row + 2], inverse[4 * row + 3]);
-        }
-        const int ids[4] = { layout.bases[k], prototype, protoRoot[(size_t)prototype], layout.protoFirst[(size_t)prototype] };
-        std::memcpy(&record[6], ids, sizeof ids);
-    }
-    return out;
-}
-
 // ---- scene creation.  createScene, at the end, is the sequence of the stages below; the arithmetic
-// that needs no device is scene_tables.h.  A stage that fails has called fail() and returns its code: the scene's one owner
-// in createScene frees whatever had been allocated by then.
+// that needs no device is scene_tables.h and, for a scene with instances, instances.h (planInstances, buildInstancedBvh).
+// A stage that fails has called fail() and returns its code: the scene's one owner in createScene frees whatever had been
+// allocated by then.
 
 static int deviceFail(hipError_t status, const char *what)
 {
@@ -1906,7 +1761,7 @@ static int buildTreeOnHost(PathedScene *scene, const PathedSceneDesc *desc, cons
         }
     }
     scene->spheresInTree = !sphereBounds.empty();
-    std::vector<float4> instanceRecords, protoBoxes;
+    std::vector<float> instanceRecords, protoBoxes;
     if (instanceDesc) {
         scene->bvh = buildInstancedBvh(desc, instanceDesc, instancedLayout, scene->options.build_threads, &instanceRecords, &scene->instancedMaxStack,
                                        &protoBoxes, &scene->topNodes, &scene->topDepth);
@@ -1919,9 +1774,9 @@ static int buildTreeOnHost(PathedScene *scene, const PathedSceneDesc *desc, cons
     if ((status = scene->nodes.upload(asQuads(scene->bvh.nodes))) != hipSuccess) { return deviceFail(status, "upload nodes"); }
     if ((status = scene->leafTris.upload(asQuads(scene->bvh.leafTris))) != hipSuccess) { return deviceFail(status, "upload triangles"); }
     if (instanceDesc) {
-        if ((status = scene->instanceRecords.upload(instanceRecords)) != hipSuccess) { return deviceFail(status, "upload instance records"); }
+        if ((status = scene->instanceRecords.upload(asQuads(instanceRecords))) != hipSuccess) { return deviceFail(status, "upload instance records"); }
         if ((status = scene->instanceBases.upload(instancedLayout.bases)) != hipSuccess) { return deviceFail(status, "upload instance bases"); }
-        if ((status = scene->protoBoxes.upload(protoBoxes)) != hipSuccess) { return deviceFail(status, "upload prototype boxes"); }
+        if ((status = scene->protoBoxes.upload(asQuads(protoBoxes))) != hipSuccess) { return deviceFail(status, "upload prototype boxes"); }
         scene->instanceSet.records = scene->instanceRecords.ptr;
         scene->instanceSet.bases = scene->instanceBases.ptr;
         scene->instanceSet.nInstances = (int)instanceDesc->n_instances;
@@ -2220,7 +2075,8 @@ static int createScene(const PathedSceneDesc *desc, const PathedSceneOptions *op
     PathedSceneOptions options;
     if ((code = resolveOptions(optionsIn, &options)) != PATHED_OK) { return code; }
     InstancedLayout instancedLayout;
-    if (instanceDesc && (code = planInstances(desc, options, instanceDesc, &instancedLayout)) != PATHED_OK) { return code; }
+    std::string refusal;
+    if (instanceDesc && (code = planInstances(desc, options, instanceDesc, &instancedLayout, &refusal)) != PATHED_OK) { return fail(code, refusal); }
     int deviceId = 0;
     if ((code = resolveDevice(options, &deviceId)) != PATHED_OK) { return code; }
 
@@ -3861,59 +3717,30 @@ int pathed_hip_scene_refit(PathedScene *scene, const float *positions, const flo
     }
     HIP_TRY(hipMemcpy(scene->soupPositions.ptr, positions, 3 * (size_t)n_vertices * sizeof(float), hipMemcpyHostToDevice));
     if (normals) { HIP_TRY(hipMemcpy(scene->soupNormals.ptr, normals, 3 * (size_t)n_vertices * sizeof(float), hipMemcpyHostToDevice)); }
-    hipEvent_t start = nullptr, stop = nullptr;
-    HIP_TRY(hipEventCreate(&start));
-    hipError_t status = hipEventCreate(&stop);
-    if (status == hipSuccess) { status = hipEventRecord(start, nullptr); }
-    if (status == hipSuccess) {
+    EventTimer timer;
+    const dim3 grid((unsigned)((nNodes + kBlock - 1) / kBlock)), block(kBlock);
+    LevelPasses passes{ scene->refitReady.ptr, (size_t)nNodes, [&](const unsigned char *in, unsigned char *out) {
+        hipLaunchKernelGGL(k_refit_pass, grid, block, 0, nullptr, scene->nodes.ptr, nNodes, scene->leafTris.ptr, scene->soupPositions.ptr,
+                           scene->soupIndices.ptr, scene->spheres.ptr, scene->refitLo.ptr, scene->refitHi.ptr, in, out);
+    } };
+    timer.run([&]() {
         // shading records (corners, normals, uvs) of every primitive, then the tree bottom-up
         hipLaunchKernelGGL(k_build_tri_shade, dim3((unsigned)((8 * nTris + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
                            scene->soupPositions.ptr, scene->soupNormals.ptr, scene->soupUvs.ptr, scene->soupIndices.ptr, scene->soupTriMaterial.ptr,
                            (uint32_t)nTris, scene->triShade.ptr, scene->triCompact.ptr);
-        status = buildLightRecords(scene, scene->device.nLights);   // an emitter that moved is sampled where it is now
-    }
-    if (status == hipSuccess) {
-        status = hipMemsetAsync(scene->refitReady.ptr, 0, 2 * (size_t)nNodes, nullptr);
-    }
-    int passes = 0;
-    unsigned char rootReady = 0;
-    const dim3 grid((unsigned)((nNodes + kBlock - 1) / kBlock)), block(kBlock);
-    auto runPasses = [&](int count) {
-        for (int k = 0; k < count; k++, passes++) {
-            unsigned char *in = scene->refitReady.ptr + (size_t)(passes & 1) * nNodes, *out = scene->refitReady.ptr + (size_t)((passes + 1) & 1) * nNodes;
-            hipLaunchKernelGGL(k_refit_pass, grid, block, 0, nullptr, scene->nodes.ptr, nNodes, scene->leafTris.ptr, scene->soupPositions.ptr,
-                               scene->soupIndices.ptr, scene->spheres.ptr, scene->refitLo.ptr, scene->refitHi.ptr, in, out);
-        }
-    };
-    // one pass per 4-wide level, back to back (no look at the flags in between: a host round trip costs more than a pass)
-    if (status == hipSuccess) { runPasses(scene->bvh.maxDepth > 0 ? scene->bvh.maxDepth + 1 : 16); status = hipGetLastError(); }
-    float ms = 0.f;
-    if (status == hipSuccess) { status = hipEventRecord(stop, nullptr); }
-    if (status == hipSuccess) { status = hipEventSynchronize(stop); }
-    if (status == hipSuccess) { status = hipEventElapsedTime(&ms, start, stop); }
-    if (status == hipSuccess) { status = hipMemcpy(&rootReady, scene->refitReady.ptr + (size_t)(passes & 1) * nNodes, 1, hipMemcpyDeviceToHost); }
-    while (status == hipSuccess && !rootReady && passes < 4096) {
-        // (a tree deeper than its recorded depth: keep going, four passes per look at the root's flag; their device time
-        // joins device_ms)
-        float extra = 0.f;
-        status = hipEventRecord(start, nullptr);
-        if (status == hipSuccess) { runPasses(4); status = hipGetLastError(); }
-        if (status == hipSuccess) { status = hipEventRecord(stop, nullptr); }
-        if (status == hipSuccess) { status = hipEventSynchronize(stop); }
-        if (status == hipSuccess) { status = hipEventElapsedTime(&extra, start, stop); }
-        ms += extra;
-        if (status == hipSuccess) { status = hipMemcpy(&rootReady, scene->refitReady.ptr + (size_t)(passes & 1) * nNodes, 1, hipMemcpyDeviceToHost); }
-    }
-    (void)hipEventDestroy(start);
-    if (stop) { (void)hipEventDestroy(stop); }
-    if (status != hipSuccess) { return fail(PATHED_E_DEVICE, std::string("refit: ") + hipGetErrorString(status)); }
+        if (!timer.keep(buildLightRecords(scene, scene->device.nLights))) { return; }   // an emitter that moved is sampled where it is now
+        if (!timer.keep(hipMemsetAsync(scene->refitReady.ptr, 0, 2 * (size_t)nNodes, nullptr))) { return; }
+        passes.launchLevels(scene->bvh.maxDepth);
+    });
+    const bool rootReady = passes.reachRoot(timer);
+    if (!timer.ok()) { return fail(PATHED_E_DEVICE, std::string("refit: ") + hipGetErrorString(timer.status)); }
     if (!rootReady) { return fail(PATHED_E_DEVICE, "refit: the root was never reached (a cycle in the tree?)"); }
     scene->bvhOnHost = false;   // exports download the refitted tree
-    if (device_ms) { *device_ms = ms; }
+    if (device_ms) { *device_ms = timer.ms; }
     return PATHED_OK;
 }
 
-// ---- moving placements (include/pathed_hip.h; kernels.h: k_instance_records, k_refit_top_pass)
+// ---- moving placements (include/pathed_hip.h; instance_kernels.h: k_instance_records, k_refit_top_pass)
 // The one compute path of both entry points: `deviceTransforms` holds 12 floats per placement on the scene's device.
 static int setInstanceTransforms(PathedScene *scene, const float *deviceTransforms, float *device_ms)
 {
@@ -3933,63 +3760,34 @@ static int setInstanceTransforms(PathedScene *scene, const float *deviceTransfor
     const unsigned int clear[2] = { 0u, 0xFFFFFFFFu };
     unsigned int bad[2] = { 0u, 0u };
     HIP_TRY(hipMemcpy(scene->instanceBad.ptr, clear, sizeof clear, hipMemcpyHostToDevice));
-    hipEvent_t start = nullptr, stop = nullptr;
-    HIP_TRY(hipEventCreate(&start));
-    hipError_t status = hipEventCreate(&stop);
-    float ms = 0.f;
-    // (the events of one timed stretch of launches on the null stream; its device time joins ms)
-    auto timed = [&](auto &&launches) {
-        float part = 0.f;
-        if (status == hipSuccess) { status = hipEventRecord(start, nullptr); }
-        if (status == hipSuccess) { launches(); status = hipGetLastError(); }
-        if (status == hipSuccess) { status = hipEventRecord(stop, nullptr); }
-        if (status == hipSuccess) { status = hipEventSynchronize(stop); }
-        if (status == hipSuccess) { status = hipEventElapsedTime(&part, start, stop); }
-        ms += part;
-    };
-    auto finish = [&]() {
-        (void)hipEventDestroy(start);
-        if (stop) { (void)hipEventDestroy(stop); }
-    };
+    EventTimer timer;
     if (nInstances > 0) {
-        timed([&]() {
+        timer.run([&]() {
             hipLaunchKernelGGL(k_instance_records, dim3((unsigned)((nInstances + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
                                deviceTransforms, nInstances, scene->instanceRecords.ptr, scene->instanceRecordsStaged.ptr, scene->instanceBad.ptr);
         });
-        if (status == hipSuccess) { status = hipMemcpy(bad, scene->instanceBad.ptr, sizeof bad, hipMemcpyDeviceToHost); }
-        if (status != hipSuccess) { finish(); return fail(PATHED_E_DEVICE, std::string("set_instance_transforms: ") + hipGetErrorString(status)); }
+        if (timer.ok()) { timer.keep(hipMemcpy(bad, scene->instanceBad.ptr, sizeof bad, hipMemcpyDeviceToHost)); }
+        if (!timer.ok()) { return fail(PATHED_E_DEVICE, std::string("set_instance_transforms: ") + hipGetErrorString(timer.status)); }
         if (bad[0] != 0u) {
             // (the staged records are simply not adopted: the live records, the tree and the flags are untouched)
-            finish();
             return fail(PATHED_E_INVALID, "instance transform " + std::to_string(bad[1]) + " is not finite or not invertible (" + std::to_string(bad[0])
                         + " of the " + std::to_string(nInstances) + " transforms are refused; the scene keeps its placements)");
         }
-        std::swap(scene->instanceRecords.ptr, scene->instanceRecordsStaged.ptr);
+        scene->instanceRecords.swap(scene->instanceRecordsStaged);
         scene->instanceSet.records = scene->instanceRecords.ptr;
     }
-    if (status == hipSuccess) { status = hipMemset(scene->topReady.ptr, 0, 2 * (size_t)topNodes); }
-    int passes = 0;
-    unsigned char rootReady = 0;
+    timer.keep(hipMemset(scene->topReady.ptr, 0, 2 * (size_t)topNodes));
     const dim3 grid((unsigned)((topNodes + kBlock - 1) / kBlock)), block(kBlock);
-    auto runPasses = [&](int count) {
-        for (int k = 0; k < count; k++, passes++) {
-            unsigned char *in = scene->topReady.ptr + (size_t)(passes & 1) * topNodes, *out = scene->topReady.ptr + (size_t)((passes + 1) & 1) * topNodes;
-            hipLaunchKernelGGL(k_refit_top_pass, grid, block, 0, nullptr, scene->nodes.ptr, topNodes, scene->instanceRecords.ptr, nInstances,
-                               scene->protoBoxes.ptr, (int)(scene->protoBoxes.count / 2), scene->topLo.ptr, scene->topHi.ptr, in, out);
-        }
-    };
-    // one pass per 4-wide level of the top tree, back to back, then the guard of pathed_hip_scene_refit
-    timed([&]() { runPasses(scene->topDepth > 0 ? scene->topDepth + 1 : 16); });
-    if (status == hipSuccess) { status = hipMemcpy(&rootReady, scene->topReady.ptr + (size_t)(passes & 1) * topNodes, 1, hipMemcpyDeviceToHost); }
-    while (status == hipSuccess && !rootReady && passes < 4096) {
-        timed([&]() { runPasses(4); });
-        if (status == hipSuccess) { status = hipMemcpy(&rootReady, scene->topReady.ptr + (size_t)(passes & 1) * topNodes, 1, hipMemcpyDeviceToHost); }
-    }
-    finish();
-    if (status != hipSuccess) { return fail(PATHED_E_DEVICE, std::string("set_instance_transforms: ") + hipGetErrorString(status)); }
+    LevelPasses passes{ scene->topReady.ptr, (size_t)topNodes, [&](const unsigned char *in, unsigned char *out) {
+        hipLaunchKernelGGL(k_refit_top_pass, grid, block, 0, nullptr, scene->nodes.ptr, topNodes, scene->instanceRecords.ptr, nInstances,
+                           scene->protoBoxes.ptr, (int)(scene->protoBoxes.count / 2), scene->topLo.ptr, scene->topHi.ptr, in, out);
+    } };
+    timer.run([&]() { passes.launchLevels(scene->topDepth); });
+    const bool rootReady = passes.reachRoot(timer);
+    if (!timer.ok()) { return fail(PATHED_E_DEVICE, std::string("set_instance_transforms: ") + hipGetErrorString(timer.status)); }
     if (!rootReady) { return fail(PATHED_E_DEVICE, "set_instance_transforms: the top tree's root was never reached (a cycle in the tree?)"); }
     scene->bvhOnHost = false;   // exports download the refitted tree
-    if (device_ms) { *device_ms = ms; }
+    if (device_ms) { *device_ms = timer.ms; }
     return PATHED_OK;
 }
 
@@ -4020,7 +3818,7 @@ int pathed_hip_scene_set_instance_transforms(PathedScene *scene, const float *tr
     return setInstanceTransforms(scene, scene->instanceTransforms.ptr, device_ms);
 }
 
-// ---- rebuilding the top tree (include/pathed_hip.h; lbvh.hip: buildTopBvhOnDevice; kernels.h: k_placement_boxes,
+// ---- rebuilding the top tree (include/pathed_hip.h; lbvh.hip: buildTopBvhOnDevice; instance_kernels.h: k_placement_boxes,
 // k_rebase_prototype_nodes, k_rebase_instance_roots).  Everything new is built beside the live arrays -- node array
 // [new top | prototypes' trees], leaf triangles [world in the new leaf order | prototypes], records with their protoRoot
 // moved -- and adopted at the end by swapping pointers: an error before that leaves the scene untouched.
@@ -4045,67 +3843,46 @@ int pathed_hip_scene_rebuild_top(PathedScene *scene, int32_t builder, float *dev
     if (scene->instanceRecordsStaged.count != scene->instanceRecords.count) { HIP_TRY(scene->instanceRecordsStaged.allocate(scene->instanceRecords.count)); }
     DeviceBuffer<float4> boxes;
     HIP_TRY(boxes.allocate(2 * (size_t)nInstances));
-    hipEvent_t start = nullptr, stop = nullptr;
-    HIP_TRY(hipEventCreate(&start));
-    hipError_t status = hipEventCreate(&stop);
-    float ms = 0.f;
-    auto timed = [&](auto &&launches) {
-        float part = 0.f;
-        if (status == hipSuccess) { status = hipEventRecord(start, nullptr); }
-        if (status == hipSuccess) { launches(); status = hipGetLastError(); }
-        if (status == hipSuccess) { status = hipEventRecord(stop, nullptr); }
-        if (status == hipSuccess) { status = hipEventSynchronize(stop); }
-        if (status == hipSuccess) { status = hipEventElapsedTime(&part, start, stop); }
-        ms += part;
-    };
-    DeviceBvh built;
-    auto giveUp = [&](const std::string &what) {
-        (void)hipEventDestroy(start);
-        if (stop) { (void)hipEventDestroy(stop); }
-        if (built.nodes) { (void)hipFree(built.nodes); }
-        if (built.leafTris) { (void)hipFree(built.leafTris); }
-        return fail(PATHED_E_DEVICE, "rebuild_top: " + what);
-    };
+    EventTimer timer;
+    const auto giveUp = [&](const std::string &what) { return fail(PATHED_E_DEVICE, "rebuild_top: " + what); };
     if (nInstances > 0) {
-        timed([&]() {
+        timer.run([&]() {
             hipLaunchKernelGGL(k_placement_boxes, dim3((unsigned)((nInstances + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
                                scene->instanceRecords.ptr, nInstances, scene->protoBoxes.ptr, (int)(scene->protoBoxes.count / 2), boxes.ptr);
         });
     }
-    if (status != hipSuccess) { return giveUp(hipGetErrorString(status)); }
+    if (!timer.ok()) { return giveUp(hipGetErrorString(timer.status)); }
+    DeviceBvh built;
     std::string message;
-    status = buildTopBvhOnDevice(builder == PATHED_BVH_PLOC_DEVICE ? kDeviceBuilderPloc : kDeviceBuilderLbvh, scene->leafTris.ptr, (uint32_t)worldTris,
-                                 boxes.ptr, (uint32_t)nInstances, protoNodes, protoTris, nullptr, &built, &message);
+    const hipError_t status = buildTopBvhOnDevice(builder == PATHED_BVH_PLOC_DEVICE ? kDeviceBuilderPloc : kDeviceBuilderLbvh, scene->leafTris.ptr, (uint32_t)worldTris,
+                                                  boxes.ptr, (uint32_t)nInstances, protoNodes, protoTris, nullptr, &built, &message);
+    // whatever the builder allocated, finished or not, is freed on every return below unless the scene adopts it
+    DeviceBuffer<float4> newNodes, newLeafTris;
+    newNodes.adopt(built.nodes, built.nodeCapacity * 8);
+    newLeafTris.adopt(built.leafTris, ((size_t)worldTris + protoTris) * 3);
     if (status != hipSuccess) { return giveUp(message.empty() ? hipGetErrorString(status) : message); }
-    ms += built.buildMs;
     const int newTop = built.nodeCount;
     if (newTop <= 0 || (size_t)newTop + protoNodes > built.nodeCapacity) { return giveUp("the builder made a wrong node count"); }
-    timed([&]() {
+    timer.run([&]() {
         if (protoNodes > 0) {
             hipLaunchKernelGGL(k_rebase_prototype_nodes, dim3((unsigned)((8 * protoNodes + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
-                               scene->nodes.ptr, oldTop, oldCount, built.nodes, newTop);
+                               scene->nodes.ptr, oldTop, oldCount, newNodes.ptr, newTop);
         }
         if (nInstances > 0) {
             hipLaunchKernelGGL(k_rebase_instance_roots, dim3((unsigned)(((size_t)kInstanceQuads * nInstances + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
                                scene->instanceRecords.ptr, scene->instanceRecordsStaged.ptr, nInstances, newTop - oldTop);
         }
         if (protoTris > 0) {
-            (void)hipMemcpyAsync(built.leafTris + 3 * (size_t)worldTris, scene->leafTris.ptr + 3 * (size_t)worldTris, protoTris * 3 * sizeof(float4), hipMemcpyDeviceToDevice, nullptr);
+            (void)hipMemcpyAsync(newLeafTris.ptr + 3 * (size_t)worldTris, scene->leafTris.ptr + 3 * (size_t)worldTris, protoTris * 3 * sizeof(float4), hipMemcpyDeviceToDevice, nullptr);
         }
     });
-    if (status == hipSuccess) { status = hipDeviceSynchronize(); }
-    if (status != hipSuccess) { return giveUp(hipGetErrorString(status)); }
-    (void)hipEventDestroy(start);
-    (void)hipEventDestroy(stop);
+    if (timer.ok()) { timer.keep(hipDeviceSynchronize()); }
+    if (!timer.ok()) { return giveUp(hipGetErrorString(timer.status)); }
 
-    // adoption: nothing below can fail
-    scene->nodes.release();
-    scene->nodes.ptr = built.nodes;
-    scene->nodes.count = built.nodeCapacity * 8;
-    scene->leafTris.release();
-    scene->leafTris.ptr = built.leafTris;
-    scene->leafTris.count = ((size_t)worldTris + protoTris) * 3;
-    std::swap(scene->instanceRecords.ptr, scene->instanceRecordsStaged.ptr);
+    // adoption: nothing below can fail (the old arrays go with newNodes / newLeafTris at the end of the call)
+    scene->nodes.swap(newNodes);
+    scene->leafTris.swap(newLeafTris);
+    scene->instanceRecords.swap(scene->instanceRecordsStaged);
     scene->instanceSet.records = scene->instanceRecords.ptr;
     scene->topNodes = newTop;
     scene->topDepth = built.maxDepth;
@@ -4127,7 +3904,7 @@ int pathed_hip_scene_rebuild_top(PathedScene *scene, int32_t builder, float *dev
     scene->topLo.release();
     scene->topHi.release();
     scene->topReady.release();
-    if (device_ms) { *device_ms = ms; }
+    if (device_ms) { *device_ms = timer.ms + built.buildMs; }
     return PATHED_OK;
 }
 

@@ -38,6 +38,7 @@
 #pragma once
 
 #include "device_scene.h"
+#include "instances.h"
 
 namespace pathed {
 
@@ -558,7 +559,7 @@ __device__ inline bool traverse(
 // The flatten routine, fp32, one rounding per operation, no fused multiply-add (the host flattens with the same statements):
 //   point   p' = ((m[0] x + m[1] y) + m[2] z) + m[3], ... rows of the 3 x 4 transform m
 //   normal  n' = ((i[0] x + i[4] y) + i[8] z), ...    columns of the inverse's 3 x 3: the inverse transpose, not renormalised
-// and the inverse i is formed in double from the floats of m by cofactors (instanceInverse) and rounded once to float.
+// and the inverse i is formed in double from the floats of m by cofactors (instances.h: instanceInverse) and rounded once to float.
 // A ray enters a prototype as (i o, i3x3 d): the direction is NOT renormalised, so t is the world t and best / tfar carry over.
 struct DInstanceSet {
     const float4 *records;   // kInstanceQuads per instance: m rows (3), inverse rows (3), (base, prototype, root node, first shading record) as ints
@@ -566,44 +567,10 @@ struct DInstanceSet {
     int nInstances;
     int worldTris;           // T0
 };
-static const int kInstanceQuads = 7;
-static const int kInstanceLeafBit = 1 << 30;
-static const int kInstanceSentinel = 0x7FFFFFFF;
-
-__host__ __device__ inline V3 flattenPoint(const float *m, V3 p)
-{
-    return v3(((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3],
-              ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7],
-              ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]);
-}
-__host__ __device__ inline V3 flattenDirection(const float *m, V3 d)
-{
-    return v3((m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z, (m[8] * d.x + m[9] * d.y) + m[10] * d.z);
-}
-__host__ __device__ inline V3 flattenNormal(const float *inverse, V3 n)
-{
-    return v3((inverse[0] * n.x + inverse[4] * n.y) + inverse[8] * n.z,
-              (inverse[1] * n.x + inverse[5] * n.y) + inverse[9] * n.z,
-              (inverse[2] * n.x + inverse[6] * n.y) + inverse[10] * n.z);
-}
-// the inverse of the affine 3 x 4 transform m, in double, rounded once; false when m is singular or not finite
-inline bool instanceInverse(const float *m, float *inverse)
-{
-    const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], k = m[10];
-    const double c00 = e * k - f * h, c01 = c * h - b * k, c02 = b * f - c * e;
-    const double c10 = f * g - d * k, c11 = a * k - c * g, c12 = c * d - a * f;
-    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
-    const double det = (a * c00 + b * c10) + c * c20;
-    if (!(det != 0.0) || !(det - det == 0.0)) { return false; }
-    const double r[9] = { c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det };
-    const double tx = m[3], ty = m[7], tz = m[11];
-    for (int row = 0; row < 3; row++) {
-        for (int col = 0; col < 3; col++) { inverse[4 * row + col] = (float)r[3 * row + col]; }
-        inverse[4 * row + 3] = (float)(-((r[3 * row] * tx + r[3 * row + 1] * ty) + r[3 * row + 2] * tz));
-    }
-    for (int i = 0; i < 12; i++) { if (!(inverse[i] - inverse[i] == 0.f)) { return false; } }
-    return true;
-}
+// kInstanceQuads, kInstanceLeafBit, kInstanceSentinel, the flatten routine on float arrays and instanceInverse: instances.h
+__host__ __device__ inline V3 flattenPoint(const float *m, V3 p) { float out[3]; flattenPoint(m, p.x, p.y, p.z, out); return v3(out[0], out[1], out[2]); }
+__host__ __device__ inline V3 flattenDirection(const float *m, V3 d) { float out[3]; flattenDirection(m, d.x, d.y, d.z, out); return v3(out[0], out[1], out[2]); }
+__host__ __device__ inline V3 flattenNormal(const float *inverse, V3 n) { float out[3]; flattenNormal(inverse, n.x, n.y, n.z, out); return v3(out[0], out[1], out[2]); }
 
 // leafStep for the two-level tree: the leaf's stored ids plus `base` are the virtual ids the acceptance rule compares
 template <bool COUNT, int ROWS, int STRIDE>

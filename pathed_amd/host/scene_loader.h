@@ -99,8 +99,9 @@ FlatScene loadScene(
 PathedMaterial makeLambertian(const float diffuse[3], const float emit[3]);
 
 // The flatten routine of include/pathed_hip.h (PathedInstanceDesc), fp32, one rounding per operation, in the operation order
-// the device applies to a prototype's shading record (pathed_amd/csrc/trace.h) and pathed_amd.flatten_instances applies in
-// numpy: transform / inverse are row-major 3 x 4; instanceInverse forms the inverse in double by cofactors and rounds once.
+// the device applies to a prototype's shading record (pathed_amd/csrc/instances.h) and pathed_amd.flatten_instances applies in
+// numpy: transform / inverse are row-major 3 x 4; instanceInverse forms the inverse in double by cofactors and rounds once,
+// statement for statement as the library's own does (instances.h: instanceInverse; this side of the C ABI sees only pathed_hip.h).
 void flattenInstancePoint(const float *transform, const float *point, float *out);
 void flattenInstanceNormal(const float *inverse, const float *normal, float *out);
 bool instanceInverse(const float *transform, float *inverse);

@@ -22,7 +22,7 @@ def _f32(value):
 
 def instance_inverse(transform):
     """The inverse of a row-major 3 x 4 transform: cofactors in float64 from the float32 entries, rounded once to float32
-    (pathed_amd/csrc/trace.h: instanceInverse, the same operations in the same order)."""
+    (pathed_amd/csrc/instances.h: instanceInverse, the same operations in the same order)."""
     m = _f32(transform).reshape(12).astype(np.float64)
     a, b, c, tx, d, e, f, ty, g, h, k, tz = (m[i] for i in range(12))
     c00, c01, c02 = e * k - f * h, c * h - b * k, b * f - c * e
@@ -63,7 +63,7 @@ def prototype_box(positions):
 
 
 def placement_box(transform, proto_lo, proto_hi):
-    """The world box of a placement as scene creation and k_refit_top_pass state it, float32, one rounding per operation: the
+    """The world box of a placement as pathed_amd/csrc/instances.h states it (placementBox), float32, one rounding per operation: the
     eight corners of the prototype's padded box (prototype_box) through the flatten routine, min / max, then a pad of
     1e-5 max(1, |lo|, |hi|) + 1e-5 (hi - lo) per axis for the roundings of the object-space ray.  The node that holds the
     placement stores pad_box of this box, as it does of every child."""

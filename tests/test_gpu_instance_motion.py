@@ -1,5 +1,5 @@
 """Moving placements (include/pathed_hip.h: pathed_hip_scene_set_instance_transforms[_device]; DESIGN.md section 4.6d;
-kernels.h: k_instance_records, k_refit_top_pass).  The yardstick throughout is a scene CREATED with the same placements: a
+instance_kernels.h: k_instance_records, k_refit_top_pass).  The yardstick throughout is a scene CREATED with the same placements: a
 moved scene answers with its bits.
 
 1. moved equals fresh   traces (closest and any hit), moments at bounces 0..3, and back again without residue

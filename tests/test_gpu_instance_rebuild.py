@@ -1,5 +1,5 @@
 """Rebuilding the top tree of an instanced scene on the device (include/pathed_hip.h: pathed_hip_scene_rebuild_top; DESIGN.md
-section 4.6d; lbvh.hip: buildTopBvhOnDevice; kernels.h: k_placement_boxes, k_rebase_prototype_nodes, k_rebase_instance_roots).
+section 4.6d; lbvh.hip: buildTopBvhOnDevice; instance_kernels.h: k_placement_boxes, k_rebase_prototype_nodes, k_rebase_instance_roots).
 The yardstick throughout is a scene CREATED with the same placements: hits do not depend on the tree (DESIGN.md "Intersector
 specification"), so a rebuilt scene answers with the fresh scene's bits although its top tree is another one.  Every case runs
 for both device builders.

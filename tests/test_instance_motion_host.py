@@ -2,10 +2,11 @@
 needs no GPU:
 
 1. the three entry points are declared, bound and exported
-2. pathed_amd.instances.placement_box / prototype_box / pad_box are, bit for bit, the boxes scene creation hands the builder
-   -- stated through a small host program over the builder's own Box and padBox (bvh_build.h) with the library's flags
+2. pathed_amd.instances.placement_box / prototype_box / pad_box are, bit for bit, the boxes scene creation hands the builder,
+   and instance_inverse the inverse it stores -- through a small host program that calls the library's own placementBox and
+   instanceInverse (instances.h) and the builder's Box and padBox (bvh_build.h) with the library's flags
 3. InstanceSet.set_transforms keeps the set, and with it flatten_instances, in step
-4. k_instance_records and k_refit_top_pass: compile-only, no scratch, the registers written down on the day, names the
+4. k_instance_records, k_refit_top_pass and k_placement_boxes: compile-only, no scratch, the registers written down on the day, names the
    symbol counts of test_kernel_resources.py do not see
 """
 import ctypes as C
@@ -49,14 +50,14 @@ def test_the_entry_points_are_declared_bound_and_exported():
 # ------------------------------------------------------------------------------------------------------------- 2. box rule
 
 BOX_PROGRAM = r"""
-#include <cmath>
 #include <cstdio>
 #include <vector>
-#include "bvh_build.h"
+#include "instances.h"
 using namespace pathed;
 using namespace pathed::bvh_detail;
 // stdin: int32 nPoints, nPoints * 3 floats (a prototype's corners), int32 nTransforms, nTransforms * 12 floats
-// stdout: the prototype's padded box (6 floats), then per transform the placement's world box and the node's copy (12 floats)
+// stdout: the prototype's padded box (6 floats), then per transform the placement's world box and the node's copy (12 floats),
+// whether instanceInverse accepts the transform (one float, 1 or 0) and the inverse it wrote (12 floats)
 int main()
 {
     int nPoints = 0, nTransforms = 0;
@@ -75,25 +76,18 @@ int main()
     fwrite(hi, 4, 3, stdout);
     for (int k = 0; k < nTransforms; k++) {
         const float *m = &transforms[(size_t)12 * k];
-        Box box;
-        box.reset();
-        for (int corner = 0; corner < 8; corner++) {
-            const float x = (corner & 1) ? hi[0] : lo[0], y = (corner & 2) ? hi[1] : lo[1], z = (corner & 4) ? hi[2] : lo[2];
-            const float point[3] = { ((m[0] * x + m[1] * y) + m[2] * z) + m[3], ((m[4] * x + m[5] * y) + m[6] * z) + m[7], ((m[8] * x + m[9] * y) + m[10] * z) + m[11] };
-            box.grow(point, point);
-        }
         Box placed;
-        for (int a = 0; a < 3; a++) {
-            const float pad = 1e-5f * std::max(1.f, std::max(std::fabs(box.lo[a]), std::fabs(box.hi[a]))) + 1e-5f * (box.hi[a] - box.lo[a]);
-            placed.lo[a] = box.lo[a] - pad;
-            placed.hi[a] = box.hi[a] + pad;
-        }
+        placementBox(m, lo, hi, placed.lo, placed.hi);   // the statement the library and its kernels run
         float nodeLo[3], nodeHi[3];
         padBox(placed, nodeLo, nodeHi);
         fwrite(placed.lo, 4, 3, stdout);
         fwrite(placed.hi, 4, 3, stdout);
         fwrite(nodeLo, 4, 3, stdout);
         fwrite(nodeHi, 4, 3, stdout);
+        float inverse[12] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+        const float accepted = instanceInverse(m, inverse) ? 1.f : 0.f;
+        fwrite(&accepted, 4, 1, stdout);
+        fwrite(inverse, 4, 12, stdout);
     }
     return 0;
 }
@@ -120,7 +114,7 @@ def test_the_numpy_box_rule_is_the_builders(tmp_path):
     source.write_text(BOX_PROGRAM)
     program = tmp_path / "box_rule"
     built = subprocess.run([compiler, "-std=c++17", "-O2", "-ffp-contract=off", "-march=x86-64-v3", "-iquote", os.path.join(ROOT, "pathed_amd", "csrc"),
-                            str(source), "-o", str(program), "-lpthread"], capture_output=True, text=True, timeout=300)
+                            "-I" + os.path.join(ROOT, "include"), str(source), "-o", str(program), "-lpthread"], capture_output=True, text=True, timeout=300)
     assert built.returncode == 0, built.stderr[-2000:]
     transforms = box_rule_transforms()
     for centre, radius in (((3.0, 2.0, 1.0), 1.0), ((-3.0, 1.0, 2.0), 0.7), ((0.0, 0.0, 0.0), 1.0), ((500.0, -0.25, 1e-3), 0.01)):
@@ -129,16 +123,24 @@ def test_the_numpy_box_rule_is_the_builders(tmp_path):
         result = subprocess.run([str(program)], input=payload, capture_output=True, timeout=60)
         assert result.returncode == 0
         words = np.frombuffer(result.stdout, dtype=np.float32)
-        assert len(words) == 6 + 12 * len(transforms)
+        assert len(words) == 6 + 25 * len(transforms)
         proto_lo, proto_hi = I.prototype_box(points)
         assert np.array_equal(bits(proto_lo), bits(words[0:3])) and np.array_equal(bits(proto_hi), bits(words[3:6]))
-        rows = words[6:].reshape(len(transforms), 12)
+        rows = words[6:].reshape(len(transforms), 25)
         for transform, row in zip(transforms, rows):
             lo, hi = I.placement_box(transform, proto_lo, proto_hi)
             assert np.array_equal(bits(lo), bits(row[0:3])) and np.array_equal(bits(hi), bits(row[3:6])), transform
             node_lo, node_hi = I.pad_box(lo, hi)
             assert np.array_equal(bits(node_lo), bits(row[6:9])) and np.array_equal(bits(node_hi), bits(row[9:12])), transform
             assert np.all(node_lo <= lo) and np.all(node_hi >= hi)
+            # the inverse: numpy's is the library's bit for bit, and they refuse the same transforms
+            try:
+                inverse = I.instance_inverse(transform)
+            except ValueError:
+                inverse = None
+            assert (inverse is not None) == (row[12] == 1.0), transform
+            if inverse is not None:
+                assert np.array_equal(bits(inverse), bits(row[13:25])), transform
 
 
 # ------------------------------------------------------------------------------------------------------- 3. the Python set
@@ -176,6 +178,7 @@ void probe_launch(const float *t, int n, const float4 *live, float4 *staged, uns
 {
     hipLaunchKernelGGL(k_instance_records, dim3(1), dim3(kBlock), 0, nullptr, t, n, live, staged, bad);
     hipLaunchKernelGGL(k_refit_top_pass, dim3(1), dim3(kBlock), 0, nullptr, nodes, topNodes, live, n, boxes, 1, lo, hi, in, out);
+    hipLaunchKernelGGL(k_placement_boxes, dim3(1), dim3(kBlock), 0, nullptr, live, n, boxes, 1, lo);
 }
 }
 """
@@ -183,6 +186,7 @@ void probe_launch(const float *t, int n, const float4 *live, float4 *staged, uns
 # what hipcc (ROCm 7, gfx950, the library's flags) reported on the day the kernels were written: see DESIGN.md section 4.6d
 RECORDS_VGPRS, RECORDS_WAVES = 61, 8      # the double-precision cofactors and nine quotients
 TOP_PASS_VGPRS, TOP_PASS_WAVES = 73, 6    # 24 box words, four children's records and corners in flight
+BOXES_VGPRS, BOXES_WAVES = 39, 8          # one record's rows, one prototype box, the corners in flight
 
 
 def test_the_new_kernels_and_their_budgets(tmp_path):
@@ -209,11 +213,12 @@ def test_the_new_kernels_and_their_budgets(tmp_path):
                 usage[name][key.split(" ")[0]] = int(value.group(1))
     records = {k: v for k, v in usage.items() if "18k_instance_records" in k}
     top_pass = {k: v for k, v in usage.items() if "16k_refit_top_pass" in k}
-    assert len(records) == 1 and len(top_pass) == 1, sorted(usage)
-    for kernel_name in list(records) + list(top_pass):
+    boxes = {k: v for k, v in usage.items() if "17k_placement_boxes" in k}
+    assert len(records) == 1 and len(top_pass) == 1 and len(boxes) == 1, sorted(usage)
+    for kernel_name in list(records) + list(top_pass) + list(boxes):
         assert not any(re.search(pattern, kernel_name) for pattern in EXISTING_PATTERNS), kernel_name
-    print("k_instance_records %s, k_refit_top_pass %s" % (list(records.values())[0], list(top_pass.values())[0]))
-    for found, cap, waves in ((records, RECORDS_VGPRS, RECORDS_WAVES), (top_pass, TOP_PASS_VGPRS, TOP_PASS_WAVES)):
+    print("k_instance_records %s, k_refit_top_pass %s, k_placement_boxes %s" % (list(records.values())[0], list(top_pass.values())[0], list(boxes.values())[0]))
+    for found, cap, waves in ((records, RECORDS_VGPRS, RECORDS_WAVES), (top_pass, TOP_PASS_VGPRS, TOP_PASS_WAVES), (boxes, BOXES_VGPRS, BOXES_WAVES)):
         value = list(found.values())[0]
         assert value["ScratchSize"] == 0 and value["VGPRs"] <= cap and value["Occupancy"] >= waves, value
 
