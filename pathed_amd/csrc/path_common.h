@@ -216,9 +216,11 @@ __device__ __forceinline__ bool pathArrive(const RenderParams &p, const DScene &
 // The vertex at `isect` (makeIsect of the hit of (path.o, path.d)) of a path that pathArrive did not finish.  Returns true
 // when the sample is finished here (*color is its value); otherwise path.o / path.d hold the next ray and *shadowOut the
 // vertex's occlusion query, if any.
-template <typename TRAITS, bool PROBES = false, typename MATERIALS>
+// KEYED (k_path_small_single): the vertex's numbers come from keyRow, the filled row of (path.random.k1, this vertex)
+// (shading.h: fillKeyRow) -- Rng::next()'s bits with the inner mixer taken from the row.
+template <typename TRAITS, bool PROBES = false, bool KEYED = false, typename MATERIALS>
 __device__ __forceinline__ bool pathDepart(const RenderParams &p, const DScene &scene, const MATERIALS &materials, PathRegisters &path,
-                                           Isect &isect, ShadowRequest *shadowOut, Rgb *color)
+                                           Isect &isect, ShadowRequest *shadowOut, Rgb *color, const uint32_t *keyRow = nullptr)
 {
     ShadowRequest shadow;
     shadow.push = false;
@@ -248,7 +250,16 @@ __device__ __forceinline__ bool pathDepart(const RenderParams &p, const DScene &
         prepareLobes<TRAITS>(material, isect);
 
         path.random.dimension = vertexBase(vertex);
-        const BSDFSample bsdfSample = materialSample<TRAITS>(material, isect, path.random);
+        const auto sampleBsdf = [&]() -> BSDFSample {
+            if constexpr (KEYED) {
+                RowRng rowRandom;
+                rowRandom.k0 = path.random.k0; rowRandom.row = keyRow; rowRandom.dimension = 0u;
+                return materialSample<TRAITS>(material, isect, rowRandom);
+            } else {
+                return materialSample<TRAITS>(material, isect, path.random);
+            }
+        };
+        const BSDFSample bsdfSample = sampleBsdf();
 
         const bool counts = checkCounts(p.startBounce, p.lastBounce, vertex);
         const bool emissive = !isBlack(matEmit(material));
@@ -259,7 +270,13 @@ __device__ __forceinline__ bool pathDepart(const RenderParams &p, const DScene &
         if (PROBES) { SHADE_REGION(7, wantDirect); }   // light sampling
         if (wantDirect) {
             path.random.dimension = vertexBase(vertex) + 3;
-            lightTerm = sampleLightsTerm<false, TRAITS>(scene, materials, isect, material, path.random, &shadow);
+            if constexpr (KEYED) {
+                RowRng rowRandom;
+                rowRandom.k0 = path.random.k0; rowRandom.row = keyRow; rowRandom.dimension = 3u;
+                lightTerm = sampleLightsTerm<false, TRAITS>(scene, materials, isect, material, rowRandom, &shadow);
+            } else {
+                lightTerm = sampleLightsTerm<false, TRAITS>(scene, materials, isect, material, path.random, &shadow);
+            }
         }
 
         // see k_shade: a vertex with nothing pending whose BSDF sample has exactly black throughput ends the sample
@@ -341,6 +358,24 @@ __device__ __forceinline__ bool putSampleAway(const RenderParams &p, bool unitIs
         }
     }
     return unitDone;
+}
+
+// The same where every unit is ONE sample (k_path_small_single): the end of a sample is the end of its unit, whose partial sum
+// is putSampleAway's 0.f + colour per channel (a -0 becomes +0), zeros for a dropped sample.  `index`: the unit's partialIndex.
+__device__ __forceinline__ void putUnitAway(const RenderParams &p, bool done, Rgb color, unsigned int index)
+{
+    if (done) {
+        float4 partial = make_float4(0.f, 0.f, 0.f, 0.f);
+        const bool finite = isfinite(color.r) && isfinite(color.g) && isfinite(color.b);
+        if (finite) {
+            partial.x += color.r;
+            partial.y += color.g;
+            partial.z += color.b;
+        } else {
+            atomicAdd(&p.stats[kStatDropped], 1ull);
+        }
+        p.state.chunkBuf[(size_t)index] = partial;
+    }
 }
 
 // ... then the unit's next sample (startNext), or the lane takes the next unit; a lane that gets none retires (alive).

@@ -2411,6 +2411,9 @@ static int renderPassFused(PathedScene *scene, const Pass &pass)
                 } else if (kSmallPrunes<decltype(COUNT)::value, TRAITS>) {
                     params.smallQuads = scene->smallLayout.nQuads | scene->smallLayout.shadowQuadPairs << 16 | scene->smallLayout.shadowLonePairs << 24;
                 }
+                // (the headline: the Cornell-like instantiation of a pass whose units are one sample each has a body of its own,
+                // kernels.h: pathSmall<.., SINGLE>; same records, same counts)
+                if (!decltype(COUNT)::value && std::is_same<TRAITS, TraitsLambertianTriangles>::value && params.chunk == 1) { return k_path_small_single; }
                 return k_path_small<true, decltype(COUNT)::value, TRAITS, false, true>;
             };
             // some triangles are halves of parallelograms: phase 1 tests those as parallelograms (small_items.h).  The rough, smooth

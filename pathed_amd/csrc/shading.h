@@ -79,7 +79,7 @@ struct Rng {
     uint32_t k0, k1;
     uint32_t dimension;
 
-    __device__ inline float next()
+    __host__ __device__ inline float next()
     {
         const uint32_t bits = mix32(k0 + mix32(k1 + dimension * 0x9e3779b9u));
         dimension++;
@@ -96,7 +96,64 @@ __host__ __device__ inline void makeKey(uint64_t seed, uint32_t pixel, uint32_t 
 
 // dimension layout: [0,1] pixel jitter (X first, src/camera.cpp:51-52);
 // vertex k >= 1 owns 8 dimensions from 2 + 8(k-1): +0..2 BSDF, +3 light choice, +4,+5 light
-__device__ inline uint32_t vertexBase(int vertex) { return 2u + 8u * (uint32_t)(vertex - 1); }
+__host__ __device__ inline uint32_t vertexBase(int vertex) { return 2u + 8u * (uint32_t)(vertex - 1); }
+
+// Inner keys (k_path_small_single).  Rng::next() runs two mixers, and the inner one, mix32(k1 + dimension * G), depends on
+// the sample index and the dimension alone: in the default unit order the lanes of a wave share k1 for a whole image, so the
+// wave keeps the inner keys of its current and its previous k1 in LDS, one ROW of eight per vertex, and a lane that finds
+// its k1 there draws a vertex's numbers with one mixer each.  A lane that does not fills the row itself: the same integers
+// either way.  Host-callable: tests/key_rows_host.hip runs this text against Rng::next().
+static const int kKeyVertices = 12;     // rows of a table: vertices 1 .. 12 cover lastBounce 10; later vertices fill their own
+static const int kKeyRowWords = 8;      // vertexBase's stride
+static const int kKeyTableWords = kKeyVertices * kKeyRowWords;
+
+__host__ __device__ inline uint32_t innerKey(uint32_t k1, uint32_t dimension) { return mix32(k1 + dimension * 0x9e3779b9u); }
+
+// the row of `vertex` (>= 1) of the stream with second key k1: row[j] keys dimension vertexBase(vertex) + j
+__host__ __device__ inline void fillKeyRow(uint32_t k1, int vertex, uint32_t *row)
+{
+    for (int j = 0; j < kKeyRowWords; j++) { row[j] = innerKey(k1, vertexBase(vertex) + (uint32_t)j); }
+}
+
+// Rng::next() of (k0, k1, vertexBase(vertex) + column) from the filled row of (k1, vertex)
+__host__ __device__ inline float drawFromRow(uint32_t k0, const uint32_t *row, uint32_t column)
+{
+    const uint32_t bits = mix32(k0 + row[column]);
+    return (float)(bits >> 8) * 5.9604638e-08f;
+}
+
+// one vertex's numbers as a stream: `dimension` counts from the vertex's base
+struct RowRng {
+    uint32_t k0;
+    const uint32_t *row;
+    uint32_t dimension;
+
+    __host__ __device__ inline float next() { return drawFromRow(k0, row, dimension++); }
+};
+
+// The two tables of a wave: which k1 each holds, and which goes next.  find: the table of k1, or -1.  claim: the table a
+// new k1 is built in -- an empty one, else the OLDER of the two.
+struct KeySlots {
+    uint32_t tag[2];
+    uint32_t filled;   // bit s: table s holds tag[s]
+    uint32_t older;    // the table claimed less recently
+
+    __host__ __device__ inline void clear() { tag[0] = 0u; tag[1] = 0u; filled = 0u; older = 0u; }
+    __host__ __device__ inline int find(uint32_t k1) const
+    {
+        if ((filled & 1u) != 0u && tag[0] == k1) { return 0; }
+        if ((filled & 2u) != 0u && tag[1] == k1) { return 1; }
+        return -1;
+    }
+    __host__ __device__ inline int claim(uint32_t k1)
+    {
+        const int slot = (filled & 1u) == 0u ? 0 : (filled & 2u) == 0u ? 1 : (int)older;
+        if (slot == 0) { tag[0] = k1; } else { tag[1] = k1; }
+        filled |= 1u << slot;
+        older = (uint32_t)(slot ^ 1);
+        return slot;
+    }
+};
 
 // ------------------------------------------------------------------------- frames
 

@@ -96,7 +96,7 @@ def main():
     parser.add_argument("--kernel", default="k_path_small|k_path_hybrid|k_path_wave|k_shade|k_trace<")
     parser.add_argument("--loops", action="store_true")
     parser.add_argument("--json", default="")
-    parser.add_argument("--bench-json", default="", help="write the trip-count-weighted mix of the Cornell instantiation of k_path_small (what bench.py times) here")
+    parser.add_argument("--bench-json", default="", help="write the trip-count-weighted mix of k_path_small_single, the Cornell instantiation of the fused kernel's body (what bench.py times), here")
     parser.add_argument("--quad-pairs", type=int, default=8, help="trips of the parallelogram-pair loop per pass (Cornell: the pass list's 15 parallelograms, 17 less the two exact copies)")
     parser.add_argument("--lone-pairs", type=int, default=1, help="trips of the lone-triangle-pair loop per pass (Cornell: 2 triangles)")
     parser.add_argument("--shadow-quad-pairs", type=int, default=6, help="... of them run for the shadow ray as well (Cornell: 12 occluder parallelograms)")
@@ -157,7 +157,8 @@ def sources_digest():
 def write_bench_mix(kernels, pretty, args):
     """One iteration of the fused kernel's loop as the compiler laid it out, every block once, the two phase-1 loops times
     their trip counts on the benchmarked scene: the mix bench.py prices against the box's probed issue rates."""
-    wanted = r"k_path_small<true, false, SceneTraits<1u, false, true, false, false, true, 3u>, false, true>"
+    # (the launch of one sample per unit, bench.py's; until it was split off: k_path_small<true, false, SceneTraits<1u, ..>, false, true>)
+    wanted = r"k_path_small_single\("
     for name, blocks in kernels.items():
         shown = pretty[name].replace("pathed::", "").replace("void ", "")
         if not re.search(wanted, shown):
@@ -227,7 +228,7 @@ def write_bench_mix(kernels, pretty, args):
             json.dump(result, handle, indent=1)
         print("bench mix: %s" % json.dumps(result["classes"]))
         return
-    raise SystemExit("static_mix.py: the Cornell instantiation of k_path_small was not found in the assembly")
+    raise SystemExit("static_mix.py: k_path_small_single was not found in the assembly")
 
 
 if __name__ == "__main__":

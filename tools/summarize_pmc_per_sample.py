@@ -95,15 +95,17 @@ def workload(prefix, samples, with_valu):
     return entry
 
 
+out = os.path.join(ROOT, "profiles", "pmc_per_sample.json")
+# a run of the Cornell passes alone (WORKLOADS=cornell) leaves the large_bvh entry as it is
+dragon = os.path.isdir(os.path.join(base, "dragon_fetch"))
 summary = {
     "note": "rocprofv3 --pmc passes of tools/pmc_per_sample.sh, one counter group per pass, over exactly the timed path's kernels; "
             "HBM bytes = 2 x FETCH_SIZE + WRITE_SIZE (gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md); large_bvh is ONE 64-spp call "
             "(ramp-up and drain of the slot pool included: 61 % of the slot visits carry a ray, a long render does better)",
     "tag": tag,
     "cornell_1024": workload("cornell", 1024 * 1024 * 256, True),
-    "large_bvh": workload("dragon", 1920 * 1080 * 64, os.path.isdir(os.path.join(base, "dragon_valu"))),
+    "large_bvh": workload("dragon", 1920 * 1080 * 64, os.path.isdir(os.path.join(base, "dragon_valu"))) if dragon else json.load(open(out))["large_bvh"],
 }
-out = os.path.join(ROOT, "profiles", "pmc_per_sample.json")
 json.dump(summary, open(out, "w"), indent=1)
 for name in ("cornell_1024", "large_bvh"):
     entry = summary[name]
