@@ -226,7 +226,9 @@ typedef struct PathedStats {
                                       8 feature kernel (the last call was pathed_hip_render_features[_device], or a render call
                                         of PATHED_INTEGRATOR_ALBEDO; its samples count in camera_samples and closest_rays),
                                       9 multiple-scattering volume kernel (PATHED_INTEGRATOR_BASIC_VOLUME),
-                                      10 wavefront of an instanced scene (k_trace_instanced + k_shade_instanced) */
+                                      10 wavefront of an instanced scene (k_trace_instanced + k_shade_instanced),
+                                      11 anisotropic multiple-scattering volume kernel (PATHED_INTEGRATOR_BASIC_VOLUME on a scene
+                                         with a Henyey-Greenstein medium, pathed_hip_scene_set_medium_phase) */
     uint32_t reserved0;
     uint64_t local_closest_rays;   /* closest-hit queries the shade kernel resolved itself (rays that cannot meet anything but the
                                       scene's few large triangles, PathedSceneOptions.local_rays) -- stats mode; NOT in closest_rays */
@@ -667,6 +669,34 @@ int pathed_hip_debug_shading_queries(PathedScene *scene, int function, int trait
  * u: n * 2 floats in [0, 1] (z's number, then phi's); out: n * 3 floats, the direction (r cos phi, z, r sin phi).  Host
  * memory both.  PATHED_E_INVALID, and nothing is launched: a number outside [0, 1], more than 2^20 records. */
 int pathed_hip_debug_phase_samples(PathedScene *scene, size_t n, const float *u, float *out);
+
+/* Anisotropic scattering: the Henyey-Greenstein phase function (pathed_amd/csrc/volume.h states value, sample, frame and
+ * threshold).  PathedMedium does not know it: like a grid, a phase function is set on a medium slot of a CREATED scene,
+ * homogeneous or grid; called again on the same slot it replaces the entry.  g > 0 scatters forward, along the direction the
+ * path travels in.  A slot of type PATHED_PHASE_ISOTROPIC, one with |g| < 1e-3 and one never set scatter isotropically, with
+ * the bits they always had.
+ * A scene with at least one Henyey-Greenstein slot of |g| >= 1e-3 (whether or not a surface references the slot):
+ *   - PATHED_INTEGRATOR_BASIC_VOLUME render calls (render, render_device, render_moments*) run the anisotropic kernels,
+ *     PathedStats.path_kernel 11;
+ *   - PATHED_INTEGRATOR_VOLUME_PATH_TRACER render calls and pixel-list renders (pathed_hip_render_pixels_device) under either
+ *     volume integrator return PATHED_E_UNSUPPORTED, and nothing is launched.
+ * PATHED_E_INVALID, and the scene is as it was: a null scene or pointer, a wrong struct_size, an index out of range (so: a
+ * scene without media), an unknown type, g not finite or |g| > 0.99. */
+enum { PATHED_PHASE_ISOTROPIC = 0, PATHED_PHASE_HENYEY_GREENSTEIN = 1 };
+#define PATHED_PHASE_ISOTROPIC_BELOW 1e-3f   /* the threshold on |g| */
+typedef struct PathedPhaseFunction {
+    uint32_t struct_size;   /* sizeof(PathedPhaseFunction) */
+    int32_t type;           /* PATHED_PHASE_* */
+    float g;                /* mean cosine, |g| <= 0.99; ignored by PATHED_PHASE_ISOTROPIC (but checked) */
+} PathedPhaseFunction;
+int pathed_hip_scene_set_medium_phase(PathedScene *scene, int medium_index, const PathedPhaseFunction *phase);
+
+/* Test hook onto that phase function, beside pathed_hip_debug_phase_samples: one thread per record calls the two functions
+ * the anisotropic kernels call.  records: n * 9 floats (g, w(3), u1, u2, wi(3)) -- w the unit propagation direction, wi a unit
+ * direction, u1 and u2 in [0, 1]; out: n * 4 floats, the direction sampled about w from (u1, u2), then p(w, wi).  Host memory
+ * both.  Below the threshold the direction is pathed_hip_debug_phase_samples' and p is 1.f / fourPi.
+ * PATHED_E_INVALID, and nothing is launched: |g| > 0.99, a number outside [0, 1] or not finite, more than 2^20 records. */
+int pathed_hip_debug_phase_hg(PathedScene *scene, size_t n, const float *records, float *out);
 
 /* Test hook onto the intersector that stands in for Embree.
  * rays: n * 8 floats (ox,oy,oz,tnear, dx,dy,dz,tfar), host memory.

@@ -80,6 +80,18 @@ class PathedGridMedium(C.Structure):
     ]
 
 
+PHASE_ISOTROPIC, PHASE_HENYEY_GREENSTEIN = 0, 1
+PHASE_ISOTROPIC_BELOW = 0.0010000000474974513   # PATHED_PHASE_ISOTROPIC_BELOW: 1e-3f as a double
+
+
+class PathedPhaseFunction(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("type", C.c_int32),
+        ("g", C.c_float),
+    ]
+
+
 class PathedEnvLight(C.Structure):
     _fields_ = [
         ("width", C.c_int32),
@@ -246,6 +258,8 @@ HIP_SYMBOLS = [
     "pathed_hip_grid_queries",
     "pathed_hip_debug_shading_queries",
     "pathed_hip_debug_phase_samples",
+    "pathed_hip_scene_set_medium_phase",
+    "pathed_hip_debug_phase_hg",
     "pathed_hip_scene_destroy",
     "pathed_hip_render",
     "pathed_hip_render_device",
@@ -416,6 +430,11 @@ def load_hip():
     if hasattr(lib, "pathed_hip_debug_phase_samples"):
         lib.pathed_hip_debug_phase_samples.argtypes = [vp, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.pathed_hip_debug_phase_samples.restype = C.c_int
+    if hasattr(lib, "pathed_hip_scene_set_medium_phase"):   # (an older build of the same ABI, as above)
+        lib.pathed_hip_scene_set_medium_phase.argtypes = [vp, C.c_int, C.POINTER(PathedPhaseFunction)]
+        lib.pathed_hip_scene_set_medium_phase.restype = C.c_int
+        lib.pathed_hip_debug_phase_hg.argtypes = [vp, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.pathed_hip_debug_phase_hg.restype = C.c_int
     lib.pathed_hip_scene_refit.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.pathed_hip_scene_refit.restype = C.c_int
     lib.pathed_hip_has_experiments.argtypes = []
@@ -468,6 +487,10 @@ def load_host():
     lib.pathed_host_scene_grid_count.restype = C.c_int
     lib.pathed_host_scene_grid.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.pathed_host_scene_grid.restype = C.POINTER(PathedGridMedium)
+    lib.pathed_host_scene_phase_count.argtypes = [C.c_void_p]
+    lib.pathed_host_scene_phase_count.restype = C.c_int
+    lib.pathed_host_scene_phase.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    lib.pathed_host_scene_phase.restype = C.c_int
     lib.pathed_host_last_error.argtypes = []
     lib.pathed_host_last_error.restype = C.c_char_p
     if hasattr(lib, "pathed_host_scene_instances"):

@@ -3475,8 +3475,12 @@ __device__ __forceinline__ void volumeQueryPairSmall(const VolumeContext<Materia
 // MULTI: the bounce loop is BasicVolumeIntegrator::L (multiple scattering, a stack of media) instead of VolumePathTracer::L; the
 // instantiations with it are k_path_scatter / k_path_scatter_grid, and the others contain none of its code.
 // LIST: the units walk a pixel list (unitPlace<true>): k_list_volume alone.
-template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS, bool QUADS, bool GRID, bool MULTI = false, bool LIST = false>
-__device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTris &smallTris)
+// ANISO (with MULTI): media scatter by Henyey-Greenstein (volume.h), one g per medium slot in `phaseG`, a table of its own that
+// arrives as a kernel argument beside RenderParams; k_path_aniso / k_path_aniso_grid alone.  It is read under `if constexpr`
+// in the two statements the phase function enters -- the light sample of a scatter point and the direction after the event --
+// and no other instantiation contains any of it.
+template <bool LDS_MATERIALS, int STACK, bool SMALL, typename TRAITS, bool QUADS, bool GRID, bool MULTI = false, bool LIST = false, bool ANISO = false>
+__device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTris &smallTris, const float *phaseG = nullptr)
 {
     extern __shared__ float4 ldsRaw[];
     // LDS: [STACK + 1][kBlock] traversal stack rows, then (LDS_MATERIALS) the material table
@@ -3755,6 +3759,10 @@ __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTri
         if (TRAITS::env && light.kind == 2) { emitted = envEmit(scene.env, lightWo); }
         else { emitted = matEmit(materials[lightMaterial]); }
         const float fourPi = (float)(4.f * 3.14159265358979323846);   // `4.f * M_PI` is a double, Color::operator/ takes a float
+        if constexpr (ANISO) {
+            const float g = phaseG[medium];
+            if (!phaseIsIsotropic(g)) { return emitted * shadowTransmittance * phaseValueHG(g, normalized(exitPoint - entry), wiWorld) / pdf; }
+        }
         return emitted * shadowTransmittance * 1.f / fourPi / pdf;
     };
 
@@ -3856,7 +3864,8 @@ __device__ __forceinline__ void pathVolume(const RenderParams &p, const SmallTri
                     modulation = modulation * weight;
                     result = result + Ld * modulation;   // not gated by the bounce window (:99-101)
                     random.dimension = phaseBase(bounce);
-                    direction = phaseSample<TRAITS::pairedTrig>(random);
+                    if constexpr (ANISO) { direction = mediumPhaseSample<TRAITS::pairedTrig>(phaseG[medium], normalized(next.point - origin), random); }
+                    else { direction = phaseSample<TRAITS::pairedTrig>(random); }
                     origin = event.point;
                     surface = false;
                 } else {
@@ -3987,6 +3996,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_V
     pathVolume<false, STACK, SMALL, TraitsAll, false, true, true>(p, smallTris);
 }
 
+// BasicVolumeIntegrator over Henyey-Greenstein media (pathVolume<.., ANISO>): the scatter family's shape, SMALL with 8 stack rows
+// or the tree walk with 22 (a tree that would fit 8 or 16 rows takes the 22-row form): four instantiations in all
+template <int STACK, bool SMALL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_aniso(RenderParams p, SmallTris smallTris, const float *phaseG)
+{
+    pathVolume<false, STACK, SMALL, TraitsAll, false, false, true, false, true>(p, smallTris, phaseG);
+}
+
+template <int STACK, bool SMALL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PATHED_VOLUME_WAVES, PATHED_VOLUME_WAVES))) void k_path_aniso_grid(RenderParams p, SmallTris smallTris, const float *phaseG)
+{
+    pathVolume<false, STACK, SMALL, TraitsAll, false, true, true, false, true>(p, smallTris, phaseG);
+}
+static_assert(sizeof(RenderParams) + sizeof(SmallTris) + sizeof(const float *) <= 4096, "the anisotropic kernels' arguments must fit the 4 KB kernarg segment");
+
 // The volume integrators over a pixel list (pathed_hip_render_pixels_device; THE UNIT ORDER: kOrderList): the one form of
 // pathVolume that knows the list order, in the generic shape of the grid and scatter families -- every material, pair-of-
 // triangles phase 1, the material table read from memory -- for SMALL scenes (8 stack rows) or the tree walk with 22 rows in
@@ -4013,6 +4037,24 @@ __global__ __launch_bounds__(kBlock) void k_debug_phase_samples(int n, const flo
     random.u[0] = u[2 * (size_t)i]; random.u[1] = u[2 * (size_t)i + 1]; random.taken = 0;
     const V3 direction = phaseSample<TraitsAll::pairedTrig>(random);
     out[3 * (size_t)i] = direction.x; out[3 * (size_t)i + 1] = direction.y; out[3 * (size_t)i + 2] = direction.z;
+}
+
+// Test hook behind pathed_hip_debug_phase_hg: one thread per record (g, w, u1, u2, wi) -> (the sampled direction, p(w, wi)),
+// through the two functions the anisotropic kernels call
+__global__ __launch_bounds__(kBlock) void k_debug_phase_hg(int n, const float *records, float *out)
+{
+    const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (i >= n) { return; }
+    const float *record = records + 9 * (size_t)i;
+    const float g = record[0];
+    const V3 w = v3(record[1], record[2], record[3]);
+    const V3 wi = v3(record[6], record[7], record[8]);
+    ScriptedPair random;
+    random.u[0] = record[4]; random.u[1] = record[5]; random.taken = 0;
+    const V3 direction = mediumPhaseSample<TraitsAll::pairedTrig>(g, w, random);
+    float *result = out + 4 * (size_t)i;
+    result[0] = direction.x; result[1] = direction.y; result[2] = direction.z;
+    result[3] = mediumPhaseValue(g, w, wi);
 }
 
 // ------------------------------------------------------------------------- scene set-up

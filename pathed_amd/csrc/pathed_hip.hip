@@ -303,6 +303,12 @@ struct PathedScene {
     std::vector<DMedium> mediaHost;
     std::vector<DGrid> gridsHost;
     std::vector<std::vector<float>> gridCells;   // per grid
+    // phase functions (volume.h: Henyey-Greenstein; pathed_hip_scene_set_medium_phase): per medium slot the type and g as they
+    // were set, and the table the anisotropic kernels read (g, 0 for an isotropic slot).  Empty until the first call.
+    std::vector<int> phaseTypeHost;
+    std::vector<float> phaseGHost;
+    DeviceBuffer<float> phaseG;
+    bool anisotropic = false;   // some slot is Henyey-Greenstein with |g| >= kPhaseIsotropicBelow: BasicVolumeIntegrator runs k_path_aniso
     DeviceBuffer<int> volumeOverflow;   // the volume kernel's traversal-stack spill, per thread
     // the fused kernel's per-pixel camera-ray candidate masks (camera_masks.h), then its started samples, per wave of its largest
     // grid (kernels.h: the camera queue)
@@ -2458,6 +2464,25 @@ static int renderPassVolume(PathedScene *scene, const Pass &pass)
             }); }); });
         });
     }
+    if (scene->anisotropic && scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME) {
+        // Henyey-Greenstein media: k_path_aniso / k_path_aniso_grid<STACK, SMALL>, the scatter family's shape with the per-slot g
+        // table as a third argument; a tree scene takes the 22-row form whatever its own row count
+        const bool small = scene->bruteForce;
+        const int rows = small ? 8 : 22;
+        return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, rows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
+            const size_t lds = (size_t)(rows + 1) * kBlock * sizeof(int);
+            params.smallQuads = 0;
+            params.smallKappaT = scene->smallLayout.kappaT;
+            params.scene.leafTris = scene->leafTris.ptr;
+            const float *table = scene->phaseG.ptr;
+            const bool grids = !scene->gridsHost.empty();
+            const auto run = [&](void (*kernel)(RenderParams, SmallTris, const float *)) {
+                hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, scene->smallTris, table);
+            };
+            if (small) { run(grids ? k_path_aniso_grid<8, true> : k_path_aniso<8, true>); }
+            else { run(grids ? k_path_aniso_grid<22, false> : k_path_aniso<22, false>); }
+        });
+    }
     return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, scene->stackRows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
         const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
         const bool small = scene->bruteForce;
@@ -2914,6 +2939,17 @@ static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uin
     }
     if (!scene->gridsHost.empty() && !volumeIntegrator(scene)) {
         return fail(PATHED_E_UNSUPPORTED, "a scene with a voxel-grid medium renders with the VolumePathTracer integrator only (pathed_hip_set_integrator)");
+    }
+    if (scene->anisotropic && volumeIntegrator(scene)) {
+        // Henyey-Greenstein media exist on BasicVolumeIntegrator's whole-image kernels alone (k_path_aniso, kernels.h)
+        if (scene->integrator == PATHED_INTEGRATOR_VOLUME_PATH_TRACER) {
+            return fail(PATHED_E_UNSUPPORTED, "the scene has a Henyey-Greenstein medium: VolumePathTracer scatters isotropically only, select the "
+                                              "BasicVolumeIntegrator (pathed_hip_set_integrator)");
+        }
+        if (pixels) {
+            return fail(PATHED_E_UNSUPPORTED, "the scene has a Henyey-Greenstein medium: pixel lists are not rendered on the anisotropic kernels "
+                                              "(k_list_volume scatters isotropically only)");
+        }
     }
     SELECT_DEVICE(scene);
     hipStream_t stream = (hipStream_t)stream_handle;
@@ -3403,6 +3439,41 @@ int pathed_hip_scene_set_grid_medium(PathedScene *scene, int medium_index, const
     return PATHED_OK;
 }
 
+int pathed_hip_scene_set_medium_phase(PathedScene *scene, int medium_index, const PathedPhaseFunction *phase)
+{
+    if (!scene || !phase) { return fail(PATHED_E_INVALID, "null scene or phase function"); }
+    if (phase->struct_size != sizeof(PathedPhaseFunction)) { return fail(PATHED_E_INVALID, "PathedPhaseFunction.struct_size does not match this library"); }
+    if (medium_index < 0 || (size_t)medium_index >= scene->mediaHost.size()) { return fail(PATHED_E_INVALID, "medium phase: medium index out of range"); }
+    if (phase->type != PATHED_PHASE_ISOTROPIC && phase->type != PATHED_PHASE_HENYEY_GREENSTEIN) { return fail(PATHED_E_INVALID, "medium phase: unknown phase function type"); }
+    if (!std::isfinite(phase->g) || std::fabs(phase->g) > 0.99f) { return fail(PATHED_E_INVALID, "medium phase: g must be finite with |g| <= 0.99"); }
+    SELECT_DEVICE(scene);
+
+    // the new tables, built beside the old ones: a failure leaves the scene as it was
+    const size_t slots = scene->mediaHost.size();
+    std::vector<int> types = scene->phaseTypeHost;
+    std::vector<float> gs = scene->phaseGHost;
+    types.resize(slots, PATHED_PHASE_ISOTROPIC);
+    gs.resize(slots, 0.f);
+    types[(size_t)medium_index] = phase->type;
+    gs[(size_t)medium_index] = phase->g;
+    std::vector<float> table(slots, 0.f);
+    bool anisotropic = false;
+    for (size_t i = 0; i < slots; i++) {
+        if (types[i] != PATHED_PHASE_HENYEY_GREENSTEIN) { continue; }
+        table[i] = gs[i];
+        anisotropic = anisotropic || !(std::fabs(gs[i]) < kPhaseIsotropicBelow);
+    }
+    HIP_TRY(hipDeviceSynchronize());   // nothing of this scene runs (as in pathed_hip_scene_set_grid_medium)
+    DeviceBuffer<float> device;
+    HIP_TRY(device.upload(table));
+    std::swap(scene->phaseG.ptr, device.ptr);
+    std::swap(scene->phaseG.count, device.count);
+    scene->phaseTypeHost.swap(types);
+    scene->phaseGHost.swap(gs);
+    scene->anisotropic = anisotropic;
+    return PATHED_OK;
+}
+
 int pathed_hip_grid_queries(PathedScene *scene, int medium_index, size_t n, const float *a, const float *b, const float *target,
                             float *transmittance, float *distance)
 {
@@ -3447,6 +3518,32 @@ int pathed_hip_debug_phase_samples(PathedScene *scene, size_t n, const float *u,
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, deviceOut.ptr, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return PATHED_OK;
+}
+
+int pathed_hip_debug_phase_hg(PathedScene *scene, size_t n, const float *records, float *out)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (n == 0) { return PATHED_OK; }
+    if (!records || !out) { return fail(PATHED_E_INVALID, "null record or result buffer"); }
+    if (n > (size_t)1 << 20) { return fail(PATHED_E_INVALID, "too many records in one call"); }
+    for (size_t i = 0; i < n; i++) {
+        const float *record = records + 9 * i;
+        if (!std::isfinite(record[0]) || std::fabs(record[0]) > 0.99f) { return fail(PATHED_E_INVALID, "phase records: g must be finite with |g| <= 0.99"); }
+        if (!(record[4] >= 0.f && record[4] <= 1.f) || !(record[5] >= 0.f && record[5] <= 1.f)) { return fail(PATHED_E_INVALID, "phase records: random numbers lie in [0, 1]"); }
+        for (int k = 1; k < 9; k++) {
+            if (!std::isfinite(record[k])) { return fail(PATHED_E_INVALID, "phase records: directions must be finite"); }
+        }
+    }
+    SELECT_DEVICE(scene);
+    DeviceBuffer<float> deviceIn, deviceOut;
+    HIP_TRY(deviceIn.upload(std::vector<float>(records, records + 9 * n)));
+    HIP_TRY(deviceOut.allocate(4 * n));
+    HIP_TRY(hipMemset(deviceOut.ptr, 0, 4 * n * sizeof(float)));
+    hipLaunchKernelGGL(k_debug_phase_hg, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, (int)n, deviceIn.ptr, deviceOut.ptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, deviceOut.ptr, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
     return PATHED_OK;
 }
 
@@ -3979,7 +4076,7 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
     out->bvh_build_ms = scene->bvhBuildMs;
     out->bvh_builder = (uint32_t)scene->bvhBuilder;
     out->trace_launches_all = (uint32_t)scene->traceLaunchesAll;
-    out->path_kernel = scene->instanced ? 10u : scene->lastCallFeatures ? 8u : (scene->lastCallList && !usesVolumeKernel(scene)) ? 1u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? 9u : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
+    out->path_kernel = scene->instanced ? 10u : scene->lastCallFeatures ? 8u : (scene->lastCallList && !usesVolumeKernel(scene)) ? 1u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? (scene->anisotropic ? 11u : 9u) : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
     if (tuningEnv("PATHED_SHADE_PROFILE")) {   // counters exist in -DPATHED_SHADE_PROFILE builds only
         static const char *regions[11] = { "all waves", "active slots", "makeIsect (hit)", "camera-ray vertex", "finish previous MIS term",
                                            "new vertex: BSDF sample", "light sampling", "sample finished", "startSample (regeneration)", "shadow ray pushed",

@@ -264,6 +264,73 @@ __device__ inline V3 phaseSample(RNG &random)
     return v3(x, z, y);
 }
 
+// ---- Henyey-Greenstein media (pathed_hip_scene_set_medium_phase; k_path_aniso / k_path_aniso_grid)
+// One g per medium slot, in a table of its own beside DScene::media.  fp32, one rounding per operation.
+//   w    the unit propagation direction of the segment the event lies on, normalized(exitPoint - entry)
+//   g2 = g * g
+// Value, c = dot(w, wi):      x = (1 + g2) - (2 g) c,   p = ((1 - g2) / (x * sqrtf(x))) / fourPi
+// Sample, from phaseBase(bounce) + {0, 1}:
+//   s = (1 - g2) / ((1 - g) + (2 g) u1),   c = ((1 + g2) - s s) / (2 g) clamped to [-1, 1]   (u1 = 0: c = -1, u1 = 1: c = +1)
+//   sinTheta = sqrtf(fmaxf(0, 1 - c c)),   phi = twoPiTimes(u2)
+//   THE FRAME: normalToWorldSpace1(w) (shading.h, the frame of every BSDF sample, pinned by golden vectors), local vector
+//   (sinTheta cos phi, c, sinTheta sin phi): w is the frame's `normal`, the middle component.
+// The pdf of the sample is the value, so a path's weight after the sample is 1, as with the isotropic sample.
+//
+// THE THRESHOLD.  A slot with |g| < kPhaseIsotropicBelow = 1e-3 (pbrt's value), and every slot never given a phase function,
+// runs the two isotropic statements literally -- phaseSample and `1.f / fourPi` -- and gives their bits.  c divides a
+// difference of two numbers near 1 by 2 g: its rounding error is about eps (1 + g2 + s s) / (2 |g|) per operation on the way
+// (the bound below), 3e-4 at |g| = 1e-3 and growing as 1 / |g| beneath it, while the function itself is within 3 |g| of the
+// isotropic one there (p * fourPi = 1 + 3 g c + O(g2)): at 1e-3 the two are 3e-3 against 3e-4, a decade apart; a decade
+// lower the sample's rounding would be as large as everything the function has left to say.
+//
+// THE BOUND on c (tests/test_gpu_anisotropic.py holds the hook to it), first order in eps = 2^-24, for exact g and u1:
+//   kappa = (|1 - g| + |2 g u1|) / |(1 - g) + 2 g u1|      the conditioning of the sum in s's denominator (1 for g > 0)
+//   rho   = 1 / (1 - g2) + kappa + 2                        relative error of s in eps: 1 - g2 after the rounding of g2, the sum
+//                                                           after its two roundings, the division
+//   |c_fp32 - c| <= eps { [1 + 2 g2 + s s (2 rho + 1)] / (2 |g|) + 2 }
+// -- the ten roundings weighted by the conditioning (1 + g2 + s s) / (2 |g|) of the last division.
+static const float kPhaseIsotropicBelow = PATHED_PHASE_ISOTROPIC_BELOW;   // include/pathed_hip.h: the hosts read it too
+
+__device__ inline bool phaseIsIsotropic(float g) { return fabsf(g) < kPhaseIsotropicBelow; }
+
+__device__ inline float phaseFourPi() { return (float)(4.f * 3.14159265358979323846); }   // as in pathVolume's scatter
+
+__device__ inline float phaseValueHG(float g, V3 w, V3 wi)
+{
+    const float g2 = g * g;
+    const float c = dot(w, wi);
+    const float x = (1.f + g2) - (2.f * g) * c;
+    return ((1.f - g2) / (x * sqrtf(x))) / phaseFourPi();
+}
+
+template <bool PAIRED = false, typename RNG>
+__device__ inline V3 phaseSampleHG(float g, V3 w, RNG &random)
+{
+    const float g2 = g * g;
+    const float u1 = random.next();
+    const float s = (1.f - g2) / ((1.f - g) + (2.f * g) * u1);
+    const float c = clampf(((1.f + g2) - s * s) / (2.f * g), -1.f, 1.f);
+    const float sinTheta = sqrtf(fmaxf(0.f, 1.f - c * c));
+    const float phi = twoPiTimes(random.next());
+    float cosPhi, sinPhi;
+    cosSin<PAIRED>(phi, &cosPhi, &sinPhi);
+    return toWorld(normalToWorldSpace1(w), v3(sinTheta * cosPhi, c, sinTheta * sinPhi));
+}
+
+// ... of a medium slot whose table entry is g: what the anisotropic kernels and the hook (k_debug_phase_hg) call
+template <bool PAIRED = false, typename RNG>
+__device__ inline V3 mediumPhaseSample(float g, V3 w, RNG &random)
+{
+    if (phaseIsIsotropic(g)) { return phaseSample<PAIRED>(random); }
+    return phaseSampleHG<PAIRED>(g, w, random);
+}
+
+__device__ inline float mediumPhaseValue(float g, V3 w, V3 wi)
+{
+    if (phaseIsIsotropic(g)) { return 1.f / phaseFourPi(); }
+    return phaseValueHG(g, w, wi);
+}
+
 // The media a path is inside of, innermost last: the reference's std::vector<std::shared_ptr<Medium>> with room for four,
 // -1 = "no medium" (the inside of a glass ball is an entry like any other).  Four named words and selects rather than an
 // indexed array: an array indexed by `depth` would live in scratch, and the kernel spills as it is.

@@ -68,6 +68,23 @@ const PathedGridMedium *pathed_host_scene_grid(void *handle, int index, int *med
     return scene.gridDesc((size_t)index);
 }
 
+// the Henyey-Greenstein phase functions of a loaded scene (scene_loader.h: FlatPhase): how many, and entry i as (medium slot, g)
+int pathed_host_scene_phase_count(void *handle)
+{
+    if (!handle) { return 0; }
+    return (int)((LoadedScene *)handle)->scene.phases.size();
+}
+
+int pathed_host_scene_phase(void *handle, int index, int *mediumIndex, float *g)
+{
+    if (!handle) { return -1; }
+    const pathed::FlatScene &scene = ((LoadedScene *)handle)->scene;
+    if (index < 0 || (size_t)index >= scene.phases.size()) { return -1; }
+    if (mediumIndex) { *mediumIndex = scene.phases[(size_t)index].medium; }
+    if (g) { *g = scene.phases[(size_t)index].g; }
+    return 0;
+}
+
 void pathed_host_free_scene(void *handle)
 {
     delete (LoadedScene *)handle;
@@ -175,6 +192,7 @@ static std::string flatSceneDigest(const pathed::FlatScene &flat)
         add(grid.desc.world_to_model, sizeof grid.desc.world_to_model); add(grid.desc.model_to_world, sizeof grid.desc.model_to_world);
         add(grid.data.data(), sizeof(float) * grid.data.size());
     }
+    for (const pathed::FlatPhase &phase : flat.phases) { add(&phase.medium, sizeof phase.medium); add(&phase.g, sizeof phase.g); }   // (none: the digest is what it was)
     char text[32];
     snprintf(text, sizeof text, "%016llx", hash);
     return text;
@@ -230,6 +248,17 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
                 throw std::runtime_error("job: the " + name + " does not render a scene with instances (the PathTracer does)");
             }
             builder = "sah";
+        }
+        if (flat.anisotropic()) {
+            // a medium with a Henyey-Greenstein "phase": what the library refuses on such a scene stops the job here, by name,
+            // before a tree is built
+            const std::string name = job.integratorName();
+            if (name == "VolumePathTracer") {
+                throw std::runtime_error("job: the VolumePathTracer does not render a scene with a henyey-greenstein medium (the BasicVolumeIntegrator does)");
+            }
+            if (noise.adaptive && name == "BasicVolumeIntegrator") {
+                throw std::runtime_error("job: \"adaptive\" does not go with a scene with a henyey-greenstein medium: pixel lists are not rendered on the anisotropic kernels");
+            }
         }
         if (builder == "auto") {
             // several replicas of a large mesh: each GPU builds its own tree in milliseconds (PLOC) instead of N host SAH

@@ -137,6 +137,7 @@ void Scene::upload(int bvhBuilderPlusOne)
     const PathedSceneDesc desc = m_flat.desc();
     const PathedInstanceDesc instances = m_flat.instanceDesc();   // scene files with "instance" / "instanced" models
     for (size_t i = 0; i < m_flat.grids.size(); i++) { (void)m_flat.gridDesc(i); }   // (sets the data pointers once, before the replica threads read them)
+    for (size_t i = 0; i < m_flat.phases.size(); i++) { (void)m_flat.phaseDesc(i); }   // (... and fills the phase records)
     try {
         // every device builds / uploads its own replica, in parallel
         ReplicaWorkers workers(m_devices.size());
@@ -156,6 +157,11 @@ void Scene::upload(int bvhBuilderPlusOne)
             for (size_t i = 0; i < m_flat.grids.size(); i++) {   // the scene file's voxel-grid media, each on its medium slot
                 if (pathed_hip_scene_set_grid_medium(m_handles[r], m_flat.grids[i].medium, m_flat.gridDesc(i)) != PATHED_OK) {
                     throw std::runtime_error(hipError("pathed_hip_scene_set_grid_medium"));
+                }
+            }
+            for (size_t i = 0; i < m_flat.phases.size(); i++) {   // ... and its Henyey-Greenstein phase functions
+                if (pathed_hip_scene_set_medium_phase(m_handles[r], m_flat.phases[i].medium, m_flat.phaseDesc(i)) != PATHED_OK) {
+                    throw std::runtime_error(hipError("pathed_hip_scene_set_medium_phase"));
                 }
             }
         });

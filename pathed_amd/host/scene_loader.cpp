@@ -1034,6 +1034,39 @@ PathedMaterial makeLambertian(const float diffuse[3], const float emit[3])
     return material;
 }
 
+// "phase": { "type": "henyey-greenstein", "g": "0.8" } on a medium of either kind (the reference's src/henyey_greenstein.cpp is
+// a stub and its parser knows no such key: this is the project's own).  "isotropic", and no key at all, leave no entry.
+static void parsePhase(const Json &mediumJson, int slot, FlatScene &scene)
+{
+    const Json &phaseJson = mediumJson["phase"];
+    if (!phaseJson.isObject()) { return; }
+    const std::string type = phaseJson["type"].isString() ? phaseJson["type"].asString() : "";
+    if (type == "isotropic") { return; }
+    if (type != "henyey-greenstein") { throw SceneLoadError("media: unknown phase function type \"" + type + "\" (isotropic, henyey-greenstein)"); }
+    FlatPhase phase;
+    phase.medium = slot;
+    if (!checkFloat(phaseJson["g"], &phase.g)) { throw SceneLoadError("media: a henyey-greenstein phase function needs a number (string) \"g\""); }
+    if (!std::isfinite(phase.g) || std::fabs(phase.g) > 0.99f) { throw SceneLoadError("media: a henyey-greenstein phase function needs |g| <= 0.99"); }
+    scene.phases.push_back(phase);
+}
+
+bool FlatScene::anisotropic() const
+{
+    for (const FlatPhase &phase : phases) {
+        if (!(std::fabs(phase.g) < PATHED_PHASE_ISOTROPIC_BELOW)) { return true; }
+    }
+    return false;
+}
+
+const PathedPhaseFunction *FlatScene::phaseDesc(size_t i) const
+{
+    FlatPhase &phase = const_cast<FlatScene *>(this)->phases[i];
+    phase.desc.struct_size = (uint32_t)sizeof(PathedPhaseFunction);
+    phase.desc.type = PATHED_PHASE_HENYEY_GREENSTEIN;
+    phase.desc.g = phase.g;
+    return &phase.desc;
+}
+
 const PathedGridMedium *FlatScene::gridDesc(size_t i) const
 {
     FlatGrid &grid = const_cast<FlatScene *>(this)->grids[i];
@@ -1177,6 +1210,7 @@ FlatScene loadScene(
                 PathedMedium placeholder;   // the slot the grid is set on; its sigmas are ignored from then on
                 std::memset(&placeholder, 0, sizeof placeholder);
                 context.mediumLookup[mediumJson["name"].asString()] = grid.medium;
+                parsePhase(mediumJson, grid.medium, scene);
                 scene.media.push_back(placeholder);
                 scene.grids.push_back(std::move(grid));
                 continue;
@@ -1187,6 +1221,7 @@ FlatScene loadScene(
             parseColor(mediumJson["sigma_s"], kBlack, medium.sigma_s);
             if (!mediumJson["name"].isString()) { throw SceneLoadError("media: a medium needs a string \"name\""); }
             context.mediumLookup[mediumJson["name"].asString()] = (int)scene.media.size();
+            parsePhase(mediumJson, (int)scene.media.size(), scene);
             scene.media.push_back(medium);
         }
     }

@@ -32,6 +32,14 @@ struct FlatGrid {
     std::vector<float> data;   // cells_x * cells_y * cells_z, index = (z * cells_y + y) * cells_x + x
 };
 
+// A medium's "phase" key (scene JSON, media of either kind): Henyey-Greenstein with mean cosine g on slot `medium`.  Like a
+// grid it is handed over on the created scene: pathed_hip_scene_set_medium_phase(scene, medium, phaseDesc(i)).
+struct FlatPhase {
+    int medium = -1;           // index into FlatScene::media
+    float g = 0.f;
+    PathedPhaseFunction desc;  // filled in by FlatScene::phaseDesc
+};
+
 // The contents of a .vol file (vol_parser.cpp's layout: "VOL", a version byte, uint32 encoding, cells x / y / z, channels,
 // six float bounds, then the cells as float32).  Throws SceneLoadError on a wrong header, a channel count other than 1, or
 // a length that is not the header plus cells x 4 bytes (the reference checks none of the three).
@@ -56,6 +64,7 @@ struct FlatScene {
     std::vector<PathedMaterial> materials;
     std::vector<PathedMedium> media;
     std::vector<FlatGrid> grids;
+    std::vector<FlatPhase> phases;
 
     bool hasEnv = false;
     PathedEnvLight env;
@@ -82,6 +91,10 @@ struct FlatScene {
     PathedSceneDesc desc() const;
     // grid i ready for pathed_hip_scene_set_grid_medium (same lifetime rule)
     const PathedGridMedium *gridDesc(size_t i) const;
+    // phase function i ready for pathed_hip_scene_set_medium_phase
+    const PathedPhaseFunction *phaseDesc(size_t i) const;
+    // some medium scatters anisotropically on the device (|g| at or above the kernels' threshold, pathed_amd/csrc/volume.h)
+    bool anisotropic() const;
 };
 
 struct SceneLoadError : std::runtime_error {

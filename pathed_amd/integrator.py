@@ -81,6 +81,7 @@ class HipScene:
     trace_blocks_per_cu, shade_kernel ("auto" | "per-slot" | "staged" | "fused" | "split" | "wave" | "hybrid"), stage_slots,
     unit_order ("auto" | "stripes" | "stripes-tiled" | "tiles"), node_format ("auto" | "wide" | "compressed" | "compressed8"), small_phase1 ("auto" | "valu" | "mfma").  `device=None` keeps the device of an earlier pathed_hip_init.
     `grids`: (medium slot, _capi.PathedGridMedium) pairs set on the created scene (LoadedScene.grids; see set_grid_medium).
+    `phases`: (medium slot, g) pairs, Henyey-Greenstein phase functions set on the created scene (LoadedScene.phases; see set_medium_phase).
     `prototypes`, `instances`: instanced geometry (pathed_hip_scene_create_instanced) -- prototypes [(first geom, geoms), ...]
     naming the description's last geoms, instances [(prototype, 12 floats: row-major 3 x 4), ...], or an instances.InstanceSet
     as `instances`; hits then carry virtual primitive ids, those of pathed_amd.flatten_instances of the same arguments.
@@ -88,7 +89,7 @@ class HipScene:
 
     BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2}  # PATHED_BVH_SAH_HOST / _LBVH_DEVICE / _PLOC_DEVICE
 
-    def __init__(self, desc_pointer, device=None, bvh_builder="sah", grids=(), prototypes=None, instances=None, **options):
+    def __init__(self, desc_pointer, device=None, bvh_builder="sah", grids=(), phases=(), prototypes=None, instances=None, **options):
         self._lib = _capi.load_hip()
         packed = _capi.PathedSceneOptions()
         packed.struct_size = C.sizeof(_capi.PathedSceneOptions)
@@ -121,6 +122,8 @@ class HipScene:
         self.height = int(desc_pointer.contents.camera.height)
         for medium_index, grid in grids:   # LoadedScene.grids: the voxel-grid media of the scene file
             self.set_grid_medium(medium_index, grid)
+        for medium_index, g in phases:   # LoadedScene.phases: the Henyey-Greenstein media of the scene file
+            self.set_medium_phase(medium_index, g)
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -573,6 +576,24 @@ class HipScene:
         out = np.zeros((u.shape[0], 3), dtype=np.float32)
         pointer = lambda array: array.ctypes.data_as(C.POINTER(C.c_float))
         _check(self._lib, self._lib.pathed_hip_debug_phase_samples(self._handle, u.shape[0], pointer(u), pointer(out)), "pathed_hip_debug_phase_samples")
+        return out
+
+    def set_medium_phase(self, medium_index, g, type_="henyey-greenstein"):
+        """The phase function of medium slot `medium_index` (pathed_hip_scene_set_medium_phase): "henyey-greenstein" with mean
+        cosine g (|g| <= 0.99; g > 0 scatters forward) or "isotropic".  Calling it again replaces the entry."""
+        phase = _capi.PathedPhaseFunction()
+        phase.struct_size = C.sizeof(_capi.PathedPhaseFunction)
+        phase.type = {"isotropic": _capi.PHASE_ISOTROPIC, "henyey-greenstein": _capi.PHASE_HENYEY_GREENSTEIN}[type_] if isinstance(type_, str) else int(type_)
+        phase.g = float(g)
+        _check(self._lib, self._lib.pathed_hip_scene_set_medium_phase(self._handle, int(medium_index), C.byref(phase)), "pathed_hip_scene_set_medium_phase")
+
+    def phase_hg(self, records):
+        """The device's Henyey-Greenstein sample and value (pathed_hip_debug_phase_hg): records (n, 9) = (g, w(3), u1, u2, wi(3))
+        -> (n, 4) float32: the direction sampled about w, then p(w, wi)."""
+        records = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 9)
+        out = np.zeros((records.shape[0], 4), dtype=np.float32)
+        pointer = lambda array: array.ctypes.data_as(C.POINTER(C.c_float))
+        _check(self._lib, self._lib.pathed_hip_debug_phase_hg(self._handle, records.shape[0], pointer(records), pointer(out)), "pathed_hip_debug_phase_hg")
         return out
 
     def set_integrator(self, name):

@@ -94,7 +94,10 @@ def main(argv=None):
         raise SystemExit("spp_per_launch must be >= 1")
 
     scene = LoadedScene(job["scene"], width, height, asset_root if asset_root is not None else job.get("asset_root"))
-    gpu = HipScene(scene.desc, device=local_rank, grids=scene.grids, prototypes=scene.prototypes, instances=scene.instances, bvh_builder=(lambda name: ("ploc" if world_size > 1 and scene.n_triangles > 1000000 else "sah") if name == "auto" else name)(job.get("bvh_builder", "auto")))
+    if any(not abs(g) < _capi.PHASE_ISOTROPIC_BELOW for _, g in scene.phases) and job["integrator"] == "VolumePathTracer":
+        # what the library refuses on such a scene stops the job here, by name, before a tree is built ("adaptive": above)
+        raise SystemExit("pathed_amd.run_job: the VolumePathTracer does not render a scene with a henyey-greenstein medium (the BasicVolumeIntegrator does)")
+    gpu = HipScene(scene.desc, device=local_rank, grids=scene.grids, phases=scene.phases, prototypes=scene.prototypes, instances=scene.instances, bvh_builder=(lambda name: ("ploc" if world_size > 1 and scene.n_triangles > 1000000 else "sah") if name == "auto" else name)(job.get("bvh_builder", "auto")))
     gpu.set_integrator(job["integrator"])
     host = _capi.load_host()
     stream = torch.cuda.current_stream().cuda_stream

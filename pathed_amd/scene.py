@@ -21,6 +21,12 @@ class LoadedScene:
             slot = C.c_int(-1)
             grid = self._host.pathed_host_scene_grid(self._handle, i, C.byref(slot))
             self.grids.append((slot.value, grid.contents))
+        # media with a "phase" key of type "henyey-greenstein": (medium slot, g) pairs for HipScene(..., phases=...)
+        self.phases = []
+        for i in range(self._host.pathed_host_scene_phase_count(self._handle)):
+            slot, g = C.c_int(-1), C.c_float(0.0)
+            self._host.pathed_host_scene_phase(self._handle, i, C.byref(slot), C.byref(g))
+            self.phases.append((slot.value, g.value))
         # "instance" / "instanced" models: (prototypes, instances) as HipScene(..., prototypes=, instances=) and
         # pathed_amd.flatten_instances take them -- one level, nesting resolved and emissive faces baked by the loader; None = flat
         self.prototypes, self.instances = None, None

@@ -2,10 +2,12 @@
 """Msamples/s of a list of scenes through the C ABI, one process, interleaved repeats; variants are PathedSceneOptions
 (the product library reads no environment variable), images of the variants of a scene compared bit for bit.
 
-    tools/rates.py [--spp 256] [--repeats 3] [--scenes C2,ON,GGX,GL,GLASS,C3,C4,C5,VOL,SMOKE,VOL-MS,SMOKE-MS] [--variants default,generic]
+    tools/rates.py [--spp 256] [--repeats 3] [--scenes C2,ON,GGX,GL,GLASS,C3,C4,C5,VOL,SMOKE,VOL-MS,SMOKE-MS,VOL-HG,SMOKE-HG] [--variants default,generic]
                    [--lib other.so]   # the second column from another build of the library (a child process per library)
 
 Variants: name or name=opt:value+opt:value, e.g. "wave=shade_kernel:wave", "front=shade_kernel:per-slot".
+"hg-idle" gives the scene one more medium slot that no surface references, Henyey-Greenstein at g = 0.8: BasicVolumeIntegrator
+then runs the anisotropic kernels on the same paths (the same image), which shows the cost of their code alone.
 """
 import argparse
 import json
@@ -32,6 +34,8 @@ SCENES = {
     "SMOKE": ("scenes/cornell-smoke.json", 1024, 1024, "VolumePathTracer"),   # a voxel-grid medium (k_path_volume_grid)
     "VOL-MS": ("scenes/cornell-medium.json", 1024, 1024, "BasicVolumeIntegrator"),   # multiple scattering (k_path_scatter)
     "SMOKE-MS": ("scenes/cornell-smoke.json", 1024, 1024, "BasicVolumeIntegrator"),   # ... in a voxel grid (k_path_scatter_grid)
+    "VOL-HG": ("scenes/cornell-medium.json", 1024, 1024, "BasicVolumeIntegrator", [(0, 0.8)]),   # Henyey-Greenstein, g = 0.8 (k_path_aniso)
+    "SMOKE-HG": ("scenes/cornell-smoke-hg.json", 1024, 1024, "BasicVolumeIntegrator"),   # ... the plume at g = 0.8 (k_path_aniso_grid)
 }
 PRESETS = {
     "default": {},
@@ -39,7 +43,23 @@ PRESETS = {
     "wave": {"shade_kernel": "wave"},
     "front": {"shade_kernel": "per-slot"},
     "bvh": {"intersector": "bvh"},
+    "hg-idle": {"idle_hg": 80},   # (hundredths of g)
 }
+
+
+def with_idle_slot(desc_pointer):
+    """(a copy of the scene description with one more medium slot that no surface references, what keeps it alive)"""
+    import ctypes as C
+    from pathed_amd import _capi
+    desc = _capi.PathedSceneDesc.from_buffer_copy(desc_pointer.contents)
+    media = (_capi.PathedMedium * (desc.n_media + 1))()
+    for i in range(desc.n_media):
+        media[i] = desc_pointer.contents.media[i]
+    media[desc.n_media].sigma_t[:] = [1.0, 1.0, 1.0]
+    media[desc.n_media].sigma_s[:] = [1.0, 1.0, 1.0]
+    desc.media = C.cast(media, C.POINTER(_capi.PathedMedium))
+    desc.n_media += 1
+    return C.pointer(desc), (desc, media)
 
 
 def parse_variant(text):
@@ -58,14 +78,21 @@ def run(args):
     from pathed_amd.scene import LoadedScene
     rows = []
     for key in args.scenes.split(","):
-        path, w, h, integrator = SCENES[key]
+        path, w, h, integrator = SCENES[key][:4]
         scene = LoadedScene(path, w, h)
+        phases = list(scene.phases) + (SCENES[key][4] if len(SCENES[key]) > 4 else [])
+        keep = []
         builder = args.builder or ("ploc" if scene.n_triangles > 1000000 else "sah")
         variants = {}
         for text in args.variants.split(","):
             name, options = parse_variant(text)
             try:
-                variants[name] = HipScene(scene.desc, device=0, bvh_builder=builder, grids=scene.grids, **options)
+                desc, own = scene.desc, list(phases)
+                if "idle_hg" in options:
+                    desc, alive = with_idle_slot(scene.desc)
+                    keep.append(alive)
+                    own.append((int(desc.contents.n_media) - 1, options.pop("idle_hg") / 100.0))
+                variants[name] = HipScene(desc, device=0, bvh_builder=builder, grids=scene.grids, phases=own, **options)
                 variants[name].set_integrator(integrator)
             except Exception as error:   # a variant that does not apply to this scene
                 print("%s %s: %s" % (key, name, error), flush=True)
