@@ -614,6 +614,15 @@ int validate(const PathedSceneDesc *desc)
 // experiments and long-lived processes.
 const int kMaxChunksPerPass = 256;
 
+// the statistics buffer, zeroed when it is made
+int ensureStats(PathedScene *scene)
+{
+    if (scene->stats.ptr) { return PATHED_OK; }
+    HIP_TRY(scene->stats.allocate(kStatCount));
+    HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
+    return PATHED_OK;
+}
+
 int ensureRenderState(PathedScene *scene, int nSlots, size_t chunkEntries)
 {
     if (scene->nSlots < nSlots || !scene->rayO.ptr) {   // capacity: a call that wants fewer slots uses a prefix
@@ -656,13 +665,9 @@ int ensureRenderState(PathedScene *scene, int nSlots, size_t chunkEntries)
         const size_t waves = (size_t)scene->traceGrid * kWavesPerBlock;
         HIP_TRY(scene->suspendMask.allocate((size_t)scene->pools * waves));
         HIP_TRY(scene->suspendData.allocate((size_t)scene->pools * waves * (size_t)(kSaveWords + scene->maxStack) * 64));
-        const size_t overflowRows = (size_t)(scene->maxStack > scene->stackRows ? scene->maxStack - scene->stackRows : 0);
-        HIP_TRY(scene->stackOverflow.allocate((size_t)scene->pools * (size_t)scene->traceGrid * kBlock * (overflowRows ? overflowRows : 1)));
+        HIP_TRY(scene->stackOverflow.allocate((size_t)scene->pools * stackSpillInts((size_t)scene->traceGrid * kBlock, scene->maxStack, scene->stackRows)));
     }
-    if (!scene->stats.ptr) {
-        HIP_TRY(scene->stats.allocate(kStatCount));
-        HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
-    }
+    if (const int code = ensureStats(scene)) { return code; }
     if (!scene->hostRemaining) {
         HIP_TRY(hipHostMalloc((void **)&scene->hostRemaining, kMaxPools * 32 * sizeof(unsigned int), hipHostMallocDefault));
     }
@@ -673,10 +678,23 @@ int ensureRenderState(PathedScene *scene, int nSlots, size_t chunkEntries)
 // constant: f is called with std::true_type or std::false_type and is compiled for both, so a rung that exists for both values
 // of a flag is one line inside it.  A rung that exists for one value only is written with that value, outside.  What the
 // ladders name is what the library contains (tests/test_kernel_resources.py counts it).
+// withStackRows does the same for a kernel's STACK argument: f is called with std::integral_constant<int, 8 | 16 | 22>, chosen
+// by stackRowsFor (scene_tables.h), and returns what f returns.  Inside it the launch takes its LDS bytes, stackLdsBytes(STACK),
+// from that same constant, so a kernel cannot be started with the stack of another.
 template <typename F>
 void withBool(bool value, F &&f)
 {
     if (value) { f(std::true_type{}); } else { f(std::false_type{}); }
+}
+
+template <typename F>
+auto withStackRows(int rows, F &&f)
+{
+    switch (stackRowsFor(rows)) {
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    default: return f(std::integral_constant<int, 22>{});
+    }
 }
 
 // k_trace<STACK, LDS_SCENE, COUNT, LISTS, SPHERES, FORMAT>: every rung with and without counting
@@ -707,13 +725,10 @@ void launchTraceInstanced(PathedScene *scene, const RenderParams &params, hipStr
     // block's worth for the shadow list
     const int wanted = 2 * params.nSlots / kBlock;
     const dim3 grid((unsigned)(wanted < scene->traceGrid ? (wanted > 0 ? wanted : 1) : scene->traceGrid)), block(kBlock);
-    const size_t lds = (size_t)(scene->stackRows + 1) * kBlock * sizeof(int);
     withBool(scene->countMode, [&](auto COUNT) {
-        switch (scene->stackRows) {
-        case 8: hipLaunchKernelGGL((k_trace_instanced<8, COUNT>), grid, block, lds, stream, params, scene->instanceSet); break;
-        case 16: hipLaunchKernelGGL((k_trace_instanced<16, COUNT>), grid, block, lds, stream, params, scene->instanceSet); break;
-        default: hipLaunchKernelGGL((k_trace_instanced<22, COUNT>), grid, block, lds, stream, params, scene->instanceSet); break;
-        }
+        withStackRows(scene->stackRows, [&](auto STACK) {
+            hipLaunchKernelGGL((k_trace_instanced<STACK, COUNT>), grid, block, stackLdsBytes(STACK), stream, params, scene->instanceSet);
+        });
     });
 }
 
@@ -727,11 +742,7 @@ void launchTrace(PathedScene *scene, const RenderParams &params, hipStream_t str
         withBool(scene->countMode, [&](auto COUNT) { hipLaunchKernelGGL((k_trace_small<COUNT>), grid, block, 0, stream, params, scene->smallTris); });
         return;
     }
-    switch (scene->stackRows) {
-    case 8: launchTraceStack<8>(scene, params, stream); break;
-    case 16: launchTraceStack<16>(scene, params, stream); break;
-    default: launchTraceStack<22>(scene, params, stream); break;
-    }
+    withStackRows(scene->stackRows, [&](auto STACK) { launchTraceStack<STACK>(scene, params, stream); });
 }
 
 #if defined(PATHED_EXPERIMENTS) && PATHED_EXPERIMENTS
@@ -896,7 +907,7 @@ void configureTrace(PathedScene *scene)
     }
 
     // per-thread traversal stacks + the waves' ray staging rows (2 float4 per thread)
-    const size_t stackBytes = (size_t)(scene->stackRows + 1) * kBlock * sizeof(int) + (size_t)2 * kBlock * kCardRounds * sizeof(float4)
+    const size_t stackBytes = stackLdsBytes(scene->stackRows) + (size_t)2 * kBlock * kCardRounds * sizeof(float4)
         + (scene->splitShade ? (size_t)kWavesPerBlock * 2 * 128 * sizeof(unsigned int) : 0);
     const size_t sceneBytes = (size_t)scene->device.nNodes * 128 + (size_t)scene->device.nTris * 48;
     // stage the BVH in LDS when it is small enough to leave >= 4 blocks per CU
@@ -2310,10 +2321,7 @@ static int persistentPass(PathedScene *scene, const Pass &pass, int blocksPerCu,
         scene->chunkCapacity = pass.bufferUnits();
     }
     if (!scene->counters.ptr) { HIP_TRY(scene->counters.allocate(kMaxPools * kCtrCount)); }
-    if (!scene->stats.ptr) {
-        HIP_TRY(scene->stats.allocate(kStatCount));
-        HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
-    }
+    if (const int code = ensureStats(scene)) { return code; }
 
     // the grid: blocksPerCu blocks per CU, or fewer when the pass has fewer than 64 units per wave
     unsigned long long blocks = (unsigned long long)scene->computeUnits * blocksPerCu;
@@ -2325,8 +2333,7 @@ static int persistentPass(PathedScene *scene, const Pass &pass, int blocksPerCu,
     RenderParams params;
     std::memset(&params, 0, sizeof params);
     if (maxStack > 0) {
-        const size_t overflowRows = (size_t)(maxStack > ldsRows ? maxStack - ldsRows : 0);
-        const size_t overflowInts = (size_t)blocks * kBlock * (overflowRows ? overflowRows : 1);
+        const size_t overflowInts = stackSpillInts((size_t)blocks * kBlock, maxStack, ldsRows);
         if (scene->volumeOverflow.count < overflowInts) { HIP_TRY(scene->volumeOverflow.allocate(overflowInts)); }
         params.stackOverflow = scene->volumeOverflow.ptr;
         params.maxStack = maxStack;
@@ -2444,110 +2451,58 @@ static int renderPassFused(PathedScene *scene, const Pass &pass)
     return code;
 }
 
-// The volume integrator (k_path_volume).  small: <= 64 triangles, <= 16 spheres go through the all-triangles intersector
-// (kernarg pair records), no tree walk.
+// The volume integrators (kernels.h, volume.h).  small: <= 64 triangles, <= 16 spheres go through the all-triangles intersector
+// (kernarg pair records), no tree walk, and take the 8-row form of every family.
 static int renderPassVolume(PathedScene *scene, const Pass &pass)
 {
-    if (pass.nList > 0) {
-        // a pixel list: k_list_volume<SMALL, GRID, MULTI> (kernels.h), the generic shape with 8 (small) or 22 stack rows in LDS
-        const bool small = scene->bruteForce;
-        const int rows = small ? 8 : 22;
-        return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, rows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
-            const size_t lds = (size_t)(rows + 1) * kBlock * sizeof(int);
-            params.smallQuads = 0;
-            params.smallKappaT = scene->smallLayout.kappaT;
-            params.scene.leafTris = scene->leafTris.ptr;
-            const bool grids = !scene->gridsHost.empty();
-            const bool multi = scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME;
-            withBool(small, [&](auto SMALL) { withBool(grids, [&](auto GRID) { withBool(multi, [&](auto MULTI) {
-                hipLaunchKernelGGL((k_list_volume<SMALL, GRID, MULTI>), grid, dim3(kBlock), lds, stream, params, scene->smallTris);
-            }); }); });
-        });
-    }
-    if (scene->anisotropic && scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME) {
-        // Henyey-Greenstein media: k_path_aniso / k_path_aniso_grid<STACK, SMALL>, the scatter family's shape with the per-slot g
-        // table as a third argument; a tree scene takes the 22-row form whatever its own row count
-        const bool small = scene->bruteForce;
-        const int rows = small ? 8 : 22;
-        return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, rows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
-            const size_t lds = (size_t)(rows + 1) * kBlock * sizeof(int);
-            params.smallQuads = 0;
-            params.smallKappaT = scene->smallLayout.kappaT;
-            params.scene.leafTris = scene->leafTris.ptr;
-            const float *table = scene->phaseG.ptr;
-            const bool grids = !scene->gridsHost.empty();
-            const auto run = [&](void (*kernel)(RenderParams, SmallTris, const float *)) {
-                hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, scene->smallTris, table);
-            };
-            if (small) { run(grids ? k_path_aniso_grid<8, true> : k_path_aniso<8, true>); }
-            else { run(grids ? k_path_aniso_grid<22, false> : k_path_aniso<22, false>); }
-        });
-    }
-    return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, scene->stackRows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
-        const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
-        const bool small = scene->bruteForce;
-        const size_t lds = (size_t)((small ? 8 : scene->stackRows) + 1) * kBlock * sizeof(int)
-            + (ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0);
-        // scenes made of quads: phase 1 over the item records (small_items.h), phase 2 over the item-ordered triangles
-        const bool quads = small && ldsMaterials && scene->smallLayout.nQuads > 0;
+    const bool small = scene->bruteForce, list = pass.nList > 0, grids = !scene->gridsHost.empty();
+    const bool multi = scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME, aniso = multi && scene->anisotropic && !list;
+    const bool ldsMaterials = scene->device.nMaterials <= kMaxLdsMaterials;
+    // the generic families -- pixel lists, multiple scattering, voxel grids: the generic set, pair-of-triangles phase 1 over the
+    // leaf-ordered triangles, the material table read from memory.  Only k_path_volume itself narrows the set, keeps the
+    // materials in LDS and, in scenes made of quads, runs phase 1 over the item records and phase 2 over the item-ordered
+    // triangles (small_items.h): QUADS and the narrowed set exist for small scenes with the materials in LDS only
+    const bool generic = list || multi || grids;
+    const bool quads = !generic && small && ldsMaterials && scene->smallLayout.nQuads > 0;
+    // a tree scene's pixel lists and Henyey-Greenstein media take the 22-row form whatever its own row count
+    const int rows = small ? 8 : (list || aniso) ? 22 : scene->stackRows;
+    return persistentPass(scene, pass, PATHED_VOLUME_WAVES, scene->maxStack, rows, [&](RenderParams &params, dim3 grid, hipStream_t stream) {
         params.smallQuads = quads ? scene->smallLayout.nQuads : 0;
         params.smallKappaT = scene->smallLayout.kappaT;
-        if (quads) { params.scene.leafTris = scene->itemTris.ptr; }
-
-        // k_path_volume<LDS_MATERIALS, STACK, SMALL, TRAITS, QUADS>: the narrowed set and QUADS exist for small scenes with the
-        // materials in LDS only
-        const auto run = [&](void (*kernel)(RenderParams, SmallTris)) {
-            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, params, quads ? scene->smallItems : scene->smallTris);
+        params.scene.leafTris = quads ? scene->itemTris.ptr : scene->leafTris.ptr;
+        const SmallTris &records = quads ? scene->smallItems : scene->smallTris;
+        const size_t materialBytes = !generic && ldsMaterials ? (size_t)scene->device.nMaterials * sizeof(DMaterial) : 0;
+        const auto choose = [&](auto STACK, auto SMALL) {
+            const auto run = [&](auto kernel, auto... more) {
+                hipLaunchKernelGGL(kernel, grid, dim3(kBlock), stackLdsBytes(STACK) + materialBytes, stream, params, records, more...);
+            };
+            if (list) {
+                // k_list_volume<SMALL, GRID, MULTI>
+                withBool(grids, [&](auto GRID) { withBool(multi, [&](auto MULTI) { run(k_list_volume<SMALL, GRID, MULTI>); }); });
+            } else if (aniso) {
+                // k_path_aniso / k_path_aniso_grid<STACK, SMALL>: the scatter family's shape with the per-slot g table as a third argument;
+                // a tree scene's only form has 22 rows (`rows` above)
+                if constexpr (SMALL || STACK == 22) { run(grids ? k_path_aniso_grid<STACK, SMALL> : k_path_aniso<STACK, SMALL>, (const float *)scene->phaseG.ptr); }
+            } else if (multi) {
+                // BasicVolumeIntegrator: k_path_scatter / k_path_scatter_grid<STACK, SMALL>
+                run(grids ? k_path_scatter_grid<STACK, SMALL> : k_path_scatter<STACK, SMALL>);
+            } else if (grids) {
+                run(k_path_volume_grid<STACK, SMALL>);
+            } else if constexpr (SMALL) {
+                // k_path_volume<LDS_MATERIALS, STACK, SMALL, TRAITS, QUADS>
+                if (ldsMaterials && scene->traits.lambertianGlassContainer) {   // the reference's own volume scene kinds
+                    withBool(quads, [&](auto QUADS) { run(k_path_volume<true, STACK, true, TraitsLambertianGlassContainer, QUADS>); });
+                } else if (quads) {
+                    run(k_path_volume<true, STACK, true, TraitsAll, true>);
+                } else {
+                    withBool(ldsMaterials, [&](auto LDS_MATERIALS) { run(k_path_volume<LDS_MATERIALS, STACK, true>); });
+                }
+            } else {
+                withBool(ldsMaterials, [&](auto LDS_MATERIALS) { run(k_path_volume<LDS_MATERIALS, STACK, false>); });
+            }
         };
-        if (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME) {
-            // BasicVolumeIntegrator: k_path_scatter / k_path_scatter_grid<STACK, SMALL>, the generic set, pair-of-triangles
-            // phase 1, the material table read from memory (eight instantiations in all)
-            params.smallQuads = 0;
-            params.scene.leafTris = scene->leafTris.ptr;
-            const size_t scatterLds = (size_t)((small ? 8 : scene->stackRows) + 1) * kBlock * sizeof(int);
-            const bool grids = !scene->gridsHost.empty();
-            const auto runScatter = [&](void (*plain)(RenderParams, SmallTris), void (*withGrids)(RenderParams, SmallTris)) {
-                hipLaunchKernelGGL(grids ? withGrids : plain, grid, dim3(kBlock), scatterLds, stream, params, scene->smallTris);
-            };
-            if (small) { runScatter(k_path_scatter<8, true>, k_path_scatter_grid<8, true>); }
-            else {
-                switch (scene->stackRows) {
-                case 8: runScatter(k_path_scatter<8, false>, k_path_scatter_grid<8, false>); break;
-                case 16: runScatter(k_path_scatter<16, false>, k_path_scatter_grid<16, false>); break;
-                default: runScatter(k_path_scatter<22, false>, k_path_scatter_grid<22, false>); break;
-                }
-            }
-        } else if (!scene->gridsHost.empty()) {
-            // a voxel-grid medium: the generic set, pair-of-triangles phase 1, the material table read from memory (four
-            // instantiations in all; params.smallQuads is 0 where no instantiation reads the item records)
-            params.smallQuads = 0;
-            params.scene.leafTris = scene->leafTris.ptr;
-            const size_t gridLds = (size_t)((small ? 8 : scene->stackRows) + 1) * kBlock * sizeof(int);
-            const auto runGrid = [&](void (*kernel)(RenderParams, SmallTris)) {
-                hipLaunchKernelGGL(kernel, grid, dim3(kBlock), gridLds, stream, params, scene->smallTris);
-            };
-            if (small) { runGrid(k_path_volume_grid<8, true>); }
-            else {
-                switch (scene->stackRows) {
-                case 8: runGrid(k_path_volume_grid<8, false>); break;
-                case 16: runGrid(k_path_volume_grid<16, false>); break;
-                default: runGrid(k_path_volume_grid<22, false>); break;
-                }
-            }
-        } else if (small && ldsMaterials && scene->traits.lambertianGlassContainer) {   // the reference's own volume scene kinds
-            withBool(quads, [&](auto QUADS) { run(k_path_volume<true, 8, true, TraitsLambertianGlassContainer, QUADS>); });
-        } else if (quads) {
-            run(k_path_volume<true, 8, true, TraitsAll, true>);
-        } else {
-            withBool(ldsMaterials, [&](auto LDS_MATERIALS) {
-                if (small) { run(k_path_volume<LDS_MATERIALS, 8, true>); return; }
-                switch (scene->stackRows) {
-                case 8: run(k_path_volume<LDS_MATERIALS, 8, false>); break;
-                case 16: run(k_path_volume<LDS_MATERIALS, 16, false>); break;
-                default: run(k_path_volume<LDS_MATERIALS, 22, false>); break;
-                }
-            });
-        }
+        if (small) { choose(std::integral_constant<int, 8>{}, std::true_type{}); }
+        else { withStackRows(rows, [&](auto STACK) { choose(STACK, std::false_type{}); }); }
     });
 }
 
@@ -2685,12 +2640,8 @@ static int renderPass(PathedScene *scene, const Pass &pass)
         q.suspendMask = scene->bruteForce ? nullptr : scene->suspendMask.ptr + (size_t)h * traceWaves;
         q.suspendData = scene->bruteForce ? nullptr
             : scene->suspendData.ptr + (size_t)h * traceWaves * (size_t)(kSaveWords + scene->maxStack) * 64;
-        {
-            const size_t overflowRows = (size_t)(scene->maxStack > scene->stackRows ? scene->maxStack - scene->stackRows : 0);
-            q.stackOverflow = scene->bruteForce ? nullptr
-                : scene->stackOverflow.ptr + (size_t)h * (size_t)scene->traceGrid * kBlock * (overflowRows ? overflowRows : 1);
-            q.maxStack = scene->maxStack;
-        }
+        q.stackOverflow = scene->bruteForce ? nullptr : scene->stackOverflow.ptr + (size_t)h * stackSpillInts((size_t)scene->traceGrid * kBlock, scene->maxStack, scene->stackRows);
+        q.maxStack = scene->maxStack;
         q.nSlots = slotsPerPool;
         // local rays (per-slot shade kernel only: the staged and split stages of the experiments build do not know them)
         q.localCount = (!scene->stagedShade && !scene->splitShade) ? scene->localCount : 0;
@@ -2826,10 +2777,7 @@ static int renderPass(PathedScene *scene, const Pass &pass)
 static int launchFeatures(PathedScene *scene, uint64_t seed, uint32_t begin, uint32_t count, int startBounce, int lastBounce,
                           bool reference, float *accum, const FeatureBuffers &out, hipStream_t stream)
 {
-    if (!scene->stats.ptr) {
-        HIP_TRY(scene->stats.allocate(kStatCount));
-        HIP_TRY(hipMemset(scene->stats.ptr, 0, kStatCount * sizeof(unsigned long long)));
-    }
+    if (const int code = ensureStats(scene)) { return code; }
     // a wave per 8 x 8 tile; the grid is what the kernel's register budget keeps resident (four blocks per CU) or fewer
     const unsigned long long tiles = (unsigned long long)((scene->width + 7) / 8) * (unsigned long long)((scene->height + 7) / 8);
     unsigned long long blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -2839,8 +2787,7 @@ static int launchFeatures(PathedScene *scene, uint64_t seed, uint32_t begin, uin
 
     RenderParams params;
     std::memset(&params, 0, sizeof params);
-    const size_t overflowRows = (size_t)(scene->maxStack > scene->stackRows ? scene->maxStack - scene->stackRows : 0);
-    const size_t overflowInts = (size_t)blocks * kBlock * (overflowRows ? overflowRows : 1);
+    const size_t overflowInts = stackSpillInts((size_t)blocks * kBlock, scene->maxStack, scene->stackRows);
     if (scene->volumeOverflow.count < overflowInts) { HIP_TRY(scene->volumeOverflow.allocate(overflowInts)); }
     params.stackOverflow = scene->volumeOverflow.ptr;
     params.maxStack = scene->maxStack;
@@ -2863,13 +2810,8 @@ static int launchFeatures(PathedScene *scene, uint64_t seed, uint32_t begin, uin
         (void)hipEventRecord(scene->traceEvents.start[timed], stream);
     }
     const dim3 grid((unsigned)blocks), block(kBlock);
-    const size_t lds = (size_t)(scene->stackRows + 1) * kBlock * sizeof(int);
     withBool(reference, [&](auto REFERENCE) {
-        switch (scene->stackRows) {
-        case 8: hipLaunchKernelGGL((k_features<8, REFERENCE>), grid, block, lds, stream, params, out); break;
-        case 16: hipLaunchKernelGGL((k_features<16, REFERENCE>), grid, block, lds, stream, params, out); break;
-        default: hipLaunchKernelGGL((k_features<22, REFERENCE>), grid, block, lds, stream, params, out); break;
-        }
+        withStackRows(scene->stackRows, [&](auto STACK) { hipLaunchKernelGGL((k_features<STACK, REFERENCE>), grid, block, stackLdsBytes(STACK), stream, params, out); });
     });
     if (timed >= 0) { (void)hipEventRecord(scene->traceEvents.stop[timed], stream); }
     scene->traceLaunchesAll++;
@@ -3031,6 +2973,56 @@ static int renderCall(PathedScene *scene, uint64_t seed, uint32_t spp_begin, uin
     return PATHED_OK;
 }
 
+// The test and measurement hooks that are one launch of a thread per record: selects the scene's device, uploads the float
+// arrays of `inputs`, makes and zeroes the device arrays of `outputs`, calls launch(grid, in, out) -- a block per kBlock of the n
+// records; in and out hold the DeviceBuffers in the order given --, waits for the kernel and downloads the outputs.
+struct HookInput { const float *host; size_t count; };
+template <typename T> struct HookOutput { T *host; size_t count; };
+
+template <typename T, typename Launch>
+static int recordHook(PathedScene *scene, size_t n, std::initializer_list<HookInput> inputs, std::initializer_list<HookOutput<T>> outputs, Launch launch)
+{
+    SELECT_DEVICE(scene);
+    std::vector<DeviceBuffer<float>> in(inputs.size());
+    std::vector<DeviceBuffer<T>> out(outputs.size());
+    size_t k = 0;
+    for (const HookInput &input : inputs) {
+        HIP_TRY(in[k].allocate(input.count));
+        HIP_TRY(hipMemcpy(in[k++].ptr, input.host, input.count * sizeof(float), hipMemcpyHostToDevice));
+    }
+    k = 0;
+    for (const HookOutput<T> &output : outputs) {
+        HIP_TRY(out[k].allocate(output.count));
+        HIP_TRY(hipMemset(out[k++].ptr, 0, output.count * sizeof(T)));
+    }
+    launch(dim3((unsigned)((n + kBlock - 1) / kBlock)), in, out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    k = 0;
+    for (const HookOutput<T> &output : outputs) { HIP_TRY(hipMemcpy(output.host, out[k++].ptr, output.count * sizeof(T), hipMemcpyDeviceToHost)); }
+    return PATHED_OK;
+}
+
+// the candidate hooks' records (an origin, two directions and a far bound: 10 floats) padded to whole blocks, since every lane
+// reads one (and issues the matrix instructions); a padding record's directions are +z
+static std::vector<float> paddedRays(const float *rays, size_t n)
+{
+    const size_t padded = (n + kBlock - 1) / kBlock * kBlock;
+    std::vector<float> host(padded * 10, 0.f);
+    std::memcpy(host.data(), rays, n * 10 * sizeof(float));
+    for (size_t i = n; i < padded; i++) { host[10 * i + 5] = 1.f; host[10 * i + 8] = 1.f; }
+    return host;
+}
+
+// ... and the four counts of an item list they report
+static void fillLayout(int32_t *layout, const SmallItemsLayout &list)
+{
+    layout[0] = list.nQuads;
+    layout[1] = list.nLone;
+    layout[2] = list.shadowQuadPairs;
+    layout[3] = list.shadowLonePairs;
+}
+
 extern "C" {
 
 int pathed_hip_render_device(PathedScene *scene, uint64_t seed,
@@ -3077,6 +3069,30 @@ int pathed_hip_render_moments(PathedScene *scene, uint64_t seed, uint32_t spp_be
     return PATHED_OK;
 }
 
+// The per-block partial sums of k_noise / k_noise_select, read back and folded in block order (the double sum and the float
+// maximum depend on it) into `out`; `host` keeps them for the caller.  Returns when the kernel before it on `stream` has.
+static int reduceNoisePartials(const DeviceBuffer<NoisePartial> &partials, int nPixels, hipStream_t stream, std::vector<NoisePartial> &host, PathedNoise *out)
+{
+    host.resize(partials.count);
+    HIP_TRY(hipMemcpyAsync(host.data(), partials.ptr, host.size() * sizeof(NoisePartial), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    double sum = 0.0;
+    float maxError = 0.f;
+    uint64_t above = 0;
+    uint32_t invalid = 0;
+    for (const NoisePartial &partial : host) {
+        sum += partial.sum;
+        if (partial.maxError > maxError) { maxError = partial.maxError; }
+        above += partial.above;
+        invalid += partial.invalid;
+    }
+    out->invalid_pixels = invalid;
+    out->mean_error = sum / (double)nPixels;
+    out->max_error = (double)maxError;
+    out->pixels_above = above;
+    return PATHED_OK;
+}
+
 int pathed_hip_noise_estimate_device(PathedScene *scene, const float *d_rgb_sum, const float *d_rgb_sq_sum, uint32_t n_samples,
                                      float floor, float threshold, float *d_error, PathedNoise *out, void *stream_handle)
 {
@@ -3102,24 +3118,8 @@ int pathed_hip_noise_estimate_device(PathedScene *scene, const float *d_rgb_sum,
     params.partials = partials.ptr;
     hipLaunchKernelGGL(k_noise, dim3(blocks), dim3(kBlock), 0, stream, params);
     HIP_TRY(hipGetLastError());
-    std::vector<NoisePartial> host(blocks);
-    HIP_TRY(hipMemcpyAsync(host.data(), partials.ptr, blocks * sizeof(NoisePartial), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    double sum = 0.0;
-    float maxError = 0.f;
-    uint64_t above = 0;
-    uint32_t invalid = 0;
-    for (const NoisePartial &partial : host) {   // in block order
-        sum += partial.sum;
-        if (partial.maxError > maxError) { maxError = partial.maxError; }
-        above += partial.above;
-        invalid += partial.invalid;
-    }
-    out->invalid_pixels = invalid;
-    out->mean_error = sum / (double)nPixels;
-    out->max_error = (double)maxError;
-    out->pixels_above = above;
-    return PATHED_OK;
+    std::vector<NoisePartial> host;
+    return reduceNoisePartials(partials, nPixels, stream, host, out);
 }
 
 int pathed_hip_select_pixels_device(PathedScene *scene, const float *d_rgb_sum, const float *d_rgb_sq_sum, const uint32_t *d_count,
@@ -3152,22 +3152,10 @@ int pathed_hip_select_pixels_device(PathedScene *scene, const float *d_rgb_sum, 
     params.selected = selected.ptr;
     hipLaunchKernelGGL(k_noise_select, dim3(blocks), dim3(kBlock), 0, stream, params);
     HIP_TRY(hipGetLastError());
-    std::vector<NoisePartial> host(blocks);
-    HIP_TRY(hipMemcpyAsync(host.data(), partials.ptr, blocks * sizeof(NoisePartial), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    double sum = 0.0;
-    float maxError = 0.f;
-    uint64_t above = 0;
-    uint32_t invalid = 0;
+    std::vector<NoisePartial> host;
+    if (const int code = reduceNoisePartials(partials, nPixels, stream, host, out)) { return code; }
     std::vector<uint32_t> hostOffsets((size_t)blocks + 1, 0u);
-    for (unsigned int b = 0; b < blocks; b++) {   // in block order
-        const NoisePartial &partial = host[b];
-        sum += partial.sum;
-        if (partial.maxError > maxError) { maxError = partial.maxError; }
-        above += partial.above;
-        invalid += partial.invalid;
-        hostOffsets[b + 1] = hostOffsets[b] + partial.unused;   // the block's selected pixels
-    }
+    for (unsigned int b = 0; b < blocks; b++) { hostOffsets[b + 1] = hostOffsets[b] + host[b].unused; }   // the block's selected pixels
     const uint32_t total = hostOffsets[blocks];
     if (total > 0u) {
         HIP_TRY(hipMemcpyAsync(offsets.ptr, hostOffsets.data(), hostOffsets.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
@@ -3176,10 +3164,6 @@ int pathed_hip_select_pixels_device(PathedScene *scene, const float *d_rgb_sum, 
         HIP_TRY(hipStreamSynchronize(stream));
     }
     *n_list = total;
-    out->invalid_pixels = invalid;
-    out->mean_error = sum / (double)nPixels;
-    out->max_error = (double)maxError;
-    out->pixels_above = above;
     return PATHED_OK;
 }
 
@@ -3241,18 +3225,15 @@ int pathed_hip_render(PathedScene *scene, uint64_t seed,
     if (!scene || !accum_rgb_sum) { return fail(PATHED_E_INVALID, "null scene or accumulation buffer"); }
     SELECT_DEVICE(scene);
     const size_t count = (size_t)3 * scene->width * scene->height;
-    float *deviceAccum = nullptr;
-    HIP_TRY(hipMalloc((void **)&deviceAccum, count * sizeof(float)));
-    hipError_t status = hipMemset(deviceAccum, 0, count * sizeof(float));
-    if (status != hipSuccess) { (void)hipFree(deviceAccum); return fail(PATHED_E_DEVICE, hipGetErrorString(status)); }
+    DeviceBuffer<float> deviceAccum;
+    HIP_TRY(deviceAccum.allocate(count));
+    HIP_TRY(hipMemset(deviceAccum.ptr, 0, count * sizeof(float)));
 
-    const int code = pathed_hip_render_device(scene, seed, spp_begin, spp_count, start_bounce, last_bounce, deviceAccum, nullptr, 1);
-    if (code != PATHED_OK) { (void)hipFree(deviceAccum); return code; }
+    const int code = pathed_hip_render_device(scene, seed, spp_begin, spp_count, start_bounce, last_bounce, deviceAccum.ptr, nullptr, 1);
+    if (code != PATHED_OK) { return code; }
 
     std::vector<float> host(count);
-    status = hipMemcpy(host.data(), deviceAccum, count * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(deviceAccum);
-    if (status != hipSuccess) { return fail(PATHED_E_DEVICE, hipGetErrorString(status)); }
+    HIP_TRY(hipMemcpy(host.data(), deviceAccum.ptr, count * sizeof(float), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < count; i++) { accum_rgb_sum[i] += host[i]; }
     return PATHED_OK;
 }
@@ -3312,56 +3293,36 @@ int pathed_hip_trace(PathedScene *scene, const float *rays, size_t n, int any_hi
     if (n > (size_t)1 << 28) { return fail(PATHED_E_INVALID, "too many rays in one call"); }
     SELECT_DEVICE(scene);
 
-    float4 *deviceRays = nullptr;
-    float4 *deviceHits = nullptr;
-    int *deviceOccluded = nullptr;
-    int *deviceOverflow = nullptr;
-    HIP_TRY(hipMalloc((void **)&deviceRays, n * 2 * sizeof(float4)));
-    hipError_t status = hipMemcpy(deviceRays, rays, n * 8 * sizeof(float), hipMemcpyHostToDevice);
-    if (status == hipSuccess) {
-        status = any_hit ? hipMalloc((void **)&deviceOccluded, n * sizeof(int)) : hipMalloc((void **)&deviceHits, n * sizeof(float4));
-    }
-    if (status == hipSuccess) {
-        const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-        const size_t lds = (size_t)(scene->stackRows + 1) * kBlock * sizeof(int);
-        const size_t overflowRows = (size_t)(scene->maxStack > scene->stackRows ? scene->maxStack - scene->stackRows : 0);
-        status = hipMalloc((void **)&deviceOverflow, (size_t)grid.x * kBlock * (overflowRows ? overflowRows : 1) * sizeof(int));
-        if (status == hipSuccess && scene->instanced) {
-            switch (scene->stackRows) {
-            case 8: hipLaunchKernelGGL((k_trace_rays_instanced<8>), grid, block, lds, 0, scene->device, scene->instanceSet, deviceRays, (int)n, any_hit, deviceHits, deviceOccluded, deviceOverflow, scene->maxStack); break;
-            case 16: hipLaunchKernelGGL((k_trace_rays_instanced<16>), grid, block, lds, 0, scene->device, scene->instanceSet, deviceRays, (int)n, any_hit, deviceHits, deviceOccluded, deviceOverflow, scene->maxStack); break;
-            default: hipLaunchKernelGGL((k_trace_rays_instanced<22>), grid, block, lds, 0, scene->device, scene->instanceSet, deviceRays, (int)n, any_hit, deviceHits, deviceOccluded, deviceOverflow, scene->maxStack); break;
-            }
-            status = hipGetLastError();
-            if (status == hipSuccess) { status = hipDeviceSynchronize(); }
-        } else if (status == hipSuccess) {
-            #define PATHED_HOOK(STACK, FORMAT) hipLaunchKernelGGL((k_trace_rays<STACK, FORMAT>), grid, block, lds, 0, scene->device, deviceRays, (int)n, any_hit, deviceHits, deviceOccluded, deviceOverflow, scene->maxStack)
-            #define PATHED_HOOK_ROWS(FORMAT) switch (scene->stackRows) { \
-                case 8: PATHED_HOOK(8, FORMAT); break; \
-                case 16: PATHED_HOOK(16, FORMAT); break; \
-                default: PATHED_HOOK(22, FORMAT); break; }
-#if PATHED_EXPERIMENTS
-            if (scene->nodeFormat == 2) { PATHED_HOOK_ROWS(2) }
-            else if (scene->nodeFormat == 1) { PATHED_HOOK_ROWS(1) }
-            else
-#endif
-            { PATHED_HOOK_ROWS(0) }
-            #undef PATHED_HOOK_ROWS
-            #undef PATHED_HOOK
-            status = hipGetLastError();
-            if (status == hipSuccess) { status = hipDeviceSynchronize(); }
+    DeviceBuffer<float4> deviceRays, deviceHits;
+    DeviceBuffer<int> deviceOccluded, deviceOverflow;
+    HIP_TRY(deviceRays.allocate(n * 2));
+    HIP_TRY(hipMemcpy(deviceRays.ptr, rays, n * 8 * sizeof(float), hipMemcpyHostToDevice));
+    if (any_hit) { HIP_TRY(deviceOccluded.allocate(n)); } else { HIP_TRY(deviceHits.allocate(n)); }
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    const int code = withStackRows(scene->stackRows, [&](auto STACK) {
+        HIP_TRY(deviceOverflow.allocate(stackSpillInts((size_t)grid.x * kBlock, scene->maxStack, STACK)));
+        if (scene->instanced) {
+            hipLaunchKernelGGL((k_trace_rays_instanced<STACK>), grid, block, stackLdsBytes(STACK), 0, scene->device, scene->instanceSet, deviceRays.ptr, (int)n, any_hit,
+                               deviceHits.ptr, deviceOccluded.ptr, deviceOverflow.ptr, scene->maxStack);
+            return (int)PATHED_OK;
         }
-    }
-    if (status == hipSuccess) {
-        status = any_hit
-            ? hipMemcpy(hits, deviceOccluded, n * sizeof(int), hipMemcpyDeviceToHost)
-            : hipMemcpy(hits, deviceHits, n * sizeof(float4), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(deviceRays);
-    if (deviceHits) { (void)hipFree(deviceHits); }
-    if (deviceOccluded) { (void)hipFree(deviceOccluded); }
-    if (deviceOverflow) { (void)hipFree(deviceOverflow); }
-    if (status != hipSuccess) { return fail(PATHED_E_DEVICE, hipGetErrorString(status)); }
+        // k_trace_rays<STACK, FORMAT>
+        const auto run = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, stackLdsBytes(STACK), 0, scene->device, deviceRays.ptr, (int)n, any_hit, deviceHits.ptr, deviceOccluded.ptr,
+                               deviceOverflow.ptr, scene->maxStack);
+            return (int)PATHED_OK;
+        };
+#if PATHED_EXPERIMENTS
+        if (scene->nodeFormat == 2) { return run(k_trace_rays<STACK, 2>); }
+        if (scene->nodeFormat == 1) { return run(k_trace_rays<STACK, 1>); }
+#endif
+        return run(k_trace_rays<STACK, 0>);
+    });
+    if (code != PATHED_OK) { return code; }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (any_hit) { HIP_TRY(hipMemcpy(hits, deviceOccluded.ptr, n * sizeof(int), hipMemcpyDeviceToHost)); }
+    else { HIP_TRY(hipMemcpy(hits, deviceHits.ptr, n * sizeof(float4), hipMemcpyDeviceToHost)); }
     return PATHED_OK;
 }
 
@@ -3484,20 +3445,10 @@ int pathed_hip_grid_queries(PathedScene *scene, int medium_index, size_t n, cons
     if (n == 0) { return PATHED_OK; }
     if (!a || !b || !target || !transmittance || !distance) { return fail(PATHED_E_INVALID, "null segment or result buffer"); }
     if (n > (size_t)1 << 24) { return fail(PATHED_E_INVALID, "too many segments in one call"); }
-    SELECT_DEVICE(scene);
-    DeviceBuffer<float> deviceA, deviceB, deviceTarget, deviceTransmittance, deviceDistance;
-    HIP_TRY(deviceA.upload(std::vector<float>(a, a + 3 * n)));
-    HIP_TRY(deviceB.upload(std::vector<float>(b, b + 3 * n)));
-    HIP_TRY(deviceTarget.upload(std::vector<float>(target, target + n)));
-    HIP_TRY(deviceTransmittance.allocate(n));
-    HIP_TRY(deviceDistance.allocate(n));
-    hipLaunchKernelGGL(k_grid_queries, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, scene->grids.ptr, scene->gridData.ptr,
-                       scene->mediaHost[(size_t)medium_index].grid, (int)n, deviceA.ptr, deviceB.ptr, deviceTarget.ptr, deviceTransmittance.ptr, deviceDistance.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(transmittance, deviceTransmittance.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(distance, deviceDistance.ptr, n * sizeof(float), hipMemcpyDeviceToHost));
-    return PATHED_OK;
+    return recordHook<float>(scene, n, { { a, 3 * n }, { b, 3 * n }, { target, n } }, { { transmittance, n }, { distance, n } }, [&](dim3 grid, auto &in, auto &out) {
+        hipLaunchKernelGGL(k_grid_queries, grid, dim3(kBlock), 0, nullptr, scene->grids.ptr, scene->gridData.ptr, scene->mediaHost[(size_t)medium_index].grid,
+                           (int)n, in[0].ptr, in[1].ptr, in[2].ptr, out[0].ptr, out[1].ptr);
+    });
 }
 
 int pathed_hip_debug_phase_samples(PathedScene *scene, size_t n, const float *u, float *out)
@@ -3509,16 +3460,9 @@ int pathed_hip_debug_phase_samples(PathedScene *scene, size_t n, const float *u,
     for (size_t i = 0; i < 2 * n; i++) {
         if (!(u[i] >= 0.f && u[i] <= 1.f)) { return fail(PATHED_E_INVALID, "phase samples: random numbers lie in [0, 1]"); }
     }
-    SELECT_DEVICE(scene);
-    DeviceBuffer<float> deviceIn, deviceOut;
-    HIP_TRY(deviceIn.upload(std::vector<float>(u, u + 2 * n)));
-    HIP_TRY(deviceOut.allocate(3 * n));
-    HIP_TRY(hipMemset(deviceOut.ptr, 0, 3 * n * sizeof(float)));
-    hipLaunchKernelGGL(k_debug_phase_samples, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, (int)n, deviceIn.ptr, deviceOut.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, deviceOut.ptr, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    return PATHED_OK;
+    return recordHook<float>(scene, n, { { u, 2 * n } }, { { out, 3 * n } }, [&](dim3 grid, auto &in, auto &result) {
+        hipLaunchKernelGGL(k_debug_phase_samples, grid, dim3(kBlock), 0, nullptr, (int)n, in[0].ptr, result[0].ptr);
+    });
 }
 
 int pathed_hip_debug_phase_hg(PathedScene *scene, size_t n, const float *records, float *out)
@@ -3535,16 +3479,9 @@ int pathed_hip_debug_phase_hg(PathedScene *scene, size_t n, const float *records
             if (!std::isfinite(record[k])) { return fail(PATHED_E_INVALID, "phase records: directions must be finite"); }
         }
     }
-    SELECT_DEVICE(scene);
-    DeviceBuffer<float> deviceIn, deviceOut;
-    HIP_TRY(deviceIn.upload(std::vector<float>(records, records + 9 * n)));
-    HIP_TRY(deviceOut.allocate(4 * n));
-    HIP_TRY(hipMemset(deviceOut.ptr, 0, 4 * n * sizeof(float)));
-    hipLaunchKernelGGL(k_debug_phase_hg, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, (int)n, deviceIn.ptr, deviceOut.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, deviceOut.ptr, 4 * n * sizeof(float), hipMemcpyDeviceToHost));
-    return PATHED_OK;
+    return recordHook<float>(scene, n, { { records, 9 * n } }, { { out, 4 * n } }, [&](dim3 grid, auto &in, auto &result) {
+        hipLaunchKernelGGL(k_debug_phase_hg, grid, dim3(kBlock), 0, nullptr, (int)n, in[0].ptr, result[0].ptr);
+    });
 }
 
 // what pathed_hip_debug_shading_queries needs to know of one SceneTraits set, and its instantiation of the kernel
@@ -3612,18 +3549,12 @@ int pathed_hip_debug_shading_queries(PathedScene *scene, int function, int trait
         }
     }
     SELECT_DEVICE(scene);
-    DeviceBuffer<float> deviceIn, deviceOut;
     DeviceBuffer<DMaterial> deviceMaterials;
-    HIP_TRY(deviceIn.upload(std::vector<float>(in, in + (size_t)inputs * n)));
-    HIP_TRY(deviceOut.allocate((size_t)outputs * n));
     if (material) { HIP_TRY(deviceMaterials.upload(materials)); }
-    HIP_TRY(hipMemset(deviceOut.ptr, 0, (size_t)outputs * n * sizeof(float)));
-    hipLaunchKernelGGL(set.kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, scene->device.env, deviceMaterials.ptr,
-                       function, (int)n, inputs, outputs, deviceIn.ptr, deviceOut.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, deviceOut.ptr, (size_t)outputs * n * sizeof(float), hipMemcpyDeviceToHost));
-    return PATHED_OK;
+    return recordHook<float>(scene, n, { { in, (size_t)inputs * n } }, { { out, (size_t)outputs * n } }, [&](dim3 grid, auto &records, auto &result) {
+        hipLaunchKernelGGL(set.kernel, grid, dim3(kBlock), 0, nullptr, scene->device.env, deviceMaterials.ptr, function, (int)n, inputs, outputs,
+                           records[0].ptr, result[0].ptr);
+    });
 }
 
 int pathed_hip_has_experiments(void) { return PATHED_EXPERIMENTS ? 1 : 0; }
@@ -3648,21 +3579,11 @@ int pathed_hip_debug_small_candidates(PathedScene *scene, const float *rays, siz
         HIP_TRY(table.upload(rows));
     }
 #endif
-    const size_t padded = (n + kBlock - 1) / kBlock * kBlock;   // whole blocks: every lane of a wave issues the matrix instructions
-    std::vector<float> hostRays(padded * 10, 0.f);
-    std::memcpy(hostRays.data(), rays, n * 10 * sizeof(float));
-    for (size_t i = n; i < padded; i++) { hostRays[10 * i + 5] = 1.f; hostRays[10 * i + 8] = 1.f; }
-    DeviceBuffer<float> deviceRays;
-    DeviceBuffer<unsigned long long> deviceOut;
-    HIP_TRY(deviceRays.upload(hostRays));
-    HIP_TRY(deviceOut.allocate(n * 8));
-    hipLaunchKernelGGL(k_debug_small_candidates, dim3((unsigned)(padded / kBlock)), dim3(kBlock), 0, nullptr, scene->device, scene->smallTris,
-                       scene->smallItems, scene->smallLayout.nQuads, scene->smallLayout.kappaT, scene->itemTris.ptr, table.ptr, frame,
-                       deviceRays.ptr, (int)n, deviceOut.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, deviceOut.ptr, n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PATHED_OK;
+    const std::vector<float> hostRays = paddedRays(rays, n);
+    return recordHook<unsigned long long>(scene, n, { { hostRays.data(), hostRays.size() } }, { { (unsigned long long *)out, n * 8 } }, [&](dim3 grid, auto &in, auto &result) {
+        hipLaunchKernelGGL(k_debug_small_candidates, grid, dim3(kBlock), 0, nullptr, scene->device, scene->smallTris, scene->smallItems, scene->smallLayout.nQuads,
+                           scene->smallLayout.kappaT, scene->itemTris.ptr, table.ptr, frame, in[0].ptr, (int)n, result[0].ptr);
+    });
 }
 
 int pathed_hip_debug_shadow_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out, int32_t *layout, uint64_t *never_occluders)
@@ -3671,30 +3592,16 @@ int pathed_hip_debug_shadow_candidates(PathedScene *scene, const float *rays, si
     if (scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector's hook does not serve scenes with instances"); }
     if (!scene->bruteForce || scene->device.nTris < 1) { return fail(PATHED_E_UNSUPPORTED, "the all-triangles intersector serves scenes of 1..64 triangles"); }
     if (!layout || !never_occluders) { return fail(PATHED_E_INVALID, "null layout or never-occluder buffer"); }
-    layout[0] = scene->smallLayout.nQuads;
-    layout[1] = scene->smallLayout.nLone;
-    layout[2] = scene->smallLayout.shadowQuadPairs;
-    layout[3] = scene->smallLayout.shadowLonePairs;
+    fillLayout(layout, scene->smallLayout);
     *never_occluders = scene->smallLayout.neverOccluders;
     if (n == 0) { return PATHED_OK; }
     if (!rays || !out) { return fail(PATHED_E_INVALID, "null ray or output buffer"); }
     if (n > (size_t)1 << 24) { return fail(PATHED_E_INVALID, "too many rays in one call"); }
-    SELECT_DEVICE(scene);
-    const size_t padded = (n + kBlock - 1) / kBlock * kBlock;   // whole blocks: the kernel reads a ray per lane
-    std::vector<float> hostRays(padded * 10, 0.f);
-    std::memcpy(hostRays.data(), rays, n * 10 * sizeof(float));
-    for (size_t i = n; i < padded; i++) { hostRays[10 * i + 5] = 1.f; hostRays[10 * i + 8] = 1.f; }
-    DeviceBuffer<float> deviceRays;
-    DeviceBuffer<unsigned long long> deviceOut;
-    HIP_TRY(deviceRays.upload(hostRays));
-    HIP_TRY(deviceOut.allocate(n * 2));
-    hipLaunchKernelGGL(k_debug_shadow_candidates, dim3((unsigned)(padded / kBlock)), dim3(kBlock), 0, nullptr, scene->device, scene->smallItems,
-                       scene->smallLayout.nQuads, scene->smallLayout.kappaT, scene->smallLayout.shadowQuadPairs, scene->smallLayout.shadowLonePairs,
-                       scene->itemTris.ptr, deviceRays.ptr, (int)n, deviceOut.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, deviceOut.ptr, n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PATHED_OK;
+    const std::vector<float> hostRays = paddedRays(rays, n);
+    return recordHook<unsigned long long>(scene, n, { { hostRays.data(), hostRays.size() } }, { { (unsigned long long *)out, n * 2 } }, [&](dim3 grid, auto &in, auto &result) {
+        hipLaunchKernelGGL(k_debug_shadow_candidates, grid, dim3(kBlock), 0, nullptr, scene->device, scene->smallItems, scene->smallLayout.nQuads, scene->smallLayout.kappaT,
+                           scene->smallLayout.shadowQuadPairs, scene->smallLayout.shadowLonePairs, scene->itemTris.ptr, in[0].ptr, (int)n, result[0].ptr);
+    });
 }
 
 int pathed_hip_debug_pass_candidates(PathedScene *scene, const float *rays, size_t n, uint64_t *out, int32_t *primitives, size_t n_triangles,
@@ -3708,10 +3615,7 @@ int pathed_hip_debug_pass_candidates(PathedScene *scene, const float *rays, size
     if (n_triangles != (size_t)scene->device.nTris || nPass < 1 || nPass > scene->device.nTris || scene->passTrisHost.size() < (size_t)12 * nPass) {
         return fail(PATHED_E_INVALID, "n_triangles must be the scene's triangle count");
     }
-    layout[0] = scene->passLayout.nQuads;
-    layout[1] = scene->passLayout.nLone;
-    layout[2] = scene->passLayout.shadowQuadPairs;
-    layout[3] = scene->passLayout.shadowLonePairs;
+    fillLayout(layout, scene->passLayout);
     layout[4] = nPass;
     *never_hit = scene->passNeverHit;
     for (size_t k = 0; k < n_triangles; k++) {
@@ -3721,22 +3625,12 @@ int pathed_hip_debug_pass_candidates(PathedScene *scene, const float *rays, size
     if (n == 0) { return PATHED_OK; }
     if (!rays || !out) { return fail(PATHED_E_INVALID, "null ray or output buffer"); }
     if (n > (size_t)1 << 24) { return fail(PATHED_E_INVALID, "too many rays in one call"); }
-    SELECT_DEVICE(scene);
-    const size_t padded = (n + kBlock - 1) / kBlock * kBlock;   // whole blocks: the kernel reads a ray per lane
-    std::vector<float> hostRays(padded * 10, 0.f);
-    std::memcpy(hostRays.data(), rays, n * 10 * sizeof(float));
-    for (size_t i = n; i < padded; i++) { hostRays[10 * i + 5] = 1.f; hostRays[10 * i + 8] = 1.f; }
-    DeviceBuffer<float> deviceRays;
-    DeviceBuffer<unsigned long long> deviceOut;
-    HIP_TRY(deviceRays.upload(hostRays));
-    HIP_TRY(deviceOut.allocate(n * 2));
-    hipLaunchKernelGGL(k_debug_pass_candidates, dim3((unsigned)(padded / kBlock)), dim3(kBlock), 0, nullptr, scene->passItems,
-                       scene->passLayout.nQuads, nPass, scene->passLayout.kappaT, scene->passLayout.shadowQuadPairs, scene->passLayout.shadowLonePairs,
-                       scene->itemTris.ptr + (size_t)3 * scene->device.nTris, deviceRays.ptr, (int)n, deviceOut.ptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, deviceOut.ptr, n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PATHED_OK;
+    const std::vector<float> hostRays = paddedRays(rays, n);
+    return recordHook<unsigned long long>(scene, n, { { hostRays.data(), hostRays.size() } }, { { (unsigned long long *)out, n * 2 } }, [&](dim3 grid, auto &in, auto &result) {
+        hipLaunchKernelGGL(k_debug_pass_candidates, grid, dim3(kBlock), 0, nullptr, scene->passItems, scene->passLayout.nQuads, nPass, scene->passLayout.kappaT,
+                           scene->passLayout.shadowQuadPairs, scene->passLayout.shadowLonePairs, scene->itemTris.ptr + (size_t)3 * scene->device.nTris, in[0].ptr, (int)n,
+                           result[0].ptr);
+    });
 }
 
 int pathed_hip_debug_camera_masks(PathedScene *scene, uint64_t *out, size_t n_pixels)

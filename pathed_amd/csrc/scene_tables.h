@@ -55,6 +55,18 @@ inline int checkSceneOptions(const PathedSceneOptions &options, std::string *mes
     return PATHED_OK;
 }
 
+// ---- the traversal stack's shape: every launch of a kernel with a STACK template argument takes all three from here
+
+// the LDS rows a lane's stack gets for a requested row count: the kernels exist with 8, 16 and 22 rows
+constexpr int stackRowsFor(int requested) { return requested == 8 || requested == 16 ? requested : 22; }
+
+// dynamic LDS of a block's stacks: `rows` rows and one of scratch, an int per lane (kOptionMinSlots is kBlock, the block size)
+constexpr size_t stackLdsBytes(int rows) { return (size_t)(rows + 1) * kOptionMinSlots * sizeof(int); }
+
+// ints of the HBM spill buffer of `threads` lanes: a column of the (maxStack - rows) entries a tree of bound maxStack may push
+// beyond the LDS rows per lane, and never less than one column
+constexpr size_t stackSpillInts(size_t threads, int maxStack, int rows) { return threads * (size_t)(maxStack > rows ? maxStack - rows : 1); }
+
 // ---- image textures
 
 // One array of texels (4 floats each, w = 0) for all textures, already through Texture::lookup's powf(x / 255.f, 2.2f)

@@ -465,9 +465,25 @@ static void testSplit()
     }
 }
 
+// ---- the traversal stack's shape
+static void testStackShape()
+{
+    for (int rows : { 8, 16, 22 }) { CHECK(stackRowsFor(rows) == rows, "rows for %d: %d", rows, stackRowsFor(rows)); }
+    for (int rows : { 0, 7, 9, 23, -8 }) { CHECK(stackRowsFor(rows) == 22, "rows for %d: %d", rows, stackRowsFor(rows)); }
+    const size_t row = (size_t)kOptionMinSlots * sizeof(int);   // one int per lane of a block (kBlock)
+    CHECK(stackLdsBytes(8) == 9 * row && stackLdsBytes(16) == 17 * row && stackLdsBytes(22) == 23 * row, "LDS bytes %zu %zu %zu", stackLdsBytes(8), stackLdsBytes(16), stackLdsBytes(22));
+    const size_t threads = (size_t)1024 * 256;
+    for (int rows : { 8, 16, 22 }) {
+        for (int maxStack : { 0, 1, rows - 1, rows }) { CHECK(stackSpillInts(threads, maxStack, rows) == threads, "spill of %d over %d rows", maxStack, rows); }
+        for (int maxStack : { rows + 1, rows + 2, 64 }) { CHECK(stackSpillInts(threads, maxStack, rows) == threads * (size_t)(maxStack - rows), "spill of %d over %d rows", maxStack, rows); }
+    }
+    CHECK(stackSpillInts((size_t)1 << 28, 70, 8) == ((size_t)62 << 28), "the product is taken in size_t");
+}
+
 int main()
 {
     testOptions();
+    testStackShape();
     testEnvTables();
     testLightList();
     testPlainRanges();

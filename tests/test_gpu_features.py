@@ -388,6 +388,46 @@ def test_albedo_integrator_is_the_references():
     _assert_reference(gpu.render(SEED, 0, SPP, 0, 3), expected, inexact)
 
 
+def _stack_rungs(bound):
+    """the LDS row counts that hold a stack of `bound` entries without a spill: the default (the rule of configureTrace) and up"""
+    default = 8 if bound <= 8 else 16 if bound <= 16 else 22
+    return [rows for rows in (8, 16, 22) if rows >= default]
+
+
+def _shallow_room():
+    """8 triangles under intersector="bvh": leaves of <= 2 triangles make <= 7 leaves, which two 4-wide levels always hold"""
+    from scene_builder import BuiltScene
+    built = BuiltScene(16, 12, origin=(0, 1, 4.5), target=(0, 1, 0), fov_degrees=45.0)
+    built.quad([(-2, 0, -2), (2, 0, -2), (2, 0, 2), (-2, 0, 2)], built.material(diffuse=(0.7, 0.6, 0.5)))
+    built.quad([(-2, 0, -2), (-2, 2.4, -2), (2, 2.4, -2), (2, 0, -2)], built.material(checker=((0.9, 0.8, 0.1), (0.1, 0.2, 0.7), (6.0, 5.0))))
+    built.quad([(-2, 0, 2), (-2, 2.4, 2), (-2, 2.4, -2), (-2, 0, -2)], built.material(diffuse=(0.6, 0.1, 0.1)))
+    built.quad([(-0.5, 2.2, -0.5), (0.5, 2.2, -0.5), (0.5, 2.2, 0.5), (-0.5, 2.2, 0.5)], built.material(diffuse=(0.3, 0.3, 0.3), emit=(5, 4, 3)))
+    assert len(built.indices) == 8
+    return built, built.finish()
+
+
+@pytest.mark.parametrize("reference", [False, True], ids=["features", "albedo-integrator"])
+def test_every_stack_row_count_gives_the_same_bits(reference):
+    """k_features<8 | 16 | 22, REFERENCE> (launchFeatures): the row count the scene takes by default and every larger one"""
+    from pathed_amd.integrator import HipScene
+    built, desc = _shallow_room()   # (`built` owns the arrays `desc` points to)
+
+    def images(rows):
+        gpu = HipScene(desc, device=0, stack_rows=rows, intersector="bvh")
+        assert 3 * gpu.stats()["bvh_max_depth"] + 1 <= 8   # the default is 8 rows: all three rungs run, none spills
+        if not reference:
+            return gpu.render_features(SEED, 0, 4)
+        gpu.set_integrator("AlbedoIntegrator")
+        image = gpu.render(SEED, 0, 4, 0, 3)
+        assert gpu.stats()["path_kernel"] == 8
+        return [image]
+
+    default = images(0)
+    assert all(image.any() for image in default)
+    for rows in _stack_rungs(8):
+        assert _equal(images(rows), default), rows
+
+
 def test_argument_errors():
     from pathed_amd import _capi
     from pathed_amd.integrator import HipScene

@@ -106,6 +106,37 @@ def test_exact_class_list_pass(exact, listed):
     assert np.all(counts[chosen] == 11) and np.all(counts[others] == 7)
 
 
+def instanced_stack_rungs(depth):
+    """The LDS row counts that hold a two-level stack without a spill, for bvh_max_depth = the top tree's levels + the deepest
+    prototype's: the bound is (3 top + 1) + (3 deepest + 1) + 1 entries; the default is the first of 8, 16, 22 that holds it"""
+    bound = 3 * depth + 3
+    default = 8 if bound <= 8 else 16 if bound <= 16 else 22
+    return [rows for rows in (8, 16, 22) if rows >= default]
+
+
+@pytest.mark.parametrize("count", [False, True], ids=["plain", "counting"])
+def test_every_stack_row_count_renders_the_same_bits(count):
+    """k_trace_instanced<8 | 16 | 22, COUNT> in a render: the row count the scene takes by default and every larger one"""
+    _, pointer, prototypes, placements = S.build(S.EXACT_PLACEMENTS, 16, 12)
+
+    def render(rows):
+        gpu = HipScene(pointer, device=0, prototypes=prototypes, instances=placements, stack_rows=rows)
+        gpu.set_stats_mode(count=count)
+        sums, squares = gpu.render_moments(5, 0, 4, 0, 3)
+        stats = gpu.stats()
+        assert stats["path_kernel"] == 10 and (stats["nodes_visited"] > 0 or not count)
+        return sums, squares, stats["bvh_max_depth"], stats["nodes_visited"]
+
+    sums, squares, depth, visited = render(0)
+    assert float(sums.sum()) > 0.0
+    rungs = instanced_stack_rungs(depth)
+    assert rungs   # (22 always is one)
+    for rows in rungs:
+        again = render(rows)
+        assert np.array_equal(bits(again[0]), bits(sums)) and np.array_equal(bits(again[1]), bits(squares)), rows
+        assert again[3] == visited, rows
+
+
 # -------------------------------------------------------------------------------------------------------- 2. general class
 
 GENERAL_SEED = 3

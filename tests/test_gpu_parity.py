@@ -524,6 +524,44 @@ def test_traversal_stack_spill_to_hbm_changes_nothing(libs):
     assert np.array_equal(default.render(3, 0, 8, 0, 8), image)
 
 
+@pytest.mark.parametrize("kind", ["flat", "instanced"])
+def test_trace_hook_gives_the_same_bits_with_every_stack_row_count(libs, kind):
+    """k_trace_rays<8 | 16 | 22> and k_trace_rays_instanced<8 | 16 | 22> (pathed_hip_trace): the row count the scene takes by
+    default and every larger one, so that no rung spills; closest hits and occlusion flags are equal bit for bit."""
+    _, HipScene, _ = libs
+    if kind == "flat":
+        # 8 triangles under intersector="bvh": leaves of <= 2 triangles make <= 7 leaves, which two 4-wide levels always hold
+        from scene_builder import BuiltScene
+        built = BuiltScene(16, 12, origin=(0, 1, 4.5), target=(0, 1, 0), fov_degrees=45.0)
+        grey = built.material(diffuse=(0.5, 0.5, 0.5))
+        built.quad([(-2, 0, -2), (2, 0, -2), (2, 0, 2), (-2, 0, 2)], grey)
+        built.quad([(-2, 0, -2), (-2, 2.4, -2), (2, 2.4, -2), (2, 0, -2)], grey)
+        built.quad([(-2, 0, 2), (-2, 2.4, 2), (-2, 2.4, -2), (-2, 0, -2)], grey)
+        built.quad([(-0.5, 2.2, -0.5), (0.5, 2.2, -0.5), (0.5, 2.2, 0.5), (-0.5, 2.2, 0.5)], built.material(emit=(5, 4, 3)))
+        desc = built.finish()
+        create = lambda rows: HipScene(desc, device=0, stack_rows=rows, intersector="bvh")
+        rays = _rays(300, 5, (0, 1.2, 0), 1.5)
+        rays[200:, 7] = 2.5   # short rays: occlusion flags of both kinds
+    else:
+        import instances_scene as S
+        _, pointer, prototypes, placements = S.build(S.EXACT_PLACEMENTS, 16, 12)
+        create = lambda rows: HipScene(pointer, device=0, prototypes=prototypes, instances=placements, stack_rows=rows)
+        rays = _rays(300, 5, S.CAMERA["target"], 6.0)
+        rays[200:, 7] = 6.0
+    default = create(0)
+    depth = default.stats()["bvh_max_depth"]
+    if kind == "flat":
+        assert 3 * depth + 1 <= 8   # the default is 8 rows: all three rungs run
+    bound = 3 * depth + 1 if kind == "flat" else 3 * depth + 3   # (two trees: (3 top + 1) + (3 deepest + 1) + 1)
+    first = 8 if bound <= 8 else 16 if bound <= 16 else 22
+    hits, occluded = default.trace(rays), default.trace(rays, any_hit=True)
+    assert 0.1 < (hits[:, 3].view(np.int32) >= 0).mean() and 0.05 < occluded.mean() < 0.95
+    for rows in [rows for rows in (8, 16, 22) if rows >= first]:
+        forced = create(rows)
+        assert np.array_equal(forced.trace(rays).view(np.int32), hits.view(np.int32)), rows
+        assert np.array_equal(forced.trace(rays, any_hit=True), occluded), rows
+
+
 def test_large_mesh_intersector_and_render_parity(libs):
     """The large-BVH configuration in small: the procedural stand-in mesh at 82 K triangles (deep
     4-wide tree, nodes in L2/HBM, stack spill possible), traced and rendered against the oracle."""
