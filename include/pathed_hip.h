@@ -227,6 +227,9 @@ typedef struct PathedStats {
                                         of PATHED_INTEGRATOR_ALBEDO; its samples count in camera_samples and closest_rays),
                                       9 multiple-scattering volume kernel (PATHED_INTEGRATOR_BASIC_VOLUME),
                                       10 wavefront of an instanced scene (k_trace_instanced + k_shade_instanced),
+                                         11 on such a scene while a shutter is set (pathed_hip_scene_set_instance_motion:
+                                         k_trace_instanced_motion + k_shade_instanced_motion; the other meaning of 11 below
+                                         cannot occur on the same scene: a scene with instances holds no medium),
                                       11 anisotropic multiple-scattering volume kernel (PATHED_INTEGRATOR_BASIC_VOLUME on a scene
                                          with a Henyey-Greenstein medium, pathed_hip_scene_set_medium_phase) */
     uint32_t reserved0;
@@ -437,6 +440,44 @@ int pathed_hip_scene_set_instance_transforms_device(PathedScene *scene, const fl
  * builder (the host builder needs the scene created again).  PATHED_E_DEVICE: an allocation or a kernel failed.  The new
  * arrays are built beside the live ones and adopted at the end: on every error the scene is exactly as it was. */
 int pathed_hip_scene_rebuild_top(PathedScene *scene, int32_t builder, float *device_ms);
+/* The shutter: placements that MOVE while a sample is taken.  transforms_close: 12 floats per instance, ALL instances, row-major
+ * 3 x 4, the placements at shutter time 1; the scene's current transforms are the placements at time 0.  Host memory, or for
+ * the _device form memory on the scene's device; one compute path, as above.  0 <= shutter_open <= shutter_close <= 1.
+ *
+ * The rule (pathed_amd/csrc/instances.h, pathed_amd.instances in numpy):
+ *   transform at time t   m[i] = ((1 - t) * a[i]) + (t * b[i]) for the 12 floats a (time 0) and b (time 1), fp32, one rounding
+ *                         per operation, no fused multiply-add (interpolateTransform); its inverse by the routine above
+ *   time of a sample      t = open + (close - open) * u in fp32, u the sample's stream u(seed, pixel, sample, .) at dimension
+ *                         0xFFFFFFFF (sampleTime) -- a dimension no vertex owns, so the camera jitter and every BSDF and light
+ *                         number are the ones a scene without motion draws, and a pure function of (seed, pixel, sample), so any
+ *                         split into calls, sample ranges, ranks or pixel lists draws the same times
+ *   same transform twice  a placement whose a and b are bit-equal does not move: it keeps its record and its static box and is
+ *                         walked and shaded as in a scene without motion, so a scene pays for the placements that move
+ *   box                   a moving placement's world box is the union of its boxes at open and at close plus a pad
+ *                         (movingPlacementBox: a point moves on a straight segment under a linearly interpolated matrix)
+ *   singular in between   both END transforms must be finite and invertible; M(t) in between need not be (a half turn
+ *                         interpolated linearly is singular at t = 0.5): a ray whose M(t) is not invertible, or whose inverse is
+ *                         not finite, SKIPS that placement
+ * Every sample of a render call then sees each moving placement at the sample's own time: a hit is what a scene created with
+ * the transforms M(t) gives, bit for bit, in the walk and in shading.  With open == close every sample sees M(open).
+ *
+ * The call stores the second transforms, restates the moving placements' boxes (k_motion_boxes) and refits the top tree on the
+ * device (k_refit_top_pass).  While motion is set the wavefront runs k_trace_instanced_motion / k_shade_instanced_motion and
+ * PathedStats.path_kernel reports 11 on such a scene (10 without motion); the pixel-list calls work as on any instanced scene.
+ * transforms_close == NULL removes the motion and restores the static boxes: renders are the static scene's bits again.
+ * pathed_hip_scene_set_instance_transforms[_device] on a scene with motion replaces the time-0 transforms AND removes the
+ * motion (the caller sets the motion of the next frame); pathed_hip_scene_rebuild_top builds over the moving boxes.
+ * Order and device_ms: as pathed_hip_scene_set_instance_transforms.
+ *
+ * PATHED_E_UNSUPPORTED: a scene without instances.  PATHED_E_INVALID: a null scene, a count that is not the scene's, a shutter
+ * outside 0 <= open <= close <= 1, a transform of time 1 that is not finite or not invertible.  All of it is refused before
+ * anything is launched (the _device form finds a bad transform on the device, in one launch that writes beside the live state);
+ * on every such refusal the scene is exactly as it was.  PATHED_E_DEVICE (a kernel of the refit failed): the scene keeps the
+ * motion state it had -- it flips only after the refit succeeded -- but the top tree's boxes may be partly rewritten. */
+int pathed_hip_scene_set_instance_motion(PathedScene *scene, const float *transforms_close, uint32_t n_instances,
+                                         float shutter_open, float shutter_close, float *device_ms);
+int pathed_hip_scene_set_instance_motion_device(PathedScene *scene, const float *d_transforms_close, uint32_t n_instances,
+                                                float shutter_open, float shutter_close, float *device_ms);
 /* Another view of the same scene: replaces the camera (reference Camera, src/camera.cpp:13-30) without rebuilding or
  * re-uploading anything; the resolution must stay (the caller's radiance sums are per pixel). */
 int pathed_hip_scene_set_camera(PathedScene *scene, const PathedCamera *camera);
@@ -707,6 +748,14 @@ int pathed_hip_debug_phase_hg(PathedScene *scene, size_t n, const float *records
  *               hits = n * int32 (1 = occluded). */
 int pathed_hip_trace(PathedScene *scene, const float *rays, size_t n,
                      int any_hit, void *hits);
+/* ... with one shutter time per ray, on a scene with motion (pathed_hip_scene_set_instance_motion): the test hook of the
+ * shutter, k_trace_rays_instanced_motion.  times: n floats inside the scene's shutter [open, close], host memory.  Ray i
+ * meets every moving placement under the transform M(times[i]) of the rule stated there -- the hit, bit for bit, of a scene
+ * created with those transforms -- and skips a placement whose M(times[i]) is not invertible.  PATHED_E_UNSUPPORTED: a
+ * scene without instances.  PATHED_E_INVALID: a scene without motion, a null buffer, a time outside the shutter (the moving
+ * boxes cover the shutter and nothing beyond it). */
+int pathed_hip_trace_timed(PathedScene *scene, const float *rays, const float *times, size_t n,
+                           int any_hit, void *hits);
 
 /* Test hook onto phase 1 of the all-triangles intersector (scenes of <= 64 triangles; the stand-in for
  * rtcIntersect1 / rtcOccluded1 on such scenes, reference src/scene.cpp:113,374).

@@ -251,6 +251,8 @@ HIP_SYMBOLS = [
     "pathed_hip_scene_set_instance_transforms",
     "pathed_hip_scene_set_instance_transforms_device",
     "pathed_hip_scene_rebuild_top",
+    "pathed_hip_scene_set_instance_motion",
+    "pathed_hip_scene_set_instance_motion_device",
     "pathed_hip_debug_instance_records",
     "pathed_hip_scene_device",
     "pathed_hip_scene_set_camera",
@@ -271,6 +273,7 @@ HIP_SYMBOLS = [
     "pathed_hip_select_pixels_device",
     "pathed_hip_render_pixels_device",
     "pathed_hip_trace",
+    "pathed_hip_trace_timed",
     "pathed_hip_debug_small_candidates",
     "pathed_hip_debug_shadow_candidates",
     "pathed_hip_debug_pass_candidates",
@@ -351,6 +354,13 @@ def load_hip():
     if hasattr(lib, "pathed_hip_scene_rebuild_top"):   # (an older build of the same ABI, as above)
         lib.pathed_hip_scene_rebuild_top.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
         lib.pathed_hip_scene_rebuild_top.restype = C.c_int
+    if hasattr(lib, "pathed_hip_scene_set_instance_motion"):   # (an older build of the same ABI, as above)
+        lib.pathed_hip_scene_set_instance_motion.argtypes = [vp, C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_float)]
+        lib.pathed_hip_scene_set_instance_motion.restype = C.c_int
+        lib.pathed_hip_scene_set_instance_motion_device.argtypes = [vp, vp, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_float)]
+        lib.pathed_hip_scene_set_instance_motion_device.restype = C.c_int
+        lib.pathed_hip_trace_timed.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_int, vp]
+        lib.pathed_hip_trace_timed.restype = C.c_int
     lib.pathed_hip_scene_device.argtypes = [vp]
     lib.pathed_hip_scene_device.restype = C.c_int
     lib.pathed_hip_scene_set_camera.argtypes = [vp, C.POINTER(PathedCamera)]
@@ -493,6 +503,9 @@ def load_host():
     lib.pathed_host_scene_phase.restype = C.c_int
     lib.pathed_host_last_error.argtypes = []
     lib.pathed_host_last_error.restype = C.c_char_p
+    if hasattr(lib, "pathed_host_scene_instances_close"):
+        lib.pathed_host_scene_instances_close.argtypes = [C.c_void_p]
+        lib.pathed_host_scene_instances_close.restype = C.POINTER(C.c_float)
     if hasattr(lib, "pathed_host_scene_instances"):
         lib.pathed_host_scene_instances.argtypes = [C.c_void_p]
         lib.pathed_host_scene_instances.restype = C.POINTER(PathedInstanceDesc)

@@ -9,6 +9,7 @@
 #include "pathed_hip.h"
 
 #include "bvh_build.h"
+#include "sample_stream.h"
 
 #include <cmath>
 #include <cstdint>
@@ -89,6 +90,73 @@ PATHED_INSTANCE_FN void placementBox(const float *m, const float *protoLo, const
         lo[a] = boxLo[a] - pad;
         hi[a] = boxHi[a] + pad;
     }
+}
+
+// ---- the shutter (DESIGN.md section 4.6d "Shutter"): a placement moves from the 12 floats a (shutter time 0, the scene's
+// current transform) to the 12 floats b (time 1), linearly, entry by entry.
+// The placement's transform at time t, fp32, one rounding per operation, no fused multiply-add.  t = 0 and t = 1 give the bits
+// of a and of b apart from the sign of a zero (1 * a + 0 * b turns a -0 into +0 where b is positive).  numpy:
+// pathed_amd.instances.interpolate_transforms.
+PATHED_INSTANCE_FN void interpolateTransform(const float *a, const float *b, float t, float *m)
+{
+    const float s = 1.f - t;
+    for (int i = 0; i < 12; i++) { m[i] = (s * a[i]) + (t * b[i]); }
+}
+
+// The time of a sample: its stream at dimension kDimTime (sample_stream.h) scaled into the shutter.  A pure function of
+// (seed, pixel, sample): no kernel stores it, and any split into calls, ranks or list passes draws the same times.
+// numpy: pathed_amd.instances.sample_time.
+PATHED_INSTANCE_FN float shutterTime(float u, float open, float close) { return open + (close - open) * u; }
+PATHED_INSTANCE_FN float sampleTime(uint64_t seed, uint32_t pixel, uint32_t sample, float open, float close)
+{
+    Rng random;
+    makeKey(seed, pixel, sample, &random.k0, &random.k1);
+    random.dimension = kDimTime;
+    return shutterTime(random.next(), open, close);
+}
+
+// A moving placement's world box over the shutter [open, close]: the union of placementBox(M(open)) and placementBox(M(close))
+// plus a pad.  Why the union: in exact arithmetic M(t) = (1 - s) M(open) + s M(close) with s = (t - open) / (close - open), so
+// the image of a point of the prototype moves on the straight segment between its two end images, and a box that holds both
+// ends holds the segment.  What the pad covers, per axis i:
+//   1. the static pad once more.  placementBox(M(t)) would pad the box of time t by 1e-5 max(1, |lo|, |hi|) + 1e-5 (hi - lo)
+//      for the roundings of the object-space ray; the box of time t lies inside the union, so the same expression over the
+//      union is at least that.
+//   2. the roundings of the interpolated matrix.  Each entry of M(t) takes three roundings (1 - t, two products, one sum; M(open)
+//      and M(close) take them too), so it is off the exact interpolant by at most 4 * 2^-24 (|a| + |b|) <= 2^-21 max(|a|, |b|),
+//      and the image of a corner x of the prototype's box by at most 2^-21 (sum_j max(|a_ij|, |b_ij|) |x_j| + max(|a_i3|, |b_i3|)).
+//      The pad takes 1e-6 (twice 2^-21) of that sum with |x_j| <= max(|protoLo_j|, |protoHi_j|).
+// A placement with a == b bit for bit never comes here: it keeps placementBox(a).  numpy: pathed_amd.instances.moving_placement_box.
+PATHED_INSTANCE_FN void movingPlacementBox(const float *a, const float *b, float open, float close, const float *protoLo, const float *protoHi, float *lo, float *hi)
+{
+    float first[12], last[12], lo0[3], hi0[3], lo1[3], hi1[3];
+    interpolateTransform(a, b, open, first);
+    interpolateTransform(a, b, close, last);
+    placementBox(first, protoLo, protoHi, lo0, hi0);
+    placementBox(last, protoLo, protoHi, lo1, hi1);
+    for (int i = 0; i < 3; i++) {
+        const float boxLo = hostMin(lo0[i], lo1[i]), boxHi = hostMax(hi0[i], hi1[i]);
+        float reach = hostMax(std::fabs(a[4 * i + 3]), std::fabs(b[4 * i + 3]));
+        for (int j = 0; j < 3; j++) {
+            reach = reach + hostMax(std::fabs(a[4 * i + j]), std::fabs(b[4 * i + j])) * hostMax(std::fabs(protoLo[j]), std::fabs(protoHi[j]));
+        }
+        const float pad = (1e-5f * hostMax(1.f, hostMax(std::fabs(boxLo), std::fabs(boxHi))) + 1e-5f * (boxHi - boxLo)) + 1e-6f * reach;
+        lo[i] = boxLo - pad;
+        hi[i] = boxHi + pad;
+    }
+}
+
+// Do the two transforms differ in any bit?  (A placement that does not move keeps its stored record and its static box.)
+PATHED_INSTANCE_FN bool transformsDiffer(const float *a, const float *b)
+{
+    bool differ = false;
+    for (int i = 0; i < 12; i++) {
+        uint32_t x, y;
+        __builtin_memcpy(&x, a + i, 4);
+        __builtin_memcpy(&y, b + i, 4);
+        differ = differ || x != y;
+    }
+    return differ;
 }
 
 // One placement's record, 28 floats: the transform's rows, the inverse's rows, then (base, prototype, root node, first

@@ -1455,8 +1455,14 @@ __global__ __launch_bounds__(kBlock) void k_trace_rays(
 // in the shape of k_trace_small -- the pool is [closest ray of every live slot | dense shadow list], one ray per lane, hit[] and
 // pend[] written the same way -- with the per-lane stack in LDS rows [row][thread] and the HBM overflow column.  No refill,
 // no parking, no suspension: the first version, not the tuned one.
-template <int STACK, bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_trace_instanced(RenderParams p, DInstanceSet instances)
+// (the body of k_trace_instanced and of k_trace_instanced_motion, instance_motion.h: MOTION walks with the time of the
+// slot's sample, traverseWithSlotTime there; without it the shutter is compiled out)
+template <bool COUNT, int STACK>
+__device__ inline void traverseWithSlotTime(
+    const TraceGeometry &g, const DInstanceSet &instances, const LaneStack &stack, const RenderParams &p, unsigned int slot,
+    const float4 *worldO, const float4 *worldD, LaneRay &ray, TraceCounters *counters, const DMotionSet *motion);
+template <int STACK, bool COUNT, bool MOTION>
+__device__ __forceinline__ void traceInstancedPool(const RenderParams &p, const DInstanceSet &instances, const DMotionSet *motion)
 {
     extern __shared__ float4 ldsRaw[];
     LaneStack stack;
@@ -1510,7 +1516,8 @@ __global__ __launch_bounds__(kBlock) void k_trace_instanced(RenderParams p, DIns
             }
         }
         if (worldO == nullptr) { continue; }
-        traverseInstanced<COUNT, STACK, kBlock>(geometry, instances, stack, p.maxStack, worldO, worldD, ray, &counters);
+        if (MOTION) { traverseWithSlotTime<COUNT, STACK>(geometry, instances, stack, p, target, worldO, worldD, ray, &counters, motion); }
+        else { traverseInstanced<COUNT, STACK, kBlock>(geometry, instances, stack, p.maxStack, worldO, worldD, ray, &counters); }
         if (ray.anyHit) {
             if (ray.occluded) { p.state.pend[target] = make_float4(0.f, 0.f, 0.f, 0.f); }
             if (COUNT) { shadowRays++; }
@@ -1528,11 +1535,23 @@ __global__ __launch_bounds__(kBlock) void k_trace_instanced(RenderParams p, DIns
     }
 }
 
+template <int STACK, bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_trace_instanced(RenderParams p, DInstanceSet instances)
+{
+    traceInstancedPool<STACK, COUNT, false>(p, instances, nullptr);
+}
+
 // ... and the test hook's kernel behind pathed_hip_trace on such a scene: k_trace_rays over the two-level tree
-template <int STACK>
-__global__ __launch_bounds__(kBlock) void k_trace_rays_instanced(
-    DScene scene, DInstanceSet instances, const float4 *rays, int n, int anyHit, float4 *hitsOut, int *occludedOut,
-    int *stackOverflow, int maxStack
+// (the body of k_trace_rays_instanced and of k_trace_rays_instanced_motion, instance_motion.h: one time per ray)
+struct GivenTime {
+    static constexpr bool shutter = true;
+    float value;
+    __device__ float operator()() const { return value; }
+};
+template <int STACK, bool MOTION>
+__device__ __forceinline__ void traceRaysInstanced(
+    const DScene &scene, const DInstanceSet &instances, const float4 *rays, int n, int anyHit, float4 *hitsOut, int *occludedOut,
+    int *stackOverflow, int maxStack, const DMotionSet *motion, const float *times
 ) {
     extern __shared__ float4 ldsRaw[];
     LaneStack stack;
@@ -1555,7 +1574,12 @@ __global__ __launch_bounds__(kBlock) void k_trace_rays_instanced(
     TraceCounters counters;
     LaneRay ray;
     laneRayInit(ray, v3(ro.x, ro.y, ro.z), v3(rd.x, rd.y, rd.z), ro.w, rd.w, anyHit != 0);
-    traverseInstanced<false, STACK, kBlock>(geometry, instances, stack, maxStack, rays + 2 * i, rays + 2 * i + 1, ray, &counters);
+    if (MOTION) {
+        GivenTime time = { times[i] };
+        traverseInstanced<false, STACK, kBlock, GivenTime>(geometry, instances, stack, maxStack, rays + 2 * i, rays + 2 * i + 1, ray, &counters, motion, &time);
+    } else {
+        traverseInstanced<false, STACK, kBlock>(geometry, instances, stack, maxStack, rays + 2 * i, rays + 2 * i + 1, ray, &counters);
+    }
     if (anyHit) {
         occludedOut[i] = ray.occluded ? 1 : 0;
     } else if (ray.bestPrim >= 0) {
@@ -1563,6 +1587,14 @@ __global__ __launch_bounds__(kBlock) void k_trace_rays_instanced(
     } else {
         hitsOut[i] = make_float4(0.f, 0.f, 0.f, intAsFloat(-1));
     }
+}
+
+template <int STACK>
+__global__ __launch_bounds__(kBlock) void k_trace_rays_instanced(
+    DScene scene, DInstanceSet instances, const float4 *rays, int n, int anyHit, float4 *hitsOut, int *occludedOut,
+    int *stackOverflow, int maxStack
+) {
+    traceRaysInstanced<STACK, false>(scene, instances, rays, n, anyHit, hitsOut, occludedOut, stackOverflow, maxStack, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------- shade
@@ -1575,8 +1607,11 @@ __device__ inline V3 triangleNormal(V3 p0, V3 p1, V3 p2) { return normalized(xcr
 // prototype triangle's record is flattened here, corners by flattenPoint and vertex normals by flattenNormal, the host's own
 // routine in the host's operation order, and then goes through the statements of the general branch: every quantity is what
 // the flattened scene's record gives for the same (t, u, v, prim)
-template <typename TRAITS = TraitsAll, bool INSTANCED = false>
-__device__ inline Isect makeIsect(const DScene &scene, V3 o, V3 d, float4 h, const DInstanceSet *instances = nullptr)
+// MOTION (k_shade_instanced_motion): a MOVING placement's triangle is flattened with M(time) and its inverse, the time of the
+// hit's sample, and then runs the same statements: the record of a static scene created with M(time)
+template <typename TRAITS = TraitsAll, bool INSTANCED = false, bool MOTION = false>
+__device__ inline Isect makeIsect(const DScene &scene, V3 o, V3 d, float4 h, const DInstanceSet *instances = nullptr,
+                                  const DMotionSet *motion = nullptr, float time = 0.f)
 {
     const float t = h.x, u = h.y, v = h.z;
 #if defined(PATHED_ABLATE) && PATHED_ABLATE == 1
@@ -1599,8 +1634,10 @@ __device__ inline Isect makeIsect(const DScene &scene, V3 o, V3 d, float4 h, con
         }
         const float4 *record = instances->records + (size_t)kInstanceQuads * low;
         const float4 m0 = record[0], m1 = record[1], m2 = record[2], i0 = record[3], i1 = record[4], i2 = record[5], ids = record[6];
-        const float m[12] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w };
-        const float inverse[12] = { i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w, i2.x, i2.y, i2.z, i2.w };
+        float m[12] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w };
+        float inverse[12] = { i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w, i2.x, i2.y, i2.z, i2.w };
+        // (a ray that hit the placement found M(time) invertible: the walk skips the placement otherwise)
+        if (MOTION && motion->moving[low]) { movingTransform(record, *motion, low, time, m, inverse); }
         const float4 *q = scene.triShade + (size_t)kTriShadeQuads * (size_t)(floatAsInt(ids.w) + (prim - floatAsInt(ids.x)));
         const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6];
         const V3 p0 = flattenPoint(m, v3(q0.x, q0.y, q0.z)), p1 = flattenPoint(m, v3(q1.x, q1.y, q1.z)), p2 = flattenPoint(m, v3(q2.x, q2.y, q2.z));
@@ -2369,8 +2406,9 @@ struct MaterialAccess {
 #endif
 // The shade stage of the wavefront, one lane per slot: the body of k_shade and of k_shade_instanced (INSTANCED: makeIsect
 // flattens the record of a hit on an instance), as pathVolume serves k_path_volume and k_list_volume.
-template <bool LDS_MATERIALS, bool ENV_ONLY, typename TRAITS, bool INSTANCED>
-__device__ __forceinline__ void shadeSlots(const RenderParams &p, const DInstanceSet *instances)
+// MOTION (k_shade_instanced_motion, instance_motion.h): a hit on a placement is flattened at the time of its sample.
+template <bool LDS_MATERIALS, bool ENV_ONLY, typename TRAITS, bool INSTANCED, bool MOTION = false>
+__device__ __forceinline__ void shadeSlots(const RenderParams &p, const DInstanceSet *instances, const DMotionSet *motion = nullptr)
 {
     __shared__ DMaterial ldsMaterials[LDS_MATERIALS ? kMaxLdsMaterials : 1];
     __shared__ unsigned int scratch[kWavesPerBlock + 1];
@@ -2480,7 +2518,13 @@ __device__ __forceinline__ void shadeSlots(const RenderParams &p, const DInstanc
         // the lanes of a wave sit at different path depths, and code inlined in both branches is
         // executed twice by every mixed wave
         SHADE_REGION(2, !miss);   // makeIsect
-        if (!miss) { isect = makeIsect<TRAITS, INSTANCED>(scene, o, d, h, instances); }
+        if (MOTION) {
+            float time = 0.f;
+            if (!miss && floatAsInt(h.w) >= instances->worldTris) {
+                time = sampleTime(((uint64_t)p.seedHi << 32) | p.seedLo, pixel, sample, motion->open, motion->close);
+            }
+            if (!miss) { isect = makeIsect<TRAITS, INSTANCED, true>(scene, o, d, h, instances, motion, time); }
+        } else if (!miss) { isect = makeIsect<TRAITS, INSTANCED>(scene, o, d, h, instances); }
         SHADE_REGION(3, rayBounce == 0);
         SHADE_REGION(4, rayBounce != 0 && (st & kStEligible) != 0);   // finishes the previous vertex's MIS term
 
@@ -4318,3 +4362,4 @@ __global__ __launch_bounds__(kBlock) void k_accum_add(float *dst, const float *s
 }  // namespace pathed
 
 #include "instance_kernels.h"   // k_instance_records, k_refit_top_pass, k_placement_boxes, k_rebase_prototype_nodes, k_rebase_instance_roots
+#include "instance_motion.h"    // the shutter: k_trace_instanced_motion, k_shade_instanced_motion, k_trace_rays_instanced_motion, k_motion_boxes

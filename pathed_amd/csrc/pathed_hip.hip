@@ -438,6 +438,17 @@ struct PathedScene {
     DeviceBuffer<unsigned int> instanceBad;
     DeviceBuffer<float4> topLo, topHi;
     DeviceBuffer<unsigned char> topReady;
+    // the shutter (pathed_hip_scene_set_instance_motion; instance_motion.h: k_motion_boxes): while hasMotion, the second
+    // transforms and the moving flags the kernels read (motionSet), and what the refit and the rebuild of the top tree read in
+    // place of the records and the prototype boxes.  A call writes the staged twins and swaps them in when nothing is refused.
+    struct MotionBuffers {
+        DeviceBuffer<float4> closeRows, boxRecords, boxTable;
+        DeviceBuffer<int> moving;
+    };
+    bool hasMotion = false;
+    MotionBuffers motion, motionStaged;
+    DMotionSet motionSet = { nullptr, nullptr, 0.f, 1.f };
+    DeviceBuffer<float> motionTransforms;   // the uploaded transforms of the host entry
 
     bool countMode = false;
     bool timeKernels = false;
@@ -718,7 +729,7 @@ void launchTraceStack(PathedScene *scene, const RenderParams &params, hipStream_
     });
 }
 
-// k_trace_instanced<STACK, COUNT>: the three stack-row counts, with and without counting
+// k_trace_instanced<STACK, COUNT>: the three stack-row counts, with and without counting (k_trace_instanced_motion while a shutter is set)
 void launchTraceInstanced(PathedScene *scene, const RenderParams &params, hipStream_t stream)
 {
     // a grid-stride kernel: at most the grid the overflow columns were sized for, at most a wave per batch of slots and one more
@@ -727,6 +738,10 @@ void launchTraceInstanced(PathedScene *scene, const RenderParams &params, hipStr
     const dim3 grid((unsigned)(wanted < scene->traceGrid ? (wanted > 0 ? wanted : 1) : scene->traceGrid)), block(kBlock);
     withBool(scene->countMode, [&](auto COUNT) {
         withStackRows(scene->stackRows, [&](auto STACK) {
+            if (scene->hasMotion) {
+                hipLaunchKernelGGL((k_trace_instanced_motion<STACK, COUNT>), grid, block, stackLdsBytes(STACK), stream, params, scene->instanceSet, scene->motionSet);
+                return;
+            }
             hipLaunchKernelGGL((k_trace_instanced<STACK, COUNT>), grid, block, stackLdsBytes(STACK), stream, params, scene->instanceSet);
         });
     });
@@ -851,6 +866,12 @@ void launchShade(PathedScene *scene, const RenderParams &params, hipStream_t str
     if (scene->instanced) {
         const dim3 slotGrid((unsigned)(params.nSlots / kBlock));
         withBool(ldsMaterials, [&](auto LDS_MATERIALS) {
+            if (scene->hasMotion) {
+                withBool(scene->traits.envOnly, [&](auto ENV_ONLY) {
+                    hipLaunchKernelGGL((k_shade_instanced_motion<LDS_MATERIALS, ENV_ONLY>), slotGrid, dim3(kBlock), 0, stream, params, scene->instanceSet, scene->motionSet);
+                });
+                return;
+            }
             if (scene->traits.envOnly) { hipLaunchKernelGGL((k_shade_instanced<LDS_MATERIALS, true>), slotGrid, dim3(kBlock), 0, stream, params, scene->instanceSet); }
             else { hipLaunchKernelGGL((k_shade_instanced<LDS_MATERIALS, false>), slotGrid, dim3(kBlock), 0, stream, params, scene->instanceSet); }
         });
@@ -3326,6 +3347,46 @@ int pathed_hip_trace(PathedScene *scene, const float *rays, size_t n, int any_hi
     return PATHED_OK;
 }
 
+// pathed_hip_trace with one shutter time per ray (k_trace_rays_instanced_motion<STACK>): the test hook of the shutter
+int pathed_hip_trace_timed(PathedScene *scene, const float *rays, const float *times, size_t n, int any_hit, void *hits)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (!scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "trace_timed: the scene has no instances (pathed_hip_scene_create_instanced makes one that has)"); }
+    if (!scene->hasMotion) { return fail(PATHED_E_INVALID, "trace_timed: the scene has no motion (pathed_hip_scene_set_instance_motion sets one)"); }
+    if (n == 0) { return PATHED_OK; }
+    if (!rays || !times || !hits) { return fail(PATHED_E_INVALID, "null ray, time or hit buffer"); }
+    if (n > (size_t)1 << 28) { return fail(PATHED_E_INVALID, "too many rays in one call"); }
+    for (size_t i = 0; i < n; i++) {
+        // (the moving boxes of the top tree cover the shutter and nothing beyond it)
+        if (!(times[i] >= scene->motionSet.open && times[i] <= scene->motionSet.close)) {
+            return fail(PATHED_E_INVALID, "trace_timed: ray " + std::to_string(i) + " has a time outside the scene's shutter");
+        }
+    }
+    SELECT_DEVICE(scene);
+
+    DeviceBuffer<float4> deviceRays, deviceHits;
+    DeviceBuffer<float> deviceTimes;
+    DeviceBuffer<int> deviceOccluded, deviceOverflow;
+    HIP_TRY(deviceRays.allocate(n * 2));
+    HIP_TRY(deviceTimes.allocate(n));
+    HIP_TRY(hipMemcpy(deviceRays.ptr, rays, n * 8 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(deviceTimes.ptr, times, n * sizeof(float), hipMemcpyHostToDevice));
+    if (any_hit) { HIP_TRY(deviceOccluded.allocate(n)); } else { HIP_TRY(deviceHits.allocate(n)); }
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    const int code = withStackRows(scene->stackRows, [&](auto STACK) {
+        HIP_TRY(deviceOverflow.allocate(stackSpillInts((size_t)grid.x * kBlock, scene->maxStack, STACK)));
+        hipLaunchKernelGGL((k_trace_rays_instanced_motion<STACK>), grid, block, stackLdsBytes(STACK), 0, scene->device, scene->instanceSet, scene->motionSet,
+                           deviceRays.ptr, deviceTimes.ptr, (int)n, any_hit, deviceHits.ptr, deviceOccluded.ptr, deviceOverflow.ptr, scene->maxStack);
+        return (int)PATHED_OK;
+    });
+    if (code != PATHED_OK) { return code; }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (any_hit) { HIP_TRY(hipMemcpy(hits, deviceOccluded.ptr, n * sizeof(int), hipMemcpyDeviceToHost)); }
+    else { HIP_TRY(hipMemcpy(hits, deviceHits.ptr, n * sizeof(float4), hipMemcpyDeviceToHost)); }
+    return PATHED_OK;
+}
+
 int pathed_hip_scene_set_grid_medium(PathedScene *scene, int medium_index, const PathedGridMedium *grid)
 {
     if (!scene || !grid) { return fail(PATHED_E_INVALID, "null scene or grid"); }
@@ -3734,6 +3795,29 @@ int pathed_hip_scene_refit(PathedScene *scene, const float *positions, const flo
     return PATHED_OK;
 }
 
+// The refit of the top tree over the placements' boxes as they stand: the records and the prototype boxes, or, while a
+// shutter is set, what stands in for them (k_motion_boxes).  topLo / topHi / topReady are allocated by the caller.
+// `motion`: the buffers of the shutter to refit over, or null for the static boxes.
+static int refitTopTree(PathedScene *scene, const PathedScene::MotionBuffers *motion, EventTimer &timer, const char *what)
+{
+    const int nInstances = scene->instanceSet.nInstances, topNodes = scene->topNodes;
+    const float4 *records = motion ? motion->boxRecords.ptr : scene->instanceRecords.ptr;
+    const float4 *boxTable = motion ? motion->boxTable.ptr : scene->protoBoxes.ptr;
+    const int nBoxes = (int)((motion ? motion->boxTable.count : scene->protoBoxes.count) / 2);
+    timer.keep(hipMemset(scene->topReady.ptr, 0, 2 * (size_t)topNodes));
+    const dim3 grid((unsigned)((topNodes + kBlock - 1) / kBlock)), block(kBlock);
+    LevelPasses passes{ scene->topReady.ptr, (size_t)topNodes, [&](const unsigned char *in, unsigned char *out) {
+        hipLaunchKernelGGL(k_refit_top_pass, grid, block, 0, nullptr, scene->nodes.ptr, topNodes, records, nInstances,
+                           boxTable, nBoxes, scene->topLo.ptr, scene->topHi.ptr, in, out);
+    } };
+    timer.run([&]() { passes.launchLevels(scene->topDepth); });
+    const bool rootReady = passes.reachRoot(timer);
+    if (!timer.ok()) { return fail(PATHED_E_DEVICE, std::string(what) + ": " + hipGetErrorString(timer.status)); }
+    if (!rootReady) { return fail(PATHED_E_DEVICE, std::string(what) + ": the top tree's root was never reached (a cycle in the tree?)"); }
+    scene->bvhOnHost = false;   // exports download the refitted tree
+    return PATHED_OK;
+}
+
 // ---- moving placements (include/pathed_hip.h; instance_kernels.h: k_instance_records, k_refit_top_pass)
 // The one compute path of both entry points: `deviceTransforms` holds 12 floats per placement on the scene's device.
 static int setInstanceTransforms(PathedScene *scene, const float *deviceTransforms, float *device_ms)
@@ -3770,17 +3854,9 @@ static int setInstanceTransforms(PathedScene *scene, const float *deviceTransfor
         scene->instanceRecords.swap(scene->instanceRecordsStaged);
         scene->instanceSet.records = scene->instanceRecords.ptr;
     }
-    timer.keep(hipMemset(scene->topReady.ptr, 0, 2 * (size_t)topNodes));
-    const dim3 grid((unsigned)((topNodes + kBlock - 1) / kBlock)), block(kBlock);
-    LevelPasses passes{ scene->topReady.ptr, (size_t)topNodes, [&](const unsigned char *in, unsigned char *out) {
-        hipLaunchKernelGGL(k_refit_top_pass, grid, block, 0, nullptr, scene->nodes.ptr, topNodes, scene->instanceRecords.ptr, nInstances,
-                           scene->protoBoxes.ptr, (int)(scene->protoBoxes.count / 2), scene->topLo.ptr, scene->topHi.ptr, in, out);
-    } };
-    timer.run([&]() { passes.launchLevels(scene->topDepth); });
-    const bool rootReady = passes.reachRoot(timer);
-    if (!timer.ok()) { return fail(PATHED_E_DEVICE, std::string("set_instance_transforms: ") + hipGetErrorString(timer.status)); }
-    if (!rootReady) { return fail(PATHED_E_DEVICE, "set_instance_transforms: the top tree's root was never reached (a cycle in the tree?)"); }
-    scene->bvhOnHost = false;   // exports download the refitted tree
+    const int code = refitTopTree(scene, nullptr, timer, "set_instance_transforms");
+    if (code != PATHED_OK) { return code; }
+    scene->hasMotion = false;   // new time-0 transforms end a shutter: the caller sets the motion of the next frame
     if (device_ms) { *device_ms = timer.ms; }
     return PATHED_OK;
 }
@@ -3812,6 +3888,115 @@ int pathed_hip_scene_set_instance_transforms(PathedScene *scene, const float *tr
     return setInstanceTransforms(scene, scene->instanceTransforms.ptr, device_ms);
 }
 
+// ---- the shutter (include/pathed_hip.h; instance_motion.h: k_motion_boxes; instance_kernels.h: k_refit_top_pass)
+// The one compute path of both entry points: `deviceClose` holds 12 floats per placement on the scene's device, or is null,
+// which removes the motion.  Everything is refused before anything is launched, or written beside the live state and adopted
+// when no transform is refused.
+static int checkInstanceMotion(PathedScene *scene, uint32_t n_instances, bool clears, float shutter_open, float shutter_close)
+{
+    if (!scene) { return fail(PATHED_E_INVALID, "null scene"); }
+    if (!scene->instanced) { return fail(PATHED_E_UNSUPPORTED, "set_instance_motion: the scene has no instances (pathed_hip_scene_create_instanced makes one that has)"); }
+    if (clears) { return PATHED_OK; }
+    if (n_instances != (uint32_t)scene->instanceSet.nInstances) { return fail(PATHED_E_INVALID, "set_instance_motion keeps the placements: the instance count must be the scene's"); }
+    if (!(0.f <= shutter_open && shutter_open <= shutter_close && shutter_close <= 1.f)) {
+        return fail(PATHED_E_INVALID, "set_instance_motion: the shutter must satisfy 0 <= open <= close <= 1");
+    }
+    return PATHED_OK;
+}
+
+static int setInstanceMotion(PathedScene *scene, const float *deviceClose, float shutter_open, float shutter_close, float *device_ms)
+{
+    const int nInstances = scene->instanceSet.nInstances;
+    const int topNodes = scene->topNodes, nPrototypes = (int)(scene->protoBoxes.count / 2);
+    if (topNodes <= 0 || (size_t)topNodes > scene->nodes.count / 8) { return fail(PATHED_E_INVALID, "the scene has no top tree"); }
+    if (device_ms) { *device_ms = 0.f; }
+    if (!deviceClose && !scene->hasMotion) { return PATHED_OK; }   // nothing to remove
+    if (!scene->topLo.ptr) {
+        HIP_TRY(scene->topLo.allocate((size_t)topNodes));
+        HIP_TRY(scene->topHi.allocate((size_t)topNodes));
+        HIP_TRY(scene->topReady.allocate(2 * (size_t)topNodes));
+    }
+    PathedScene::MotionBuffers &staged = scene->motionStaged;
+    if (deviceClose && staged.moving.count != (size_t)nInstances + 1) {
+        HIP_TRY(staged.closeRows.allocate((size_t)3 * nInstances + 1));
+        HIP_TRY(staged.moving.allocate((size_t)nInstances + 1));
+        HIP_TRY(staged.boxRecords.allocate((size_t)kInstanceQuads * nInstances + 1));
+        HIP_TRY(staged.boxTable.allocate(2 * ((size_t)nPrototypes + (size_t)nInstances)));
+    }
+    if (deviceClose && !scene->instanceBad.ptr) { HIP_TRY(scene->instanceBad.allocate(2)); }
+    // render calls on a caller's stream may still walk the tree, and the caller's own stream may still write the transforms
+    HIP_TRY(hipDeviceSynchronize());
+    EventTimer timer;
+    if (deviceClose) {
+        const unsigned int clear[2] = { 0u, 0xFFFFFFFFu };
+        unsigned int bad[2] = { 0u, 0u };
+        HIP_TRY(hipMemcpy(scene->instanceBad.ptr, clear, sizeof clear, hipMemcpyHostToDevice));
+        const int threads = nInstances > 2 * nPrototypes ? nInstances : 2 * nPrototypes;
+        if (threads > 0) {
+            timer.run([&]() {
+                hipLaunchKernelGGL(k_motion_boxes, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
+                                   deviceClose, nInstances, scene->instanceRecords.ptr, scene->protoBoxes.ptr, nPrototypes, shutter_open, shutter_close,
+                                   staged.closeRows.ptr, staged.moving.ptr, staged.boxRecords.ptr, staged.boxTable.ptr, scene->instanceBad.ptr);
+            });
+        }
+        if (timer.ok()) { timer.keep(hipMemcpy(bad, scene->instanceBad.ptr, sizeof bad, hipMemcpyDeviceToHost)); }
+        if (!timer.ok()) { return fail(PATHED_E_DEVICE, std::string("set_instance_motion: ") + hipGetErrorString(timer.status)); }
+        if (bad[0] != 0u) {
+            // (the staged buffers are simply not adopted: the scene keeps the motion it had, or none)
+            return fail(PATHED_E_INVALID, "instance transform " + std::to_string(bad[1]) + " of shutter time 1 is not finite or not invertible (" + std::to_string(bad[0])
+                        + " of the " + std::to_string(nInstances) + " transforms are refused; the scene keeps its state)");
+        }
+    }
+    // the refit over the staged boxes (or, removing the motion, over the static ones); the scene's state flips once it succeeded
+    const int code = refitTopTree(scene, deviceClose ? &staged : nullptr, timer, "set_instance_motion");
+    if (code != PATHED_OK) { return code; }
+    if (deviceClose) {
+        scene->motion.closeRows.swap(staged.closeRows);
+        scene->motion.moving.swap(staged.moving);
+        scene->motion.boxRecords.swap(staged.boxRecords);
+        scene->motion.boxTable.swap(staged.boxTable);
+        scene->motionSet.closeRows = scene->motion.closeRows.ptr;
+        scene->motionSet.moving = scene->motion.moving.ptr;
+        scene->motionSet.open = shutter_open;
+        scene->motionSet.close = shutter_close;
+    }
+    scene->hasMotion = deviceClose != nullptr;
+    if (device_ms) { *device_ms = timer.ms; }
+    return PATHED_OK;
+}
+
+int pathed_hip_scene_set_instance_motion_device(PathedScene *scene, const float *d_transforms_close, uint32_t n_instances, float shutter_open, float shutter_close, float *device_ms)
+{
+    const int code = checkInstanceMotion(scene, n_instances, d_transforms_close == nullptr, shutter_open, shutter_close);
+    if (code != PATHED_OK) { return code; }
+    SELECT_DEVICE(scene);
+    return setInstanceMotion(scene, d_transforms_close, shutter_open, shutter_close, device_ms);
+}
+
+int pathed_hip_scene_set_instance_motion(PathedScene *scene, const float *transforms_close, uint32_t n_instances, float shutter_open, float shutter_close, float *device_ms)
+{
+    const int code = checkInstanceMotion(scene, n_instances, transforms_close == nullptr, shutter_open, shutter_close);
+    if (code != PATHED_OK) { return code; }
+    SELECT_DEVICE(scene);
+    if (!transforms_close) { return setInstanceMotion(scene, nullptr, shutter_open, shutter_close, device_ms); }
+    // the endpoints are refused by name before anything is launched (the device kernel repeats the test for the _device entry)
+    for (size_t i = 0; i < (size_t)12 * n_instances; i++) {
+        if (!(transforms_close[i] - transforms_close[i] == 0.f)) {
+            return fail(PATHED_E_INVALID, "instance transform " + std::to_string(i / 12) + " of shutter time 1 is not finite");
+        }
+    }
+    for (uint32_t k = 0; k < n_instances; k++) {
+        float inverse[12];
+        if (!instanceInverse(transforms_close + (size_t)12 * k, inverse)) {
+            return fail(PATHED_E_INVALID, "instance transform " + std::to_string(k) + " of shutter time 1 is not invertible");
+        }
+    }
+    const size_t floats = (size_t)12 * n_instances;
+    if (scene->motionTransforms.count != floats + 1) { HIP_TRY(scene->motionTransforms.allocate(floats + 1)); }
+    if (floats > 0) { HIP_TRY(hipMemcpy(scene->motionTransforms.ptr, transforms_close, floats * sizeof(float), hipMemcpyHostToDevice)); }
+    return setInstanceMotion(scene, scene->motionTransforms.ptr, shutter_open, shutter_close, device_ms);
+}
+
 // ---- rebuilding the top tree (include/pathed_hip.h; lbvh.hip: buildTopBvhOnDevice; instance_kernels.h: k_placement_boxes,
 // k_rebase_prototype_nodes, k_rebase_instance_roots).  Everything new is built beside the live arrays -- node array
 // [new top | prototypes' trees], leaf triangles [world in the new leaf order | prototypes], records with their protoRoot
@@ -3841,8 +4026,12 @@ int pathed_hip_scene_rebuild_top(PathedScene *scene, int32_t builder, float *dev
     const auto giveUp = [&](const std::string &what) { return fail(PATHED_E_DEVICE, "rebuild_top: " + what); };
     if (nInstances > 0) {
         timer.run([&]() {
+            // (while a shutter is set: over the moving boxes, from what k_motion_boxes left in place of records and prototype boxes)
+            const float4 *records = scene->hasMotion ? scene->motion.boxRecords.ptr : scene->instanceRecords.ptr;
+            const float4 *boxTable = scene->hasMotion ? scene->motion.boxTable.ptr : scene->protoBoxes.ptr;
+            const int nBoxes = (int)((scene->hasMotion ? scene->motion.boxTable.count : scene->protoBoxes.count) / 2);
             hipLaunchKernelGGL(k_placement_boxes, dim3((unsigned)((nInstances + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr,
-                               scene->instanceRecords.ptr, nInstances, scene->protoBoxes.ptr, (int)(scene->protoBoxes.count / 2), boxes.ptr);
+                               records, nInstances, boxTable, nBoxes, boxes.ptr);
         });
     }
     if (!timer.ok()) { return giveUp(hipGetErrorString(timer.status)); }
@@ -3970,7 +4159,7 @@ int pathed_hip_get_stats(PathedScene *scene, PathedStats *out)
     out->bvh_build_ms = scene->bvhBuildMs;
     out->bvh_builder = (uint32_t)scene->bvhBuilder;
     out->trace_launches_all = (uint32_t)scene->traceLaunchesAll;
-    out->path_kernel = scene->instanced ? 10u : scene->lastCallFeatures ? 8u : (scene->lastCallList && !usesVolumeKernel(scene)) ? 1u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? (scene->anisotropic ? 11u : 9u) : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
+    out->path_kernel = scene->instanced ? (scene->hasMotion ? 11u : 10u) : scene->lastCallFeatures ? 8u : (scene->lastCallList && !usesVolumeKernel(scene)) ? 1u : usesVolumeKernel(scene) ? (scene->integrator == PATHED_INTEGRATOR_BASIC_VOLUME ? (scene->anisotropic ? 11u : 9u) : 4u) : scene->fusedPath ? 3u : scene->lastCallHybrid ? 7u : scene->lastCallWave ? 6u : scene->splitShade ? 5u : (scene->stagedShade ? 2u : 1u);
     if (tuningEnv("PATHED_SHADE_PROFILE")) {   // counters exist in -DPATHED_SHADE_PROFILE builds only
         static const char *regions[11] = { "all waves", "active slots", "makeIsect (hit)", "camera-ray vertex", "finish previous MIS term",
                                            "new vertex: BSDF sample", "light sampling", "sample finished", "startSample (regeneration)", "shadow ray pushed",

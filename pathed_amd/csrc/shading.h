@@ -9,6 +9,7 @@
 #pragma once
 
 #include "device_scene.h"
+#include "sample_stream.h"
 
 namespace pathed {
 
@@ -63,36 +64,7 @@ typedef SceneTraits<(1u << 0) | (1u << 4) | (1u << 5), false, true, false, false
 __host__ __device__ inline float twoPiTimes(float u) { return (float)(6.283185307179586476925286766559 * (double)u); }
 
 // ---------------------------------------------------------------------------- rng
-// Counter-based stream u(seed, pixel, sample, dimension); replaces the reference's
-// shared, unseedable mt19937 (src/random_generator.cpp:4-6).  Two bijective 32-bit
-// mixers keyed by pixel and sample, so no two (pixel, sample) pairs share a stream.
-
-__host__ __device__ inline uint32_t mix32(uint32_t x)
-{
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-struct Rng {
-    uint32_t k0, k1;
-    uint32_t dimension;
-
-    __host__ __device__ inline float next()
-    {
-        const uint32_t bits = mix32(k0 + mix32(k1 + dimension * 0x9e3779b9u));
-        dimension++;
-        // 24 bits scaled into [0, 1 - 2^-23): the range of the reference generator
-        return (float)(bits >> 8) * 5.9604638e-08f;
-    }
-};
-
-__host__ __device__ inline void makeKey(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t *k0, uint32_t *k1)
-{
-    *k0 = mix32(pixel ^ mix32((uint32_t)seed));
-    *k1 = mix32(sample ^ mix32((uint32_t)(seed >> 32) ^ 0x9e3779b9u));
-}
+// mix32, Rng and makeKey: sample_stream.h (the host programs of the tests read them too)
 
 // dimension layout: [0,1] pixel jitter (X first, src/camera.cpp:51-52);
 // vertex k >= 1 owns 8 dimensions from 2 + 8(k-1): +0..2 BSDF, +3 light choice, +4,+5 light

@@ -572,6 +572,35 @@ __host__ __device__ inline V3 flattenPoint(const float *m, V3 p) { float out[3];
 __host__ __device__ inline V3 flattenDirection(const float *m, V3 d) { float out[3]; flattenDirection(m, d.x, d.y, d.z, out); return v3(out[0], out[1], out[2]); }
 __host__ __device__ inline V3 flattenNormal(const float *inverse, V3 n) { float out[3]; flattenNormal(inverse, n.x, n.y, n.z, out); return v3(out[0], out[1], out[2]); }
 
+// The shutter (instances.h: interpolateTransform, sampleTime; DESIGN.md section 4.6d "Shutter"): a scene with motion holds a
+// second transform per placement, the one of shutter time 1; the record's own is the one of time 0.  A placement whose two
+// transforms are bit-equal does not move (moving[k] == 0): it is walked and shaded through its record, as in a scene without
+// motion.  A ray of time t enters a moving placement through instanceInverse(M(t)); where M(t) is not invertible (a half turn
+// interpolated linearly is singular at t = 0.5) the ray skips the placement.
+struct DMotionSet {
+    const float4 *closeRows;   // 3 per placement: the rows of the transform at shutter time 1
+    const int *moving;         // per placement: do the two transforms differ in any bit
+    float open, close;         // the shutter, 0 <= open <= close <= 1
+};
+// where a traversal takes its ray's time from: nowhere (scenes without motion, the default), or a callable the walk asks
+// when the ray first meets a MOVING placement -- most rays of a scene where three of 400 placements move never do
+struct NoShutter {
+    static constexpr bool shutter = false;
+    __device__ float operator()() const { return 0.f; }
+};
+
+// the transform and the inverse of placement `placement` at `time`: false where M(time) is not invertible
+__device__ inline bool movingTransform(const float4 *record, const DMotionSet &motion, int placement, float time, float *m, float *inverse)
+{
+    const float4 a0 = record[0], a1 = record[1], a2 = record[2];
+    const float4 *rows = motion.closeRows + (size_t)3 * placement;
+    const float4 b0 = rows[0], b1 = rows[1], b2 = rows[2];
+    const float a[12] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w };
+    const float b[12] = { b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w };
+    interpolateTransform(a, b, time, m);
+    return instanceInverse(m, inverse);
+}
+
 // leafStep for the two-level tree: the leaf's stored ids plus `base` are the virtual ids the acceptance rule compares
 template <bool COUNT, int ROWS, int STRIDE>
 __device__ inline bool leafStepInstanced(const TraceGeometry &g, const LaneStack &stack, LaneRay &ray, int base, TraceCounters *counters)
@@ -606,10 +635,14 @@ __device__ inline bool leafStepInstanced(const TraceGeometry &g, const LaneStack
 // pushes the sentinel, takes the ray into the prototype's space and goes on at the prototype's root; popping the sentinel
 // brings the world ray back (worldO / worldD: the lane reloads it from where the caller read it, so it costs no registers meanwhile).
 // maxStack = the top tree's bound + the deepest prototype's + 1 (the sentinel).
-template <bool COUNT, int ROWS, int STRIDE>
+// TIME (above: NoShutter by default, which compiles the shutter out): on the instance leaf of a MOVING placement the lane asks
+// (*time)() for the ray's time, interpolates the 12 floats and inverts them -- about 40 fp64 operations and 9 divisions, on
+// instance leaves only, never on the inner-node path -- and enters the prototype as it enters any other.
+template <bool COUNT, int ROWS, int STRIDE, typename TIME = NoShutter>
 __device__ inline void traverseInstanced(
     const TraceGeometry &g, const DInstanceSet &instances, const LaneStack &stack, int maxStack,
-    const float4 *worldO, const float4 *worldD, LaneRay &ray, TraceCounters *counters
+    const float4 *worldO, const float4 *worldD, LaneRay &ray, TraceCounters *counters,
+    const DMotionSet *motion = nullptr, TIME *time = nullptr
 ) {
     if (g.nNodes <= 0) { return; }
     int base = 0;
@@ -632,7 +665,16 @@ __device__ inline void traverseInstanced(
         } else if (ray.pendingLeaf & kInstanceLeafBit) {
             const float4 *record = instances.records + (size_t)kInstanceQuads * (ray.pendingLeaf & (kInstanceLeafBit - 1));
             const float4 i0 = record[3], i1 = record[4], i2 = record[5], ids = record[6];
-            const float inverse[12] = { i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w, i2.x, i2.y, i2.z, i2.w };
+            float inverse[12] = { i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w, i2.x, i2.y, i2.z, i2.w };
+            if (TIME::shutter) {
+                const int placement = ray.pendingLeaf & (kInstanceLeafBit - 1);
+                float m[12];
+                if (motion->moving[placement] && !movingTransform(record, *motion, placement, (*time)(), m, inverse)) {
+                    ray.pendingLeaf = 0;
+                    done = popWork<ROWS, STRIDE>(stack, ray);
+                    continue;
+                }
+            }
             if (ray.sp < maxStack) { stackWrite<ROWS, STRIDE>(stack, ray.sp, kEmptyChild); ray.sp++; }
             const float kHuge = 3e30f;
             const float4 wo = *worldO, wd = *worldD;

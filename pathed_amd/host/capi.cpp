@@ -42,6 +42,15 @@ const PathedSceneDesc *pathed_host_scene_desc(void *handle)
     return &((LoadedScene *)handle)->desc;
 }
 
+// the placements of shutter time 1 of a loaded scene (scene_loader.h: FlatScene::instancesClose), 12 floats per instance, or
+// null where nothing moves
+const float *pathed_host_scene_instances_close(void *handle)
+{
+    if (!handle) { return nullptr; }
+    LoadedScene *loaded = static_cast<LoadedScene *>(handle);
+    return loaded->scene.moves() ? loaded->scene.instancesClose.data() : nullptr;
+}
+
 // the instanced geometry of a loaded scene (scene_loader.h: FlatScene::prototypes / instances), or null for a flat scene
 const PathedInstanceDesc *pathed_host_scene_instances(void *handle)
 {
@@ -184,6 +193,11 @@ static std::string flatSceneDigest(const pathed::FlatScene &flat)
     add(desc.media, sizeof(PathedMedium) * desc.n_media);
     for (const PathedPrototype &prototype : flat.prototypes) { add(&prototype.first_geom, sizeof(int32_t)); add(&prototype.n_geoms, sizeof(int32_t)); }
     for (const PathedInstance &instance : flat.instances) { add(&instance.prototype, sizeof(int32_t)); add(instance.transform, sizeof instance.transform); }
+    if (flat.moves()) {   // (a scene where nothing moves keeps the digest it had)
+        add(flat.instancesClose.data(), flat.instancesClose.size() * sizeof(float));
+        add(&flat.shutterOpen, sizeof(float));
+        add(&flat.shutterClose, sizeof(float));
+    }
     for (const pathed::FlatGrid &grid : flat.grids) {   // the .vol file's bytes as loaded, and what the scene file says about the medium
         add(&grid.medium, sizeof grid.medium);
         add(&grid.desc.cells_x, sizeof(uint32_t)); add(&grid.desc.cells_y, sizeof(uint32_t)); add(&grid.desc.cells_z, sizeof(uint32_t));
@@ -237,6 +251,12 @@ int runJob(const std::string &jobPath, const std::string &assetRootOverride)
         struct CommGuard { PathedComm *&comm; ~CommGuard() { if (comm) { pathed_hip_comm_destroy(comm); } } } commGuard{ earlyComm };
         const auto loadBegin = std::chrono::steady_clock::now();
         FlatScene flat = loadScene(job.scene(), width, height, assetRoot);
+        // "shutter": the interval the scene file's moving placements ("transform_close") are sampled over; read before the digest is
+        // taken, which holds it: a state file of another shutter is another job's
+        job.shutter(&flat.shutterOpen, &flat.shutterClose);
+        if (job.hasShutter() && !flat.moves()) {
+            throw std::runtime_error("job: \"shutter\" does not go with a scene where nothing moves (no \"instanced\" model carries \"transform_close\")");
+        }
         const std::string sceneDigest = flatSceneDigest(flat);
         if (flat.instanced()) {
             // a scene file with "instance" / "instanced" models: what the library refuses beside instances (include/pathed_hip.h)

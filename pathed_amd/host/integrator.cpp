@@ -154,6 +154,12 @@ void Scene::upload(int bvhBuilderPlusOne)
             } else if (pathed_hip_scene_create_ex(&desc, &options, &m_handles[r]) != PATHED_OK) {
                 throw std::runtime_error(hipError("pathed_hip_scene_create_ex"));
             }
+            if (m_flat.moves()) {   // the scene file's "transform_close" placements over the job's "shutter"
+                if (pathed_hip_scene_set_instance_motion(m_handles[r], m_flat.instancesClose.data(), (uint32_t)m_flat.instances.size(),
+                                                         m_flat.shutterOpen, m_flat.shutterClose, nullptr) != PATHED_OK) {
+                    throw std::runtime_error(hipError("pathed_hip_scene_set_instance_motion"));
+                }
+            }
             for (size_t i = 0; i < m_flat.grids.size(); i++) {   // the scene file's voxel-grid media, each on its medium slot
                 if (pathed_hip_scene_set_grid_medium(m_handles[r], m_flat.grids[i].medium, m_flat.gridDesc(i)) != PATHED_OK) {
                     throw std::runtime_error(hipError("pathed_hip_scene_set_grid_medium"));

@@ -78,6 +78,20 @@ std::vector<std::string> Job::features() const
     return names;
 }
 
+void Job::shutter(float *open, float *close) const
+{
+    *open = 0.f;
+    *close = 1.f;
+    const Json &value = m_json["shutter"];
+    if (value.isNull()) { return; }
+    const char *rule = "job: \"shutter\" must be [open, close] with 0 <= open <= close <= 1";
+    if (!value.isArray() || value.elements().size() != 2 || !value.elements()[0].isNumber() || !value.elements()[1].isNumber()) { throw std::runtime_error(rule); }
+    const float first = (float)value.elements()[0].asNumber(), last = (float)value.elements()[1].asNumber();
+    if (!(0.f <= first && first <= last && last <= 1.f)) { throw std::runtime_error(rule); }
+    *open = first;
+    *close = last;
+}
+
 Job::NoiseSettings Job::noise() const
 {
     NoiseSettings settings;

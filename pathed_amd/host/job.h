@@ -25,6 +25,10 @@
 //   "stderr_image" (false; implied by "target_noise"): write the per-channel standard error of the mean as auto-stderr*.exr
 //               beside every auto*.exr and record the figure in the log and in metrics.json ("noise", "stopped_on_noise").
 //               Neither key goes with "resume": the state file holds no squares.  Bad values are refused by name.
+//   "shutter" (absent = [0, 1]): [open, close] with 0 <= open <= close <= 1.  A scene file whose top-level "instanced" models
+//               carry "transform_close" renders with those placements moving from "transform" (shutter time 0) to
+//               "transform_close" (time 1): every sample sees them at its own time in [open, close] (include/pathed_hip.h:
+//               pathed_hip_scene_set_instance_motion).  Refused by name on a scene where nothing moves,
 //   "adaptive" (false; needs "target_noise"): render on only the pixels that are still noisy.  The schedule is fixed:
 //                 1. min("min_spp", "spp") samples of every pixel (pathed_hip_render_moments_device);
 //                 2. rounds: each selects, among the pixels still active, those whose OWN error e exceeds "target_noise"
@@ -104,6 +108,11 @@ public:
         bool adaptive = false; // "adaptive": pixel lists (needs a target)
     };
     NoiseSettings noise() const;
+    // "shutter": [open, close] with 0 <= open <= close <= 1, the interval the moving placements of the scene file
+    // ("transform_close") are sampled over; absent: [0, 1].  A bad value throws an error that names the key; so does the
+    // key on a scene where nothing moves (the caller's check: it knows the scene).
+    bool hasShutter() const { return !m_json["shutter"].isNull(); }
+    void shutter(float *open, float *close) const;
     int gpu() const { return m_json["gpu"].isNumber() ? m_json["gpu"].asInt() : 0; }
     std::string assetRoot() const { return m_json["asset_root"].isString() ? m_json["asset_root"].asString() : ""; }
     std::string bvhBuilder() const { return m_json["bvh_builder"].isString() ? m_json["bvh_builder"].asString() : "auto"; }

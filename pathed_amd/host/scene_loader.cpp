@@ -25,6 +25,8 @@ using MaterialMap = std::map<std::string, int>;
 struct NestedPlacement {
     int prototype;
     double transform[12];   // row-major 3 x 4, the floats of the file
+    bool moves = false;     // "transform_close": the placement at shutter time 1 (top-level "instanced" models only)
+    double transformClose[12];
 };
 struct PrototypeBuild {
     std::string name;
@@ -800,6 +802,20 @@ NestedPlacement parseInstanced(const Json &model, LoaderContext &context)
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 4; c++) { placement.transform[4 * r + c] = (double)columnMajor[4 * c + r]; }
     }
+    // "transform_close": the same 16 numbers for shutter time 1 (include/pathed_hip.h: pathed_hip_scene_set_instance_motion)
+    if (!model["transform_close"].isNull()) {
+        if (context.prototype) {
+            throw SceneLoadError("instanced \"" + name + "\": \"transform_close\" on a nested \"instanced\" model is not supported (a top-level placement moves as a whole)");
+        }
+        if (!model["transform_close"].isArray() || model["transform_close"].elements().size() != 16) {
+            throw SceneLoadError("instanced \"" + name + "\": transform_close must be an array of 16 numbers (column-major)");
+        }
+        for (int i = 0; i < 16; i++) { columnMajor[i] = parseFloat(model["transform_close"].elements()[(size_t)i], "instanced transform_close"); }
+        placement.moves = true;
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 4; c++) { placement.transformClose[4 * r + c] = (double)columnMajor[4 * c + r]; }
+        }
+    }
     return placement;
 }
 
@@ -916,26 +932,38 @@ void finishInstances(LoaderContext &context)
 {
     FlatScene &scene = *context.scene;
     if (context.prototypes.empty()) { return; }
-    struct Placement { int prototype; float transform[12]; };
+    // (a placement with "transform_close" carries its transform of shutter time 1, the others their one transform twice; what
+    // the outer placement holds inside moves with it: the composition is linear in the outer transform)
+    struct Placement { int prototype; float transform[12]; bool moves; float transformClose[12]; };
     std::vector<Placement> placements;
-    auto rounded = [](int prototype, const double *transform) {
+    auto rounded = [](int prototype, const double *transform, bool moves, const double *transformClose) {
         Placement placement;
         placement.prototype = prototype;
-        for (int i = 0; i < 12; i++) { placement.transform[i] = (float)transform[i]; }
+        placement.moves = moves;
+        for (int i = 0; i < 12; i++) {
+            placement.transform[i] = (float)transform[i];
+            placement.transformClose[i] = moves ? (float)transformClose[i] : placement.transform[i];
+        }
         return placement;
     };
-    for (const NestedPlacement &outer : context.worldPlacements) {
-        placements.push_back(rounded(outer.prototype, outer.transform));
-        for (const NestedPlacement &inner : context.prototypes[(size_t)outer.prototype].nested) {
-            double composed[12];
-            for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 4; c++) {
-                    double sum = 0.0;
-                    for (int k = 0; k < 3; k++) { sum += outer.transform[4 * r + k] * inner.transform[4 * k + c]; }
-                    composed[4 * r + c] = sum + (c == 3 ? outer.transform[4 * r + 3] : 0.0);
-                }
+    auto compose = [](const double *outer, const double *inner, double *composed) {
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 4; c++) {
+                double sum = 0.0;
+                for (int k = 0; k < 3; k++) { sum += outer[4 * r + k] * inner[4 * k + c]; }
+                composed[4 * r + c] = sum + (c == 3 ? outer[4 * r + 3] : 0.0);
             }
-            placements.push_back(rounded(inner.prototype, composed));
+        }
+    };
+    bool anyMoves = false;
+    for (const NestedPlacement &outer : context.worldPlacements) {
+        anyMoves = anyMoves || outer.moves;
+        placements.push_back(rounded(outer.prototype, outer.transform, outer.moves, outer.transformClose));
+        for (const NestedPlacement &inner : context.prototypes[(size_t)outer.prototype].nested) {
+            double composed[12], composedClose[12];
+            compose(outer.transform, inner.transform, composed);
+            if (outer.moves) { compose(outer.transformClose, inner.transform, composedClose); }
+            placements.push_back(rounded(inner.prototype, composed, outer.moves, composedClose));
         }
     }
     // emissive faces: ordinary world triangles and ordinary lights, once per placement
@@ -947,6 +975,10 @@ void finishInstances(LoaderContext &context)
     for (const Placement &placement : placements) {
         const MeshBuffers &source = emissive[(size_t)placement.prototype];
         if (source.indices.empty()) { continue; }
+        if (placement.moves) {
+            // the baked emitters are static world triangles: they would stay behind
+            throw SceneLoadError("instanced \"" + context.prototypes[(size_t)placement.prototype].name + "\": \"transform_close\" on a placement of a prototype that holds an emitter is not supported (emitters do not move)");
+        }
         float inverse[12];
         if (!instanceInverse(placement.transform, inverse)) { throw SceneLoadError("instanced \"" + context.prototypes[(size_t)placement.prototype].name + "\": the transform is not invertible"); }
         MeshBuffers baked = source;
@@ -974,6 +1006,7 @@ void finishInstances(LoaderContext &context)
         instance.prototype = abiIndex[(size_t)placement.prototype];
         std::memcpy(instance.transform, placement.transform, sizeof instance.transform);
         scene.instances.push_back(instance);
+        if (anyMoves) { scene.instancesClose.insert(scene.instancesClose.end(), placement.transformClose, placement.transformClose + 12); }
     }
 }
 

@@ -85,6 +85,14 @@ struct FlatScene {
     std::vector<std::string> prototypeNames;
     std::vector<PathedInstance> instances;
     bool instanced() const { return !prototypes.empty() || !instances.empty(); }
+    // The shutter (include/pathed_hip.h: pathed_hip_scene_set_instance_motion): a top-level "instanced" model may carry
+    // "transform_close", 16 numbers like "transform", its placement at shutter time 1.  When any does, instancesClose holds 12
+    // floats per entry of `instances` (a placement that does not move: its transform again) and the scene is created with that
+    // motion over [shutterOpen, shutterClose] -- the job key "shutter", [0, 1] by default.  Refused by name: the key on a
+    // nested "instanced" model, and on a placement of a prototype that holds an emitter (baked emitters would stay behind).
+    std::vector<float> instancesClose;
+    float shutterOpen = 0.f, shutterClose = 1.f;
+    bool moves() const { return !instancesClose.empty(); }
     PathedInstanceDesc instanceDesc() const;
 
     // valid as long as this FlatScene is alive and unmodified

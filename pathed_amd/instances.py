@@ -78,6 +78,72 @@ def placement_box(transform, proto_lo, proto_hi):
     return (lo - pad).astype(np.float32), (hi + pad).astype(np.float32)
 
 
+DIM_TIME = 0xFFFFFFFF   # pathed_amd/csrc/sample_stream.h: kDimTime
+
+
+def interpolate_transforms(a, b, t):
+    """The placements' transforms at shutter time t (pathed_amd/csrc/instances.h: interpolateTransform), float32, one rounding per
+    operation: m[i] = ((1 - t) * a[i]) + (t * b[i]).  `a` (time 0) and `b` (time 1) are (n, 12) or (12,) float32; t = 0 and t = 1
+    give the bits of a and of b apart from the sign of a zero."""
+    a, b, t = _f32(a), _f32(b), np.float32(t)
+    s = np.float32(1.0) - t
+    return ((s * a).astype(np.float32) + (t * b).astype(np.float32)).astype(np.float32)
+
+
+def _mix32(x):
+    """pathed_amd/csrc/sample_stream.h: mix32, on uint32 (numpy wraps modulo 2^32)"""
+    x = np.asarray(x, dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        x = x ^ (x >> np.uint32(16))
+        x = x * np.uint32(0x7feb352d)
+        x = x ^ (x >> np.uint32(15))
+        x = x * np.uint32(0x846ca68b)
+        x = x ^ (x >> np.uint32(16))
+    return x
+
+
+def stream_value(seed, pixel, sample, dimension):
+    """u(seed, pixel, sample, dimension) of the counter-based stream (sample_stream.h: makeKey, Rng::next), float32; pixel, sample
+    and dimension may be arrays."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    pixel, sample, dimension = (np.asarray(v, dtype=np.uint32) for v in (pixel, sample, dimension))
+    with np.errstate(over="ignore"):
+        k0 = _mix32(pixel ^ _mix32(np.uint32(seed & 0xFFFFFFFF)))
+        k1 = _mix32(sample ^ _mix32(np.uint32(seed >> 32) ^ np.uint32(0x9e3779b9)))
+        bits = _mix32(k0 + _mix32(k1 + dimension * np.uint32(0x9e3779b9)))
+    return ((bits >> np.uint32(8)).astype(np.float32) * np.float32(5.9604638e-08)).astype(np.float32)
+
+
+def sample_time(seed, pixel, sample, open, close):
+    """The shutter time of a sample (instances.h: sampleTime): t = open + (close - open) * u in float32, u the sample's stream at
+    dimension DIM_TIME -- a pure function of (seed, pixel, sample)."""
+    open, close = np.float32(open), np.float32(close)
+    u = stream_value(seed, pixel, sample, DIM_TIME)
+    return (open + ((close - open) * u).astype(np.float32)).astype(np.float32)
+
+
+def moving_placement_box(a, b, open, close, proto_lo, proto_hi):
+    """A moving placement's world box over the shutter (instances.h: movingPlacementBox, where the pad is derived): the union of
+    placement_box at `open` and at `close`, widened per axis by the static pad over the union plus 1e-6 of
+    sum_j max(|a_ij|, |b_ij|) max(|lo_j|, |hi_j|) + max(|a_i3|, |b_i3|) for the roundings of the interpolated matrix."""
+    a, b = _f32(a).reshape(12), _f32(b).reshape(12)
+    proto_lo, proto_hi = _f32(proto_lo).reshape(3), _f32(proto_hi).reshape(3)
+    lo0, hi0 = placement_box(interpolate_transforms(a, b, open), proto_lo, proto_hi)
+    lo1, hi1 = placement_box(interpolate_transforms(a, b, close), proto_lo, proto_hi)
+    box_lo, box_hi = _host_min(lo0, lo1), _host_max(hi0, hi1)
+    extent = _host_max(np.abs(proto_lo), np.abs(proto_hi))
+    lo, hi = np.zeros(3, dtype=np.float32), np.zeros(3, dtype=np.float32)
+    for i in range(3):
+        reach = _host_max(np.abs(a[4 * i + 3]), np.abs(b[4 * i + 3]))
+        for j in range(3):
+            reach = np.float32(reach + np.float32(_host_max(np.abs(a[4 * i + j]), np.abs(b[4 * i + j])) * extent[j]))
+        static = np.float32(np.float32(np.float32(1e-5) * _host_max(np.float32(1.0), _host_max(np.abs(box_lo[i]), np.abs(box_hi[i]))))
+                            + np.float32(np.float32(1e-5) * np.float32(box_hi[i] - box_lo[i])))
+        pad = np.float32(static + np.float32(np.float32(1e-6) * reach))
+        lo[i], hi[i] = np.float32(box_lo[i] - pad), np.float32(box_hi[i] + pad)
+    return lo, hi
+
+
 def flatten_points(transform, points):
     """x' = ((m[0] x + m[1] y) + m[2] z) + m[3], ... in float32, for (n, 3) float32 points."""
     m = _f32(transform).reshape(12)

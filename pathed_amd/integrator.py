@@ -490,6 +490,55 @@ class HipScene:
             self.instance_set.set_transforms(transforms)
         return float(ms.value)
 
+    def set_instance_motion(self, transforms_close, shutter=(0.0, 1.0)):
+        """The placements at shutter time 1 (pathed_hip_scene_set_instance_motion); the scene's current transforms are the
+        placements at time 0.  Every sample then sees each moving placement at its own time, `instances.sample_time` of
+        (seed, pixel, sample), under `instances.interpolate_transforms`; a placement whose two transforms are bit-equal does not
+        move.  `transforms_close` as set_instance_transforms takes them (numpy, or a torch tensor on the scene's device);
+        `shutter` = (open, close) with 0 <= open <= close <= 1.  Returns the device time of the kernels in milliseconds."""
+        ms = C.c_float(0.0)
+        shutter_open, shutter_close = C.c_float(float(shutter[0])), C.c_float(float(shutter[1]))
+        if hasattr(transforms_close, "data_ptr"):
+            import torch
+            if not (transforms_close.is_cuda and transforms_close.device.index == self.device):
+                raise ValueError("the transforms tensor must live on the scene's device (cuda:%d)" % self.device)
+            if transforms_close.dtype != torch.float32 or not transforms_close.is_contiguous() or transforms_close.numel() % 12 != 0:
+                raise ValueError("the transforms tensor must be contiguous float32, 12 values per instance")
+            if transforms_close.numel() == 0:
+                raise ValueError("an empty tensor names no motion: clear_instance_motion() removes one")
+            code = self._lib.pathed_hip_scene_set_instance_motion_device(self._handle, C.c_void_p(transforms_close.data_ptr()), transforms_close.numel() // 12,
+                                                                        shutter_open, shutter_close, C.byref(ms))
+            _check(self._lib, code, "pathed_hip_scene_set_instance_motion_device")
+            return float(ms.value)
+        transforms_close = np.ascontiguousarray(transforms_close, dtype=np.float32).reshape(-1, 12)
+        padded = transforms_close if len(transforms_close) else np.zeros((1, 12), dtype=np.float32)   # (an empty array has no address to pass)
+        code = self._lib.pathed_hip_scene_set_instance_motion(self._handle, padded.ctypes.data_as(C.POINTER(C.c_float)), len(transforms_close),
+                                                             shutter_open, shutter_close, C.byref(ms))
+        _check(self._lib, code, "pathed_hip_scene_set_instance_motion")
+        return float(ms.value)
+
+    def clear_instance_motion(self):
+        """Removes the motion (pathed_hip_scene_set_instance_motion with no transforms): the static boxes are restored and
+        renders are the static scene's bits again.  Returns the device time of the refit in milliseconds."""
+        ms = C.c_float(0.0)
+        code = self._lib.pathed_hip_scene_set_instance_motion(self._handle, None, 0, C.c_float(0.0), C.c_float(1.0), C.byref(ms))
+        _check(self._lib, code, "pathed_hip_scene_set_instance_motion")
+        return float(ms.value)
+
+    def trace_timed(self, rays, times, any_hit=False):
+        """`trace` with one shutter time per ray, on a scene with motion (pathed_hip_trace_timed)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        times = np.ascontiguousarray(times, dtype=np.float32).reshape(-1)
+        n = rays.shape[0]
+        if len(times) != n:
+            raise ValueError("%d times for %d rays" % (len(times), n))
+        out = np.zeros(n, dtype=np.int32) if any_hit else np.zeros((n, 4), dtype=np.float32)
+        code = self._lib.pathed_hip_trace_timed(
+            self._handle, rays.ctypes.data_as(C.POINTER(C.c_float)), times.ctypes.data_as(C.POINTER(C.c_float)), n, 1 if any_hit else 0,
+            out.ctypes.data_as(C.c_void_p))
+        _check(self._lib, code, "pathed_hip_trace_timed")
+        return out
+
     def rebuild_top(self, builder="ploc"):
         """A new top tree over the world triangles and the placements' current world boxes, built on the device
         (pathed_hip_scene_rebuild_top): what follows set_instance_transforms when the placements were scattered far, since a

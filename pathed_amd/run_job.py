@@ -97,7 +97,17 @@ def main(argv=None):
     if any(not abs(g) < _capi.PHASE_ISOTROPIC_BELOW for _, g in scene.phases) and job["integrator"] == "VolumePathTracer":
         # what the library refuses on such a scene stops the job here, by name, before a tree is built ("adaptive": above)
         raise SystemExit("pathed_amd.run_job: the VolumePathTracer does not render a scene with a henyey-greenstein medium (the BasicVolumeIntegrator does)")
+    # "shutter": the interval the scene file's moving placements ("transform_close") are sampled over, as the C++ host reads it: refused
+    # by name before a tree is built or anything is uploaded
+    shutter = job.get("shutter", [0.0, 1.0])
+    if not (isinstance(shutter, list) and len(shutter) == 2 and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in shutter)
+            and 0.0 <= np.float32(shutter[0]) <= np.float32(shutter[1]) <= 1.0):
+        raise SystemExit("pathed_amd.run_job: job: \"shutter\" must be [open, close] with 0 <= open <= close <= 1")
+    if "shutter" in job and scene.instances_close is None:
+        raise SystemExit("pathed_amd.run_job: job: \"shutter\" does not go with a scene where nothing moves (no \"instanced\" model carries \"transform_close\")")
     gpu = HipScene(scene.desc, device=local_rank, grids=scene.grids, phases=scene.phases, prototypes=scene.prototypes, instances=scene.instances, bvh_builder=(lambda name: ("ploc" if world_size > 1 and scene.n_triangles > 1000000 else "sah") if name == "auto" else name)(job.get("bvh_builder", "auto")))
+    if scene.instances_close is not None:
+        gpu.set_instance_motion(scene.instances_close, shutter=(shutter[0], shutter[1]))
     gpu.set_integrator(job["integrator"])
     host = _capi.load_host()
     stream = torch.cuda.current_stream().cuda_stream

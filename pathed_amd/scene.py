@@ -35,6 +35,13 @@ class LoadedScene:
             described = found.contents
             self.prototypes = [(described.prototypes[i].first_geom, described.prototypes[i].n_geoms) for i in range(described.n_prototypes)]
             self.instances = [(described.instances[i].prototype, [float(x) for x in described.instances[i].transform]) for i in range(described.n_instances)]
+        # top-level "instanced" models with "transform_close": the placements at shutter time 1, (n, 12) float32 in instance order
+        # for HipScene.set_instance_motion (a placement that does not move: its transform again); None = nothing moves
+        self.instances_close = None
+        close = self._host.pathed_host_scene_instances_close(self._handle) if self.instances else None
+        if close:
+            import numpy as np
+            self.instances_close = np.ctypeslib.as_array(close, shape=(len(self.instances), 12)).astype(np.float32).copy()
         self.width = width
         self.height = height
 
